@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the raycast hot path on MI355X, one JSON line per run.
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3|c4|c5] [--camera far|mid|near]
+  python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3|c4|c5] [--camera far|mid|near] [--dump-outputs DIR]
 
 Workloads (BASELINE.json configs[1..4]; scenes are synthetic, see cuda-raytracing_amd/scenes.py):
   c2  70k-triangle blob, 1920x1080, 1 primary ray per pixel -- the workload the metric is quoted on; the default
@@ -11,7 +11,8 @@ Workloads (BASELINE.json configs[1..4]; scenes are synthetic, see cuda-raytracin
   c6  the atrium generator at 4.07 M triangles (395 MB of records: larger than the 256 MiB Infinity Cache), 3840x2160, 1 primary
       ray per pixel -- the HBM regime; `--bounces 2 --metallic 1 --roughness 0.3` is its incoherent variant
 One "step" = one frame.  `value` = primary rays (width x height x spp) per second of wall clock over K steps, scene and
-frame buffers resident in HBM, timed between two barrier + synchronise pairs, max over ranks.  The untimed warm-up is at
+frame buffers resident in HBM, timed between two barrier + synchronise pairs, max over ranks; the timed region is exactly K
+steps, run once, and `ms_per_step` is its time divided by K.  The untimed warm-up is at
 least W steps and, for the 1-spp stream, at least 320 frames (a frame is 0.13 ms; the GPU's clock needs tens of
 milliseconds of load to settle): the line reports the requested and the executed warm-up.
 
@@ -32,6 +33,12 @@ torch.distributed carries only the control plane (barriers, the max over ranks, 
 torch.distributed.run, before this process touches a GPU) and relays their one line.
 
 stdout carries exactly one line, the result; everything else (library banners included) goes to stderr.
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step -- the last frame, RGB -- as
+DIR/frame.npy (float32, height x width x 3, values 0..255).  The scenes and the camera path are seeded, so the same arguments
+render the same frames on every run and two builds can be compared output for output.  An output above 64 MB (4K and 8K
+frames) is stored as a fixed, seeded sample of its elements: DIR/frame_sample.npy with their flat indices in
+DIR/frame_sample_index.npy (float64).
 """
 import argparse
 import ctypes as C
@@ -42,6 +49,7 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -133,7 +141,7 @@ class PhaseWatchdog:
                 os._exit(3)
 
 
-REPEATS_SHORT = 9                # a timed region of ONE launch is measured this many times, back to back; the line reports the median
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this many bytes of .npy data in all
 
 
 class NodeBarrier:
@@ -200,6 +208,24 @@ class NodeBarrier:
         self.slots = None
 
 
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32.  One that does not fit the budget left (DUMP_LIMIT_BYTES in all) is
+    stored as a fixed, seeded sample of its elements, d/<name>_sample.npy, with their flat indices in d/<name>_sample_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes <= left:
+            np.save(os.path.join(d, name + ".npy"), a)
+            left -= a.nbytes
+            continue
+        n = min(a.size, left // (4 + 8))                          # (a float32 value and its float64 index per element)
+        idx = np.unique(np.random.default_rng(20251015).integers(0, a.size, n))
+        np.save(os.path.join(d, name + "_sample.npy"), a.ravel()[idx])
+        np.save(os.path.join(d, name + "_sample_index.npy"), idx.astype(np.float64))
+        left -= idx.size * (4 + 8)
+
+
 def aggregate_repeats(dts, steps):
     """dts = wall-clock seconds of each repeat of the K-step timed region (max over ranks already taken per repeat).
     -> dict(dt = the region's time the line is priced with (the median), fields = what the line says about it)."""
@@ -254,9 +280,27 @@ def algorithmic_bytes(st):
     return 24 * st["aabb"] + 8 * interior + 8 * leaf + 52 * st["tris"] + 24 * st["inside"] + 3 * st["rays"]
 
 
-def scene_path(workload):
+def scene_cache(names):
+    """The directory the workload's OBJ files are read from: the tree's .scene_cache when it holds them all or can be written, else a
+    per-user directory under the system's temporary directory (a tree built by one user and benchmarked by another).  The files
+    are generated from fixed seeds: every directory holds the same bytes."""
     d = os.path.join(ROOT, ".scene_cache")
+    if all(os.path.exists(os.path.join(d, n)) for n in names):
+        return d
+    try:
+        os.makedirs(d, exist_ok=True)
+        if os.access(d, os.W_OK):
+            return d
+    except OSError:
+        pass
+    d = os.path.join(tempfile.gettempdir(), "rt-scene-cache-%d" % os.getuid())
     os.makedirs(d, exist_ok=True)
+    return d
+
+
+def scene_path(workload):
+    names = {"c4": ["atrium.obj"], "c6": ["atrium_c6.obj"], "demo": ["demo_area.obj", "demo_board.obj", "demo_board_baked.obj"]}
+    d = scene_cache(names.get(workload, ["blob70k.obj"]))
     if workload == "c4":
         p = os.path.join(d, "atrium.obj")
         if not os.path.exists(p):
@@ -492,6 +536,8 @@ def main():
     ap.add_argument("--roughness", type=float, default=-1.0, help="override the workload's Material::roughness")
     ap.add_argument("--frames-per-launch", type=int, default=0, help="stream workloads: 0 = as many as one launch takes (32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed frame to DIR/frame.npy (float32; see the module docstring)")
     ap.add_argument("--no-latency", action="store_true", help="skip the F = 1 / F = 2 latency figures")
     ap.add_argument("--phase-deadline", type=float, default=180.0,
                     help="N > 1: seconds every phase of a rank may take (process group, scene, communicator, first exchange, timed loop x 4, check) "
@@ -575,7 +621,8 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
     phase("scene")
-    rt.build()
+    # the libraries are build()'s: a run loads them, and libs() refuses (or, where it can, rebuilds) one not built from this tree's
+    # sources -- nothing is written when they are current, so the tree may belong to another user
     hlib = rt.libs()[0]
     wl = dict(scenes.WORKLOADS[args.workload])
     if args.metallic >= 0:
@@ -689,6 +736,8 @@ def main():
     if args.predict_scaling is not None:
         if dist_on:
             sys.exit("bench.py --predict-scaling runs on one GPU (no --gpus, no --force-collective)")
+        if args.dump_outputs:
+            sys.exit("bench.py --dump-outputs writes the frames of a timed run: not with --predict-scaling")
         res = predict_scaling(args, locals())
     elif stream_mode:
         res = run_stream(args, locals())
@@ -843,12 +892,10 @@ def run_stream(args, env):
     sync()
     if pipe is not None:
         # per unit: wait for buffer / render / exchange / un-stripe (events created here, only recorded inside the timed region)
-        pipe.stage_timing(True, expect_groups=len(units) * (REPEATS_SHORT if len(groups) == 1 else 1))
+        pipe.stage_timing(True, expect_groups=len(units))
     g["phase"]("timed loop", 4.0)
-    # The timed region = the K steps between two barrier + synchronise pairs.  When K fits ONE launch (the driver's
-    # --steps 20) that region is a single 2.7 ms sample: it is then measured REPEATS_SHORT times back to back and the line
-    # reports the median (with min / max / repeats); still a few tens of milliseconds in all.
-    repeats = REPEATS_SHORT if len(groups) == 1 else 1
+    # The timed region = the K steps between two barrier + synchronise pairs, run once: --steps sets how many frames are timed.
+    repeats = 1
     dts, t_issue = [], 0.0
     for rep in range(repeats):
         t0 = time.perf_counter()
@@ -865,6 +912,14 @@ def run_stream(args, env):
         dts = [float(v) for v in tmax.tolist()]
     timing = aggregate_repeats(dts, args.steps)
     dt = timing["dt"]
+    if args.dump_outputs:
+        # the last frame of the last unit, on the rank that assembled it (before the kernel timing below reuses the frame buffers)
+        last = units[-1]
+        f_last, mine = last[0] + last[1] - 1, my_frames(last)
+        if f_last in mine:
+            slot = mine.index(f_last) if (dist_on and rotate) else f_last - (last[0] if dist_on else 0)
+            held = frames_of((repeats * len(units) - 1) & 1)[slot].cpu().numpy()
+            dump_outputs(args.dump_outputs, {"frame": held[:, :W * 3].reshape(H, W, 3)})
     # where a rank's time went, per group of F frames: every rank reports, rank 0 prints all of them
     per_rank = None
     if pipe is not None:
@@ -1325,6 +1380,8 @@ def run_frames(args, env):
 
     last_pose = poses[(args.steps - 1) % len(poses)]
     got = frame.cpu().numpy().reshape(H, W, 3) if rank == 0 else None            # the last timed frame (before the probe below reuses the buffer)
+    if got is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frame": got})
 
     # kernel time of this rank's share of one frame (render_ex_kernel launches + resolve passes), hipEvents
     kernel_ms = None

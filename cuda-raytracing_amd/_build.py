@@ -102,10 +102,17 @@ def _host_deps():
     return d
 
 
+def _hip_out_of_date():
+    return _stale(HIP_SO, HIP_DEPS) or (library_mismatch() is not None and not variant_allowed())
+
+
 def build(force=False, verbose=False):
     """Compile whatever is out of date.  Raises CalledProcessError on a compiler error.
     Safe to call from several processes at once (one rank per GPU): an exclusive file lock serialises them
-    and every process after the first finds the libraries fresh."""
+    and every process after the first finds the libraries fresh.  When both libraries are fresh nothing is
+    written, not even the lock: a tree built by one user can be used by another who cannot write to it."""
+    if not force and not _hip_out_of_date() and not _stale(HOST_SO, _host_deps()):
+        return HIP_SO, HOST_SO
     import fcntl
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -116,7 +123,7 @@ def build(force=False, verbose=False):
 
 
 def _build_locked(force, verbose):
-    if force or _stale(HIP_SO, HIP_DEPS) or (library_mismatch() is not None and not variant_allowed()):
+    if force or _hip_out_of_date():
         # RT_HIPCC_EXTRA: extra compiler flags for A/B experiments on the kernels (e.g. -DRT_PRED_STACK=1); never set in a normal build.
         # The hash of what is being compiled goes into the binary (rt_build_info): the roofline guard of bench.py and libs()
         # check the library that runs, not the sources next to it.

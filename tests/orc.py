@@ -2,6 +2,7 @@
 reference-probe library (oracle/_ref/libref_probe.so).  TEST INFRASTRUCTURE ONLY: the product
 package never imports this module."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 import numpy as np
@@ -278,3 +279,68 @@ def ref_probe():
         _REF = _Lib(path, "ref_")
         _REF.lib.ref_instance_build.argtypes = [C.c_int, C.c_int, _f, _f, C.c_void_p]
     return _REF
+
+
+# ---- the reference's answers where oracle/_ref cannot be built --------------------------------------------------------------
+REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_digests.npz")
+
+
+def _canon(a):
+    """The bytes two outputs share when they agree as the tests compare them: a float NaN's sign and payload do not count."""
+    if isinstance(a, dict):
+        return b"".join(k.encode() + _canon(a[k]) for k in sorted(a))
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        a = np.where(np.isnan(a), np.float32(np.nan), a).astype(a.dtype)
+    return str(a.shape).encode() + a.dtype.str.encode() + a.tobytes()
+
+
+def agree(a, b):
+    """Bit for bit, NaNs as NaNs (any sign or payload); dicts key by key."""
+    if isinstance(a, dict):
+        return sorted(a) == sorted(b) and all(agree(a[k], b[k]) for k in a)
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype.kind != "f":
+        return bool(np.array_equal(a, b))
+    w = a.view(np.uint32 if a.itemsize == 4 else np.uint64)
+    return bool(np.all((w == b.view(w.dtype)) | (np.isnan(a) & np.isnan(b))))
+
+
+class RefAnswers:
+    """A test's comparisons with the reference's own code.  Where oracle/_ref was built every call runs against the probe; in
+    every case the outputs of one iteration of the test's loop are folded into a 64-bit digest and held against the digest of
+    the reference's outputs recorded for the same iteration (tests/golden/ref_digests.npz, written by
+    tests/golden/make_ref_digests.py where the probe exists).  So a checkout without the reference still holds the oracle to
+    the reference's answers on the same inputs, one iteration at a time."""
+
+    def __init__(self, key):
+        self.key, self.live, self.done = key, ref_probe(), []
+        self.record = os.environ.get("RT_RECORD_REF_DIGESTS")
+        self.want = None if self.record else np.load(REF_DIGESTS)[key]
+        self.h = hashlib.blake2b(digest_size=8)
+
+    def same(self, what, mine, call):
+        """mine = this side's output; call(probe) -> the reference's output of the same call."""
+        if self.live is not None:
+            theirs = call(self.live)
+            assert agree(mine, theirs), (self.key, what)
+        elif self.record:
+            raise RuntimeError("recording the reference's answers needs oracle/_ref (make -C oracle where the reference is mounted)")
+        self.h.update(_canon(theirs if self.live is not None else mine))
+
+    def end_iteration(self, what=""):
+        d = np.frombuffer(self.h.digest(), np.uint64)[0]
+        self.h = hashlib.blake2b(digest_size=8)
+        i = len(self.done)
+        self.done.append(d)
+        if self.want is not None:
+            assert i < len(self.want) and d == self.want[i], \
+                "%s, iteration %d %s: outputs differ from the reference's recorded ones (build oracle/_ref for the call that differs)" % (self.key, i, what)
+
+    def finish(self):
+        if self.record:
+            np.save(os.path.join(self.record, self.key + ".npy"), np.array(self.done, np.uint64))
+        else:
+            assert len(self.done) == len(self.want), (self.key, len(self.done), len(self.want))

@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -36,8 +38,8 @@ def test_single_gpu_run_fails_loudly_without_gpu():
 
 
 def test_timed_region_aggregation():
-    """The one driver-timed number: a K-step region that fits one launch is measured nine times and the line is priced with
-    the median (bench.aggregate_repeats); a longer run stays one measurement."""
+    """bench.aggregate_repeats: the median of the repeats of a timed region, with min / max beside it; one measurement (what
+    bench.py takes: the timed region is exactly --steps steps, run once) is priced as it is."""
     sys.path.insert(0, ROOT)
     import bench
     a = bench.aggregate_repeats([0.0030, 0.0027, 0.0100, 0.0026, 0.0028, 0.0027, 0.0029, 0.0027, 0.0031], 20)
@@ -48,7 +50,76 @@ def test_timed_region_aggregation():
     assert b["dt"] == 0.5 and b["fields"] == {"repeats": 1}
     c = bench.aggregate_repeats([0.004, 0.002], 10)                     # (an even count: mean of the middle two)
     assert abs(c["dt"] - 0.003) < 1e-12
-    assert bench.REPEATS_SHORT == 9
+    assert not hasattr(bench, "REPEATS_SHORT")                          # no hidden repeats: --steps K times K steps
+
+
+def test_dump_outputs_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays as DIR/<name>.npy; an array beyond the 64 MB budget becomes a fixed, seeded sample of its
+    elements with their flat indices, the same on every call."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    img = np.arange(6 * 5 * 3, dtype=np.uint8).reshape(6, 5, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"frame": img})
+    got = np.load(str(tmp_path / "a" / "frame.npy"))
+    assert got.dtype == np.float32 and got.shape == img.shape and np.array_equal(got, img)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1200)                # room for 100 (value, index) pairs
+    big = np.random.default_rng(3).integers(0, 256, (40, 30, 3)).astype(np.uint8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"frame": big})
+    assert not (tmp_path / "b" / "frame.npy").exists()
+    v, i = np.load(str(tmp_path / "b" / "frame_sample.npy")), np.load(str(tmp_path / "b" / "frame_sample_index.npy"))
+    assert v.dtype == np.float32 and i.dtype == np.float64 and 0 < v.size <= 100 and v.size == i.size
+    assert v.nbytes + i.nbytes <= 1200
+    assert np.array_equal(v, big.ravel()[i.astype(np.int64)])
+    assert np.array_equal(i, np.load(str(tmp_path / "c" / "frame_sample_index.npy")))
+
+
+
+def test_scene_cache_outside_a_tree_that_cannot_be_written(tmp_path, monkeypatch):
+    """bench.scene_cache: the tree's .scene_cache when it holds the workload's files or can be written, else a per-user directory
+    under the temporary directory -- a benchmark run needs no write access to a tree another user built."""
+    sys.path.insert(0, ROOT)
+    import bench
+    tree, tmp = tmp_path / "tree", tmp_path / "tmp"
+    (tree / ".scene_cache").mkdir(parents=True)
+    tmp.mkdir()
+    monkeypatch.setattr(bench, "ROOT", str(tree))
+    monkeypatch.setattr(bench.tempfile, "tempdir", str(tmp))
+    assert bench.scene_cache(["blob70k.obj"]) == str(tree / ".scene_cache")          # writable
+    real_access = os.access
+    monkeypatch.setattr(bench.os, "access", lambda p, m: False if str(p).startswith(str(tree)) else real_access(p, m))
+    d = bench.scene_cache(["blob70k.obj"])
+    assert d == str(tmp / ("rt-scene-cache-%d" % os.getuid())) and os.path.isdir(d)
+    (tree / ".scene_cache" / "blob70k.obj").write_text("v 0 0 0\n")
+    assert bench.scene_cache(["blob70k.obj"]) == str(tree / ".scene_cache")          # already there: read in place
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["c2", "c3"])
+def test_bench_steps_and_dump_outputs(tmp_path, workload):
+    """--steps K times K steps (ms_per_step = the timed region / K) and --dump-outputs writes the last timed frame, the same
+    frame on a second run with the same arguments."""
+    import json
+    import numpy as np
+    small = ["--width", "320", "--height", "180"] + (["--spp", "4", "--bounces", "2"] if workload == "c3" else [])
+    outs = []
+    for k, steps in enumerate((5, 7)):
+        d = tmp_path / str(k)
+        r = _run("--workload", workload, "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--dump-outputs", str(d), *small)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        assert abs(line["value"] - 320 * 180 * (4 if workload == "c3" else 1) / (line["ms_per_step"] * 1e3)) <= 0.02 * line["value"]
+        assert "repeats" not in line or line["repeats"] == 1
+        img = np.load(str(d / "frame.npy"))
+        assert img.dtype == np.float32 and img.shape == (180, 320, 3) and img.max() > 0
+        outs.append(img)
+    if workload == "c3":                                                 # (one frame per step over an 8-pose path: steps 5 and 7 differ)
+        assert not np.array_equal(outs[0], outs[1])
+    r = _run("--workload", workload, "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--dump-outputs", str(tmp_path / "again"), *small)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert np.array_equal(np.load(str(tmp_path / "again" / "frame.npy")), outs[0])
 
 
 def test_multi_rank_report_fields():

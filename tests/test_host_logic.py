@@ -247,7 +247,7 @@ def test_host_math_on_special_values_vs_oracle(rt, oracle):
         fn(*[np.ascontiguousarray(a, np.float32).ctypes.data_as(f) for a in ins], out.ctypes.data_as(f))
         return out
     import orc as orc_mod
-    ref = orc_mod.ref_probe()
+    ref = orc_mod.RefAnswers("host_math_vs_reference_instance_build")
     rng = np.random.default_rng(777)
     with np.errstate(all="ignore"):
         for it in range(4000):
@@ -261,12 +261,17 @@ def test_host_math_on_special_values_vs_oracle(rt, oracle):
             assert _same_or_both_nan(call(s.rth_invert_intrinsic, 9, m9), oracle.invert_intrinsic(m9)), ("invert_intrinsic", m9)
             x = float(op._draw(rng, 1, ps)[0])
             assert _same_or_both_nan(s.rth_q_rsqrt(x), oracle.q_rsqrt(x)), ("q_rsqrt", x)
-            # MeshInstance::build_inv (MeshInstance.hpp): against the reference's own constructor where oracle/_ref was built
-            if ref is not None:
-                sc = op._draw(rng, 3, ps, 1.0)
+            # MeshInstance::build_inv (MeshInstance.hpp): against the reference's own constructor (live where oracle/_ref was built,
+            # else its recorded answers: orc.RefAnswers)
+            sc = op._draw(rng, 3, ps, 1.0)
+
+            def theirs(r):
                 buf = np.zeros(26, np.float32)
-                ref.lib.ref_instance_build(0, 0, np.ascontiguousarray(p, np.float32).ctypes.data_as(f), sc.ctypes.data_as(f), buf.ctypes.data)
-                assert _same_or_both_nan(call(s.rth_instance_build, 24, p, sc), buf[2:]), ("instance_build", p, sc)
+                r.lib.ref_instance_build(0, 0, np.ascontiguousarray(p, np.float32).ctypes.data_as(f), sc.ctypes.data_as(f), buf.ctypes.data)
+                return buf[2:]
+            ref.same(("instance_build", p, sc), call(s.rth_instance_build, 24, p, sc), theirs)
+            ref.end_iteration()
+    ref.finish()
 
 
 def test_obj_loader_error_behaviour(rt, tmp_path):
@@ -804,3 +809,21 @@ def test_damaged_obj_files_never_crash_and_parse_the_same_on_any_thread_count(rt
             assert a == b, (k, lenient)
             parsed += not isinstance(a, str)
     assert 20 < parsed < 2 * len(files)
+
+
+def test_build_of_a_current_tree_writes_nothing(rt, monkeypatch):
+    """build() on libraries that are current opens no file for writing (not even its lock) and runs no compiler: a tree built
+    by one user can be loaded by another who cannot write to it."""
+    from importlib import import_module
+    b = import_module("cuda-raytracing_amd._build")
+    real_open = open
+
+    def no_writes(path, mode="r", *a, **k):
+        assert not any(c in mode for c in "wax+"), ("build() opened %s for writing" % path)
+        return real_open(path, mode, *a, **k)
+
+    def no_compiler(*a, **k):
+        raise AssertionError("build() ran %s" % (a[0] if a else k))
+    monkeypatch.setattr(b, "open", no_writes, raising=False)
+    monkeypatch.setattr(b.subprocess, "run", no_compiler)
+    assert b.build() == (b.HIP_SO, b.HOST_SO)

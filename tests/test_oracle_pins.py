@@ -2,7 +2,8 @@
   * golden vectors generated from the REFERENCE's own headers (tests/golden/make_golden.py, via
     oracle/_ref/libref_probe.so) -- L0 math, AABB slab, triangle tests, BVH topology, OBJ loading;
   * the known-answer values and full-frame hashes SURVEY.md recorded from the reference's render();
-  * when oracle/_ref is present (build container), the reference code itself on fresh random inputs."""
+  * the reference code itself on seeded random inputs: live where oracle/_ref is present (build container), elsewhere through
+    the digests of its answers recorded for the same inputs (orc.RefAnswers, tests/golden/ref_digests.npz)."""
 import hashlib
 import json
 import os
@@ -241,39 +242,47 @@ def test_blob70k_bvh_stats(orc, oracle, blob70k, pins):
     assert (st["nodes"], st["leaves"], st["max_tris"], st["max_depth"]) == (p["nodes"], p["leaves"], p["max_tris_per_leaf"], p["print_stats_max_depth"])
 
 
-# ---- live comparison with the reference's own code (only where oracle/_ref was built) -----------------
+# ---- the reference's own code: live where oracle/_ref was built, else its recorded answers (orc.RefAnswers) -----------------
+# (orc.agree is the comparison: bit for bit, NaN against NaN whatever its sign or payload -- these inputs make no NaN but the rule is
+# the one of the special-value tests below)
 
 def test_oracle_vs_reference_live(orc, oracle):
-    r = orc.ref_probe()
-    if r is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+    ref = orc.RefAnswers("oracle_vs_reference_live")
     rng = np.random.default_rng(99)
-    for _ in range(300):
+    for it in range(300):
         p = np.concatenate([rng.uniform(-5, 5, 3), rng.uniform(-3.2, 3.2, 3)]).astype(np.float32)
         v = rng.normal(0, 2, 3).astype(np.float32)
-        assert same(oracle.invert_lre(p), r.invert_lre(p))
-        assert same(oracle.apply_lre(p, v), r.apply_lre(p, v))
-        assert same(oracle.normalize(v), r.normalize(v))
+        ref.same("invert_lre", oracle.invert_lre(p), lambda r: r.invert_lre(p))
+        ref.same("apply_lre", oracle.apply_lre(p, v), lambda r: r.apply_lre(p, v))
+        ref.same("normalize", oracle.normalize(v), lambda r: r.normalize(v))
         bmin = rng.uniform(-2, 1, 3).astype(np.float32)
         bmax = (bmin + rng.uniform(0, 2, 3)).astype(np.float32)
         o3, d3 = rng.uniform(-4, 4, 3).astype(np.float32), rng.normal(0, 1, 3).astype(np.float32)
-        assert same(oracle.aabb(bmin, bmax, o3, d3), r.aabb(bmin, bmax, o3, d3))
+        ref.same("aabb", oracle.aabb(bmin, bmax, o3, d3), lambda r: r.aabb(bmin, bmax, o3, d3))
         t = oracle.tri_from_vertices(rng.uniform(-1, 1, 9).astype(np.float32))
-        assert same(t[:12], r.tri_from_vertices(t[:9])[:12])
-        assert same(oracle.tri_test(t, o3, d3), r.tri_test(t, o3, d3))
+        ref.same("tri_from_vertices", t[:12], lambda r: r.tri_from_vertices(t[:9])[:12])
+        ref.same("tri_test", oracle.tri_test(t, o3, d3), lambda r: r.tri_test(t, o3, d3))
         m9 = rng.normal(0, 2, 9).astype(np.float32)
-        assert same(oracle.apply_matrix33(m9, v), r.apply_matrix33(m9, v))
-        assert same(oracle.ray_ctor(o3, d3), r.ray_ctor(o3, d3))
+        ref.same("apply_matrix33", oracle.apply_matrix33(m9, v), lambda r: r.apply_matrix33(m9, v))
+        ref.same("ray_ctor", oracle.ray_ctor(o3, d3), lambda r: r.ray_ctor(o3, d3))
+        ref.end_iteration()
+    ref.finish()
 
 
 def test_oracle_bvh_vs_reference_live(orc, oracle):
-    r = orc.ref_probe()
-    if r is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
     import scene_defs as sd
+    ref = orc.RefAnswers("oracle_bvh_vs_reference_live")
     for seed, n in [(1, 1), (2, 2), (3, 17), (4, 900)]:
         tris = sd.random_triangles(n, seed=seed)
-        _mesh_equal(oracle.mesh_dump(oracle.mesh_from_triangles(tris)), r.mesh_dump(r.mesh_from_triangles(tris)))
+        mine = oracle.mesh_dump(oracle.mesh_from_triangles(tris))
+
+        def theirs(r):
+            e = r.mesh_dump(r.mesh_from_triangles(tris))
+            _mesh_equal(mine, e)
+            return e
+        ref.same("mesh", mine, theirs)
+        ref.end_iteration("(seed %d)" % seed)
+    ref.finish()
 
 
 # ---- the same live comparison where the arithmetic is least comfortable (round 6, third session) ---------------------------
@@ -305,9 +314,7 @@ def test_oracle_vs_reference_live_on_special_values(orc, oracle):
     inputs drawn from zeros of both signs, denormals, FLT_MIN / FLT_MAX, infinities, NaN, 1e-20 / 1e18 / 1e30 mixed with ordinary
     values: flat and inverted boxes, origins on box faces, rays parallel to axes, zero-area triangles, rays aimed at a triangle from
     on or near its plane."""
-    r = orc.ref_probe()
-    if r is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+    ref = orc.RefAnswers("oracle_vs_reference_live_on_special_values")
     rng = np.random.default_rng(4321)
     F = np.float32
     with np.errstate(all="ignore"):
@@ -323,46 +330,53 @@ def test_oracle_vs_reference_live_on_special_values(orc, oracle):
                 o3[int(rng.integers(3))] = bmin[int(rng.integers(3))]
             if rng.random() < 0.3:
                 d3[int(rng.integers(3))] = F(0.0) if rng.random() < 0.5 else F(-0.0)
-            assert same_or_both_nan(oracle.aabb(bmin, bmax, o3, d3), r.aabb(bmin, bmax, o3, d3)), ("aabb", bmin, bmax, o3, d3)
+            ref.same(("aabb", bmin, bmax, o3, d3), oracle.aabb(bmin, bmax, o3, d3), lambda r: r.aabb(bmin, bmax, o3, d3))
             v9 = _draw(rng, 9, ps, 1.0)
             if rng.random() < 0.3:
                 v9[3:6] = v9[0:3]
             if rng.random() < 0.2:
                 v9[6:9] = v9[0:3] + F(2) * (v9[3:6] - v9[0:3])
             t = oracle.tri_from_vertices(v9)
-            assert same_or_both_nan(t[:12], r.tri_from_vertices(v9)[:12]), ("tri_from_vertices", v9)
-            assert same_or_both_nan(oracle.tri_test(t, o3, d3), r.tri_test(t, o3, d3)), ("tri_test", t, o3, d3)
+            ref.same(("tri_from_vertices", v9), t[:12], lambda r: r.tri_from_vertices(v9)[:12])
+            ref.same(("tri_test", t, o3, d3), oracle.tri_test(t, o3, d3), lambda r: r.tri_test(t, o3, d3))
             w = rng.dirichlet((1, 1, 1)).astype(np.float32)
             o4 = _draw(rng, 3, ps * 0.3)
             d4 = ((w[0] * t[0:3] + w[1] * t[3:6] + w[2] * t[6:9]).astype(np.float32) - o4).astype(np.float32)
-            assert same_or_both_nan(oracle.tri_test(t, o4, d4), r.tri_test(t, o4, d4)), ("tri_test, aimed", t, o4, d4)
-            assert same_or_both_nan(oracle.tri_center(t), r.tri_center(t))
+            ref.same(("tri_test, aimed", t, o4, d4), oracle.tri_test(t, o4, d4), lambda r: r.tri_test(t, o4, d4))
+            ref.same(("tri_center", t), oracle.tri_center(t), lambda r: r.tri_center(t))
             v = _draw(rng, 3, ps)
             p = np.concatenate([_draw(rng, 3, ps), _draw(rng, 3, ps, 3.0)])
             e, q, m9 = _draw(rng, 3, ps, 3.0), _draw(rng, 4, ps, 1.0), _draw(rng, 9, ps)
             for name, args in (("normalize", (v,)), ("invert_lre", (p,)), ("apply_lre", (p, v)), ("euler2quat", (e,)), ("apply_quat", (q, v)),
                                ("apply_euler", (e, v)), ("apply_matrix33", (m9, v)), ("invert_intrinsic", (m9,)), ("ray_ctor", (o3, d3)), ("lre2homo", (p,))):
-                assert same_or_both_nan(getattr(oracle, name)(*args), getattr(r, name)(*args)), (name, args)
-            assert same_or_both_nan(oracle.magnitude(v), r.magnitude(v)), ("magnitude", v)
+                ref.same((name, args), getattr(oracle, name)(*args), lambda r: getattr(r, name)(*args))
+            ref.same(("magnitude", v), oracle.magnitude(v), lambda r: r.magnitude(v))
             x = float(_draw(rng, 1, ps)[0])
-            assert same_or_both_nan(oracle.q_rsqrt(x), r.q_rsqrt(x)), ("q_rsqrt", x)
+            ref.same(("q_rsqrt", x), oracle.q_rsqrt(x), lambda r: r.q_rsqrt(x))
+            ref.end_iteration()
+    ref.finish()
 
 
 def test_oracle_bvh_vs_reference_live_on_awkward_meshes(orc, oracle):
     """BVHTree::fill (BVHTree.hpp:203-292), restatement against the reference's own builder, on the mesh kinds of the adversarial GPU
     fuzz (tests/test_gpu_parity.py _adversarial_mesh): lattice vertices (flat boxes, coincident centroids), zero-area triangles, piles
     of coincident triangles (unsplittable leaves above 30), coordinates at 1e6..1e18 and 1e-6..1e-20, slivers, non-finite vertices."""
-    r = orc.ref_probe()
-    if r is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+    ref = orc.RefAnswers("oracle_bvh_vs_reference_live_on_awkward_meshes")
     import collections
     import test_gpu_parity as gp
     seen = collections.Counter()
     for seed in range(600):
         kind, tris = gp._adversarial_mesh(oracle, np.random.default_rng(52000 + seed))
-        d, e = oracle.mesh_dump(oracle.mesh_from_triangles(tris)), r.mesh_dump(r.mesh_from_triangles(tris))
-        assert same_or_both_nan(d["boxes"], e["boxes"]) and same_or_both_nan(d["tris"], e["tris"]), (seed, kind)
-        for k in ("child", "leaf_count", "leaf_idx"):
-            assert np.array_equal(d[k], e[k]), (seed, kind, k)
+        d = oracle.mesh_dump(oracle.mesh_from_triangles(tris))
+
+        def theirs(r):
+            e = r.mesh_dump(r.mesh_from_triangles(tris))
+            assert same_or_both_nan(d["boxes"], e["boxes"]) and same_or_both_nan(d["tris"], e["tris"]), (seed, kind)
+            for k in ("child", "leaf_count", "leaf_idx"):
+                assert np.array_equal(d[k], e[k]), (seed, kind, k)
+            return e
+        ref.same((seed, kind), d, theirs)
+        ref.end_iteration("(seed %d, %s)" % (seed, kind))
         seen[kind] += 1
+    ref.finish()
     assert len(seen) == 8 and min(seen.values()) >= 30, seen

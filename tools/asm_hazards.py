@@ -12,7 +12,7 @@ Rules (wait states = instructions issued in between, an `s_nop N` counting N + 1
      non-transcendental VALU instruction reads it
 The scan is linear in program order (labels do not reset it: a fall-through path is a path).
    python tools/asm_hazards.py [file.s]          (without a file: compiles rt_kernels.hip for gfx950 first)"""
-import os, re, subprocess, sys
+import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRANS = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_exp_", "v_log_", "v_sin_", "v_cos_")
 
@@ -20,11 +20,12 @@ TRANS = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_exp_", "v_log_", "v_sin_", "v_cos_")
 def device_asm(path=None):
     if path:
         return open(path).read()
-    out = "/tmp/rt_kernels_hazards.s"
     src = os.path.join(ROOT, "cuda-raytracing_amd", "csrc", "rt_kernels.hip")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-                    "--cuda-device-only", "-S", "-o", out, src], check=True, stderr=subprocess.DEVNULL)
-    return open(out).read()
+    with tempfile.TemporaryDirectory() as d:                # a private directory: another user's or run's file cannot be in the way
+        out = os.path.join(d, "rt_kernels_hazards.s")
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
+                        "--cuda-device-only", "-S", "-o", out, src], check=True, stderr=subprocess.DEVNULL)
+        return open(out).read()
 
 
 def regs(tok):
