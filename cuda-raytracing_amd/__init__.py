@@ -53,6 +53,10 @@ class RtInstanceDesc(C.Structure):
                 ("rotation", C.c_float * 3), ("inv_rotation", C.c_float * 3), ("scale", C.c_float * 3), ("inv_scale", C.c_float * 3)]
 
 
+class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers, any may be NULL)
+    _fields_ = [(n, _vp) for n in ("t", "instance", "triangle", "location", "normal", "uv", "pops")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -66,7 +70,7 @@ RT_HIP_SYMBOLS = [
     "rt_render_debug", "rt_render_ids", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
-    "rt_timer_elapsed_ms", "rt_timer_destroy"]
+    "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -192,6 +196,11 @@ def _declare(h, s):
     h.rt_render_tiled.argtypes = [_vp, _vp, C.POINTER(RtCameraParams), _vp, _vp, C.c_size_t, C.c_int32, C.c_int32, _vp, C.c_int]
     h.rt_render_tiled_all.argtypes = [C.POINTER(_vp), C.POINTER(_vp), C.c_int32, C.POINTER(RtCameraParams), _vp, _vp, C.c_size_t,
                                       C.c_int32, C.c_int32, C.POINTER(_vp), C.c_int]
+    h.rt_trace_workspace_bytes.restype = C.c_size_t
+    h.rt_trace_workspace_bytes.argtypes = [C.c_int32]
+    h.rt_trace_rays.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtRayHits), _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_occluded.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
     h.rt_timer_start.argtypes = [_vp, _vp]
     h.rt_timer_stop.argtypes = [_vp, _vp]
@@ -469,6 +478,28 @@ class Scene:
         d["asm_loop_frac"] = round(d["asm"] / casts, 5) if casts else None
         return d
 
+    RAY_OUTPUTS = ("t", "instance", "triangle", "location", "normal", "uv", "pops")     # the fields of RtRayHits
+
+    def trace_rays(self, origins, directions, outputs=("t", "instance", "triangle"), stream=None, binning=None):
+        """The reference's cast_ray (raycast.cu:21-142) on the caller's rays, closest hit, bit for bit (rt_trace_rays): dict of the
+        wanted RAY_OUTPUTS -- t [...] float32 (HitInfo::min, the world DISTANCE to the hit, FLT_MAX on a miss; directions are not
+        normalised), instance / triangle [...] int32 (-1 on a miss), location / normal [..., 3] float32 (raycast.cu:98-102 for the
+        accepted hit, :115-122), uv [..., 2] float32 (TrianglePrimitive::point_inside), pops [...] int32 (node pops, :61).
+        origins, directions: float32 [..., 3], contiguous, same shape.  torch tensors on the scene's (current) device: outputs
+        are torch tensors allocated there and the call is enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t; default
+        torch.cuda.current_stream()) without a synchronise.  numpy arrays: copied to the device and back, the call synchronises.  binning: sort the rays by direction
+        octant on the device first (same results; None = TRACE_BINNING, see DESIGN.md "Ray queries")."""
+        bad = [o for o in outputs if o not in self.RAY_OUTPUTS]
+        if bad or not outputs:
+            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.RAY_OUTPUTS, tuple(outputs)))
+        return _ray_query(self, origins, directions, None, tuple(outputs), stream, binning)
+
+    def occluded(self, origins, directions, tmax=None, stream=None, binning=None):
+        """Occlusion (rt_occluded): cast_ray(ray, lighting_pass = true, light_distance = tmax) with the early return of
+        raycast.cu:129-133 -- uint8 [...], 1 where the cast accepts a hit closer than tmax (None: FLT_MAX for every ray; a
+        float32 array of the rays' leading shape otherwise).  Arguments and paths as in trace_rays."""
+        return _ray_query(self, origins, directions, tmax, ("occluded",), stream, binning)["occluded"]
+
     def info(self):
         b = C.c_size_t(0)
         d = C.c_int32(0)
@@ -504,6 +535,29 @@ class Camera:
         p = RtCameraParams()
         libs()[1].rth_camera_params(self.h, C.addressof(p))
         return p
+
+    def rays(self, as_numpy=False, stream=None):
+        """(origins, directions) float32 [height, width, 3] of every pixel's primary ray, exactly as the render kernels make it
+        (raycast.cu:156-188; rt_camera_rays): torch tensors on the current device, enqueued on `stream` (default the current torch
+        stream) without a synchronise -- or numpy arrays with as_numpy=True."""
+        h = libs()[0]
+        p = self.params()
+        shape = (self.height, self.width, 3)
+        if as_numpy:
+            n = self.width * self.height * 3 * 4
+            bo, bd = DeviceBuffer(nbytes=n), DeviceBuffer(nbytes=n)
+            try:
+                check(h.rt_camera_rays(C.byref(p), bo.ptr, bd.ptr, stream, 1), "rt_camera_rays")
+                return bo.to_host(np.float32).reshape(shape), bd.to_host(np.float32).reshape(shape)
+            finally:
+                bo.free()
+                bd.free()
+        import torch
+        o = torch.empty(shape, dtype=torch.float32, device="cuda")
+        d = torch.empty(shape, dtype=torch.float32, device="cuda")
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(h.rt_camera_rays(C.byref(p), o.data_ptr(), d.data_ptr(), st, 0), "rt_camera_rays")
+        return o, d
 
     def render_scene(self, scene, d_img, pitch, synchronize=False):
         check(libs()[1].rth_camera_render_scene(self.h, scene.h, d_img, pitch, 1 if synchronize else 0), "Camera::render_scene")
@@ -729,6 +783,88 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+# Whether Scene.trace_rays / occluded sort the rays by direction octant before tracing when the caller does not say (binning=None).
+# Off: tools/ray_query_bench.py measured the sort winning 1.4-1.6 x on shuffled and random rays but costing 11-36 % on camera rays in
+# pixel order and 19 % on shadow rays from a frame's hits (DESIGN.md "Ray queries"); callers with incoherent rays pass binning=True.
+TRACE_BINNING = False
+
+
+def _ray_query(scene, origins, directions, tmax, outputs, stream, binning):
+    """Scene.trace_rays / Scene.occluded: every argument is checked before any device call."""
+    torch_in = type(origins).__module__.split(".")[0] == "torch"
+    if torch_in != (type(directions).__module__.split(".")[0] == "torch") or \
+            (tmax is not None and torch_in != (type(tmax).__module__.split(".")[0] == "torch")):
+        raise ValueError("origins, directions (and tmax) must all be torch tensors or all numpy arrays")
+    if not torch_in and not all(isinstance(a, np.ndarray) for a in (origins, directions) + (() if tmax is None else (tmax,))):
+        raise ValueError("rays must be numpy arrays or torch tensors")
+    arrays = (origins, directions) + (() if tmax is None else (tmax,))
+    for name, a in zip(("origins", "directions", "tmax"), arrays):
+        if str(a.dtype) not in ("float32", "torch.float32"):
+            raise ValueError("%s must be float32, got %s" % (name, a.dtype))
+        contiguous = a.is_contiguous() if torch_in else a.flags["C_CONTIGUOUS"]
+        if not contiguous:
+            raise ValueError("%s must be contiguous" % name)
+    if tuple(origins.shape) != tuple(directions.shape) or len(origins.shape) < 1 or origins.shape[-1] != 3:
+        raise ValueError("origins and directions must have the same shape [..., 3], got %s and %s"
+                         % (tuple(origins.shape), tuple(directions.shape)))
+    lead = tuple(origins.shape[:-1])
+    if tmax is not None and tuple(tmax.shape) != lead:
+        raise ValueError("tmax must have the rays' leading shape %s, got %s" % (lead, tuple(tmax.shape)))
+    n = int(np.prod(lead, dtype=np.int64))
+    if n > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 rays per call, got %d" % n)
+    if torch_in:
+        import torch
+        for name, a in zip(("origins", "directions", "tmax"), arrays):
+            if not a.is_cuda:
+                raise ValueError("%s is on %s: torch rays must be on the scene's GPU" % (name, a.device))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        for name, a in zip(("origins", "directions", "tmax"), arrays):
+            if a.device != dev:
+                raise ValueError("%s is on %s, the scene's device is %s" % (name, a.device, dev))
+    if binning is None:
+        binning = TRACE_BINNING
+    h = libs()[0]
+    handle = scene.device_handle
+    ws_bytes = h.rt_trace_workspace_bytes(n) if binning and n > 0 else 0
+    shapes = dict(t=(lead, np.float32), instance=(lead, np.int32), triangle=(lead, np.int32), location=(lead + (3,), np.float32),
+                  normal=(lead + (3,), np.float32), uv=(lead + (2,), np.float32), pops=(lead, np.int32), occluded=(lead, np.uint8))
+    if torch_in:
+        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}
+        out = {k: torch.empty(shapes[k][0], dtype=tdt[shapes[k][1]], device=dev) for k in outputs}
+        ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        if ws is not None:
+            ws.record_stream(ts)                                # (freed here, in use until `ts` has passed the call)
+        st = ts.cuda_stream
+        ptr = {k: v.data_ptr() for k, v in out.items()}
+        args = (origins.data_ptr(), directions.data_ptr(), None if tmax is None else tmax.data_ptr(), ws.data_ptr() if ws is not None else None)
+        sync, keep = 0, []
+    else:
+        keep = [DeviceBuffer(nbytes=max(a.nbytes, 1)) for a in arrays]
+        for b, a in zip(keep, arrays):
+            if a.nbytes:
+                check(h.rt_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes, stream), "rt_memcpy_h2d")
+        bufs = {k: DeviceBuffer(nbytes=max(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize, 1)) for k in outputs}
+        ws = DeviceBuffer(nbytes=ws_bytes) if ws_bytes else None
+        keep += list(bufs.values()) + ([ws] if ws is not None else [])
+        ptr = {k: b.ptr for k, b in bufs.items()}
+        args = (keep[0].ptr, keep[1].ptr, keep[2].ptr if tmax is not None else None, ws.ptr if ws is not None else None)
+        st, sync = stream, 1
+    try:
+        if outputs == ("occluded",):
+            check(h.rt_occluded(handle, args[0], args[1], args[2], n, ptr["occluded"], args[3], ws_bytes, st, sync), "rt_occluded")
+        else:
+            hits = RtRayHits(*[ptr.get(k) for k in Scene.RAY_OUTPUTS])
+            check(h.rt_trace_rays(handle, args[0], args[1], n, C.byref(hits), args[3], ws_bytes, st, sync), "rt_trace_rays")
+        if torch_in:
+            return out
+        return {k: b.to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0]) for k, b in bufs.items()}
+    finally:
+        for b in keep:
+            b.free()
 
 
 def render_debug(scene, camera):

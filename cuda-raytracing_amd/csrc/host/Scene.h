@@ -5,6 +5,8 @@
 // without rebuilding.  The device side is owned by librt_hip.so behind `d_scene` (an RtScene*, see include/rt_hip.h)
 // instead of the reference's three raw device pointers.
 #pragma once
+#include <cstddef>
+#include <cstdint>
 #include <vector>
 
 #include "Material.hpp"
@@ -12,6 +14,7 @@
 #include "MeshPrimitive.h"
 
 struct RtScene;
+struct RtRayHits;
 
 class Scene {
 public:
@@ -43,6 +46,13 @@ public:
     // call has succeeded: on an error (last_error) host and device still describe the old mesh and the old scene still renders.
     // Returns when the new tree is in place.
     void rebuild_mesh(int mesh_index, std::vector<TrianglePrimitive> triangles, void* stream = nullptr);
+    // Ray queries on the device scene: the reference's cast_ray (raycast.cu:21-142) on rays the caller chooses -- rt_trace_rays /
+    // rt_occluded of include/rt_hip.h, where the semantics are.  Rays and outputs are DEVICE arrays; a workspace of
+    // rt_trace_workspace_bytes(n) bytes (optional) sorts the rays by direction octant first.  Returns the status (also in last_error).
+    int trace_rays(const float* d_origins, const float* d_directions, int32_t n, const RtRayHits& out, void* d_workspace = nullptr,
+                   size_t workspace_bytes = 0, void* stream = nullptr, bool synchronize = false);
+    int occluded(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, uint8_t* d_occluded,
+                 void* d_workspace = nullptr, size_t workspace_bytes = 0, void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

@@ -595,6 +595,23 @@ void Scene::refit_mesh(int mesh_index, std::vector<TrianglePrimitive> moved, voi
     if (last_error == RT_OK) last_error = rt_stream_synchronize(stream);   // v and n die with this call
 }
 
+int Scene::trace_rays(const float* d_origins, const float* d_directions, int32_t n, const RtRayHits& out, void* d_workspace,
+                      size_t workspace_bytes, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_trace_rays(d_scene, d_origins, d_directions, n, &out, d_workspace, workspace_bytes, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::occluded(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, uint8_t* d_occluded,
+                    void* d_workspace, size_t workspace_bytes, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_occluded(d_scene, d_origins, d_directions, d_tmax, n, d_occluded, d_workspace, workspace_bytes, stream,
+                                       synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

@@ -375,15 +375,16 @@ __device__ __forceinline__ bool triangle_test(const RenderParams& p, const DevIn
 // COUNT: *iters counts this lane's loop iterations (the cost measure behind the heavy-first dispatch order).
 // POPS (the extension kernel): *pops counts the lane's node pops, the one visit count that kernel reports.
 // OCT >= 0: every lane of the wave is known to hold a ray of sign octant OCT that meets slab_oct's preconditions.
-// ANYHIT (the extension's shadow rays): raycast.cu:129-133 restored -- cast_ray(..., lighting_pass = true, light_distance =
-// FLT_MAX) returns at the first accepted hit whose distance is below light_distance.
+// ANYHIT (the extension's shadow rays, rt_occluded): raycast.cu:129-133 restored -- cast_ray(..., lighting_pass = true, light_distance =
+// tmax) returns at the first accepted hit whose distance is below light_distance (FLT_MAX for shadow rays, per ray for rt_occluded).
 // VIEW (primary rays of render_kernel<.., VIEW>): interior records are read from the frame's view records, `vdelta` bytes behind the
 // record itself, whose box words already are box - r.ro (view_records_kernel: the same subtraction, done once per frame and
 // instance instead of per visit and lane); an iteration in which the whole wave holds the same interior node takes them as
 // scalar operands and skips the leaf half of the loop altogether.
 template <bool DEBUG, bool PROF, bool EX, bool COUNT, class STK, bool POPS, int OCT, bool ANYHIT = false, bool VIEW = false>
 __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInstance& in, int inst_index, const MeshRay& r,
-                                           V3 org, STK& stack, Hit& hit, Counters<DEBUG>& cnt, int* iters, int* pops, uint32_t vdelta = 0)
+                                           V3 org, STK& stack, Hit& hit, Counters<DEBUG>& cnt, int* iters, int* pops, uint32_t vdelta = 0,
+                                           float tmax = FLT_MAX)
 {
     static_assert(!VIEW || (!DEBUG && !PROF && !EX && RT_SENTINEL && RT_LEAF_FLAT), "view records: the timed primary kernels only");
     stack.sp = 0;
@@ -543,7 +544,7 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
             // raycast.cu:129-133: `if (lighting_pass && distance < light_distance) return hit_info;` -- the lane is done with
             // this cast: it takes the sentinel, which ends its loop at the bottom test (and cast_ray_ex skips its other instances)
             if constexpr (ANYHIT) {
-                const bool done = accept & (c.dist < FLT_MAX);
+                const bool done = accept & (c.dist < tmax);
                 if constexpr (kNeedPopValue) cur = done ? kSentinel : cur;
                 else {
                     // (the flag forms of the A/B switches RT_SENTINEL=0 / RT_NEED_POP_VALUE=0: the lane leaves its leaf and finds
@@ -756,11 +757,12 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
 
 // LOC (the bounce kernel's primary ray): the accepted candidate's point on its plane, in mesh space -- the caller turns it into the
 // world-space hit location with the reference's own sequence (raycast.cu:98-104), once, for the hit that was kept
-// ANYHIT (a shadow ray of the extension kernel, raycast.cu:129-133: the cast returns at its first accepted hit): s[66:67] = the lanes
-// that accepted a hit in this triangle step (cleared at the step's start, set in the accepted-candidate block where exec = those
+// ANYHIT (a shadow ray of the extension kernel or a query of rt_occluded, raycast.cu:129-133: the cast returns at its first accepted hit
+// below the lane's light distance %[tmax], a VGPR: FLT_MAX for shadow rays, per ray for rt_occluded): s[66:67] = the lanes
+// that accepted such a hit in this triangle step (cleared at the step's start, set in the accepted-candidate block where exec = those
 // lanes and v21 = the distance); they take the sentinel after the step's own bookkeeping and leave the loop at the latch
 #define RT_ASM_ANYHIT_CLEAR "s_mov_b64 s[66:67], 0\n\t"
-#define RT_ASM_ANYHIT_MARK "v_cmp_lt_f32_e64 s[66:67], v21, %[fmax]\n\t"
+#define RT_ASM_ANYHIT_MARK "v_cmp_lt_f32_e64 s[66:67], v21, %[tmax]\n\t"
 #define RT_ASM_ANYHIT_LEAVE "v_cndmask_b32_e64 %[cur], %[cur], -2, s[66:67]\n\t"
 #define RT_ASM_LOC "v_mov_b32_e32 %[px], v18\n\tv_mov_b32_e32 %[py], v19\n\tv_mov_b32_e32 %[pz], v20\n\t"
 
@@ -1111,13 +1113,12 @@ static_assert(offsetof(DevInstance, q_inv_pose) == 0x20 && offsetof(DevInstance,
 template <int OCT, bool COUNT, int ROW_SHIFT, bool VIEW, bool POPS, bool LOC, bool ORGV = false, bool ANYHIT = false>  // ROW_SHIFT = log2 of the bytes between two entries of a lane's LDS stack column
 __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_index, const MeshRay& r, V3 org, lds_int* column, int lds_depth,
                                                int32_t& cur, int32_t& sp, Hit& hit, int& wave_iters, uint32_t vdelta, int& pops, V3& point,
-                                               V3 back, const DevInstance* general)
+                                               V3 back, const DevInstance* general, float tmax = FLT_MAX)
 {
     // back = DevInstance::inv_pose_xyz (wave-uniform: scalar operands); general = the instance when its mesh -> world transform scales or
     // rotates (the candidate block then reads scale and q_inv_pose through the scalar cache), null when it only translates
     static_assert(!LOC || POPS, "the hit point is kept for the extension kernel, which counts pops");
     static_assert(!(ORGV && VIEW) && !(ANYHIT && (LOC || !POPS || !ORGV)), "secondary rays: no view; a shadow ray keeps no location");
-    const float fmax = FLT_MAX;
     int32_t rem = -1;
 #if RT_ASM_V2
     // the stack pointer as the LDS address of the next free row of the lane's column, and the address of the first row that is not there
@@ -1139,6 +1140,7 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
 #define RT_ASM_OUT_PLAIN
 #define RT_ASM_OUT_POPS , [pops] "+v"(pops)           /* (only the variants that count pops hold a register for them) */
 #define RT_ASM_OUT_LOC , [pops] "+v"(pops), [px] "+v"(point.x), [py] "+v"(point.y), [pz] "+v"(point.z)
+#define RT_ASM_OUT_ANYHIT , [pops] "+v"(pops), [tmax] "+v"(tmax)     /* (only read; in this list it costs the other variants no register) */
 #define RT_ASM_GO(TEXT) RT_ASM_GO2(TEXT, RT_ASM_OUT_PLAIN)
 #define RT_ASM_GO2(TEXT, ...)        /* (... = more output operands, with their leading comma, or nothing) */ \
     asm volatile(TEXT \
@@ -1146,7 +1148,7 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
                    [hu] "+v"(hit.u), [hv] "+v"(hit.v), [iters] "+s"(wave_iters) __VA_ARGS__ \
                  : [rox] "v"(r.ro.x), [roy] "v"(r.ro.y), [roz] "v"(r.ro.z), [rdx] "v"(r.rd.x), [rdy] "v"(r.rd.y), [rdz] "v"(r.rd.z), \
                    [dix] "v"(r.dinv.x), [diy] "v"(r.dinv.y), [diz] "v"(r.dinv.z), RT_ASM_STACK_IN, \
-                   [rec] "s"(p.records), [lc] "s"(p.leaf_count), [orgx] RT_ASM_ORG_C(org.x), [orgy] RT_ASM_ORG_C(org.y), [orgz] RT_ASM_ORG_C(org.z) RT_ASM_XIN, \
+                   [rec] "s"(p.records), [lc] "s"(p.leaf_count), [orgx] RT_ASM_ORG_C(org.x), [orgy] RT_ASM_ORG_C(org.y), [orgz] RT_ASM_ORG_C(org.z), \
                    [inst] "s"(inst_index), [eps] "s"(eps), [vdelta] "s"(vdelta), \
                    [tx] "s"(back.x), [ty] "s"(back.y), [tz] "s"(back.z), [ip] "s"(general) \
                  : "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", \
@@ -1183,22 +1185,18 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
     RT_ASM_CASE(5, RT_ASM_ARGS("v3", "v0", "v1", "v4", "v5", "v2", "v9", "v6", "v7", "v10", "v11", "v8"), RT_ASM_ARGS("s51", "s48", "s49", "s52", "s53", "s50", "s57", "s54", "s55", "s58", "s59", "s56")) \
     RT_ASM_CASE(6, RT_ASM_ARGS("v0", "v3", "v4", "v1", "v5", "v2", "v6", "v9", "v10", "v7", "v11", "v8"), RT_ASM_ARGS("s48", "s51", "s52", "s49", "s53", "s50", "s54", "s57", "s58", "s55", "s59", "s56")) \
     RT_ASM_CASE(7, RT_ASM_ARGS("v3", "v0", "v4", "v1", "v5", "v2", "v9", "v6", "v10", "v7", "v11", "v8"), RT_ASM_ARGS("s51", "s48", "s52", "s49", "s53", "s50", "s57", "s54", "s58", "s55", "s59", "s56"))
-    // (the same eight loops with the ray's world origin in vector registers and FLT_MAX at hand: secondary rays)
+    // (the same eight loops with the ray's world origin in vector registers, and the any-hit form: secondary rays and ray queries)
     if constexpr (ORGV) {
 #define RT_ASM_ORG_C "v"
-#define RT_ASM_XIN , [fmax] "s"(fmax)
-#define RT_ASM_CASE_ANYHIT(VN, SN) else if constexpr (ANYHIT) { RT_ASM_VARIANT(RT_ASM_NOCOUNT, RT_ASM_POPS_INTERIOR, RT_ASM_POPS_LEAF RT_ASM_ANYHIT_CLEAR, RT_ASM_ANYHIT_MARK, RT_ASM_ANYHIT_LEAVE, RT_ASM_OUT_POPS, RT_ASM_ARGS(VN), RT_ASM_ARGS(SN)); }
+#define RT_ASM_CASE_ANYHIT(VN, SN) else if constexpr (ANYHIT) { RT_ASM_VARIANT(RT_ASM_NOCOUNT, RT_ASM_POPS_INTERIOR, RT_ASM_POPS_LEAF RT_ASM_ANYHIT_CLEAR, RT_ASM_ANYHIT_MARK, RT_ASM_ANYHIT_LEAVE, RT_ASM_OUT_ANYHIT, RT_ASM_ARGS(VN), RT_ASM_ARGS(SN)); }
         RT_ASM_ALL_CASES
 #undef RT_ASM_ORG_C
-#undef RT_ASM_XIN
 #undef RT_ASM_CASE_ANYHIT
     } else {
 #define RT_ASM_ORG_C "s"
-#define RT_ASM_XIN
 #define RT_ASM_CASE_ANYHIT(VN, SN)
         RT_ASM_ALL_CASES
 #undef RT_ASM_ORG_C
-#undef RT_ASM_XIN
 #undef RT_ASM_CASE_ANYHIT
     }
 #undef RT_ASM_ALL_CASES
@@ -1212,6 +1210,7 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
 #undef RT_ASM_OUT_PLAIN
 #undef RT_ASM_OUT_POPS
 #undef RT_ASM_OUT_LOC
+#undef RT_ASM_OUT_ANYHIT
 #undef RT_ASM_STACK_OUT
 #undef RT_ASM_STACK_IN
 #if RT_ASM_V2
@@ -1243,7 +1242,7 @@ template <bool DEBUG, bool PROF, bool EX = false, bool COUNT = false, class STK 
           bool VIEW = false, bool UNIFORM_ORG = !EX, bool STATS = false, bool SEC = false>
 __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevInstance& in, int inst_index,
                                                V3 org, V3 dir, STK& stack, Hit& hit, Counters<DEBUG>& cnt, int* iters = nullptr,
-                                               int* pops = nullptr, uint32_t view_off = 0)
+                                               int* pops = nullptr, uint32_t view_off = 0, float tmax = FLT_MAX)
 {
     const MeshRay r = to_mesh_space(in, org, dir);
     const uint32_t vdelta = VIEW ? view_off + (uint32_t)p.view_inst_off[inst_index] : 0u;
@@ -1284,7 +1283,7 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
             const DevInstance* general = (const DevInstance*)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ia >> 32)) << 32) |
                                                               (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ia));
 #define RT_TRACE_ASM(O) trace_loop_asm<O, COUNT, (STK::kStride == 64 ? 8 : 10), VIEW, POPS, EX, SEC, ANYHIT>(p, inst_index, r, org, stack.lds, stack.lds_depth, cur, sp, hit, wave_iters, vdelta, \
-                                                                                              POPS ? *pops : no_pops, point, back, general)
+                                                                                              POPS ? *pops : no_pops, point, back, general, tmax)
             switch (oct) {
             case 0: RT_TRACE_ASM(0); break;
             case 1: RT_TRACE_ASM(1); break;
@@ -1312,7 +1311,7 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
     else {
     // (the C++ loop reads view records for the primary kernels' rays only; an extension ray that does not qualify for the hand-written
     // loop reads the records themselves)
-#define RT_TRACE_LOOP(O) trace_loop<DEBUG, PROF, EX, COUNT, STK, POPS, O, ANYHIT, (VIEW && !EX)>(p, in, inst_index, r, org, stack, hit, cnt, iters, pops, vdelta)
+#define RT_TRACE_LOOP(O) trace_loop<DEBUG, PROF, EX, COUNT, STK, POPS, O, ANYHIT, (VIEW && !EX)>(p, in, inst_index, r, org, stack, hit, cnt, iters, pops, vdelta, tmax)
     if constexpr (STATS) loop_stat(p, STK::kSpill ? RT_LOOP_DEEP : (oct >= 0 ? RT_LOOP_CPP_OCTANT : RT_LOOP_CPP_GENERIC));
     switch (oct) {                                              // (wave-uniform: a scalar branch)
     case 0: RT_TRACE_LOOP(0); break;
@@ -1539,8 +1538,16 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
 // VIEW (the samples-only kernel's primary rays: they share the frame's origin): the cast reads view records, see trace_loop.
 // PRIMARY: the ray starts at the camera in every lane (trace_instance's UNIFORM_ORG).
 // SEC: a secondary ray through the hand-written loop (trace_instance); with OCTANTS and OPTIMISTIC.
+// tmax (ANYHIT): the light distance of raycast.cu:129-133 -- a lane is done at its first accepted hit below it, and the instance loops
+// skip the instances after that hit (FLT_MAX for the extension's shadow rays, per ray for rt_occluded).
+// Whether the cast has returned: a hit was accepted below tmax.  (hit.min starts at FLT_MAX, which is below a tmax of +inf without any
+// hit; for tmax <= FLT_MAX -- the shadow rays' constant among them -- `hit.min < tmax` alone says it.)
+__device__ __forceinline__ bool any_hit_done(const Hit& hit, float tmax)
+{
+    return hit.min < tmax && (tmax <= FLT_MAX || hit.instance >= 0);
+}
 template <bool LOC = true, bool OCTANTS = false, bool ANYHIT = false, class STK = Stack, bool OPTIMISTIC = false, bool VIEW = false, bool PRIMARY = false, bool SEC = false>
-__device__ __forceinline__ Hit cast_ray_ex(const RenderParams& p, V3 org, V3 dir, STK& stack, int& pops)
+__device__ __forceinline__ Hit cast_ray_ex(const RenderParams& p, V3 org, V3 dir, STK& stack, int& pops, float tmax = FLT_MAX)
 {
     static_assert(!VIEW || OPTIMISTIC, "view records are read by the LDS-only loops");
     static_assert(!SEC || (OCTANTS && OPTIMISTIC && !VIEW && !PRIMARY), "SEC");
@@ -1556,11 +1563,11 @@ __device__ __forceinline__ Hit cast_ray_ex(const RenderParams& p, V3 org, V3 dir
         const int pops_before = pops;
         int outgrown = 0;
         for (int i = 0; i < p.num_instances; i++) {
-            if constexpr (ANYHIT) { if (hit.min < FLT_MAX) continue; }
+            if constexpr (ANYHIT) { if (any_hit_done(hit, tmax)) continue; }
             trace_instance<false, false, LOC, false, StackT<STK::kStride, false, true>, true, OCTANTS, ANYHIT, VIEW, PRIMARY, false, SEC>(p, p.instances[i], i, org, dir, fast, hit, none,
-                                                                                                                                        nullptr, &pops, p.view_base);
+                                                                                                                                        nullptr, &pops, p.view_base, tmax);
             // (a shadow ray that found its hit left the loop with entries on its stack: it is done, not outgrown)
-            outgrown |= (ANYHIT && SEC && hit.min < FLT_MAX) ? 0 : fast.sp;
+            outgrown |= (ANYHIT && SEC && any_hit_done(hit, tmax)) ? 0 : fast.sp;
         }
         if (outgrown == 0) return hit;
         pops = pops_before;
@@ -1568,8 +1575,8 @@ __device__ __forceinline__ Hit cast_ray_ex(const RenderParams& p, V3 org, V3 dir
         hit.loc = v3(0.0f, 0.0f, 0.0f);
     }
     for (int i = 0; i < p.num_instances; i++) {
-        if constexpr (ANYHIT) { if (hit.min < FLT_MAX) continue; }
-        trace_instance<false, false, LOC, false, STK, true, OCTANTS, ANYHIT>(p, p.instances[i], i, org, dir, stack, hit, none, nullptr, &pops);
+        if constexpr (ANYHIT) { if (any_hit_done(hit, tmax)) continue; }
+        trace_instance<false, false, LOC, false, STK, true, OCTANTS, ANYHIT>(p, p.instances[i], i, org, dir, stack, hit, none, nullptr, &pops, 0u, tmax);
     }
     return hit;
 }
@@ -2345,6 +2352,170 @@ __global__ __launch_bounds__(256) void view_records_kernel(const RenderParams p,
     ((float4*)view)[(size_t)(job.first[i] + rec) * 4 + quarter] = v;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Ray queries (rt_trace_rays / rt_occluded / rt_camera_rays): the reference's cast_ray (raycast.cu:21-142) on rays the caller
+// chooses.  No new traversal: cast_ray_ex with per-lane origins (SEC: the hand-written loop when a wave's rays share a sign octant in
+// mesh space, the compiler's loop on the general stack otherwise), one wave per workgroup like the primary kernels.  The scene's
+// per-sample extension scratch is not touched: queries on one scene may overlap each other and renders on other streams.
+// ---------------------------------------------------------------------------------------------------------
+struct QueryParams {
+    const float* org;           // [n][3] world origins
+    const float* dir;           // [n][3] world directions (not normalised: cast_ray takes them as they are)
+    const float* tmax;          // rt_occluded: [n] light distances, null = FLT_MAX
+    const int32_t* order;       // octant binning: workgroup slot k traces ray order[k] (null = ray k)
+    int32_t n;
+    float* t;                   // outputs, each optional (null = not wanted), indexed by the ray's ORIGINAL index
+    int32_t *instance, *triangle;
+    float *location, *normal, *uv;
+    int32_t* pops;
+    uint8_t* occluded;
+    int32_t* bins;              // octant binning: [0..7] rays per octant, [8..15] the scatter's cursors
+};
+constexpr int kQueryBlock = 64;
+typedef StackT<kQueryBlock> QueryStack;
+
+// the ray a workgroup slot traces (read again after the cast instead of being kept across it: registers the loop has no room for)
+__device__ __forceinline__ int32_t query_ray(const QueryParams& q, int32_t slot) { return q.order ? q.order[slot] : slot; }
+
+// ANYHIT = rt_occluded: cast_ray_lp(ray, lighting_pass = 1, light_distance = tmax[i]) (raycast.cu:129-133); occluded = the cast accepted a
+// hit below tmax (= its min < tmax, except that a miss is not occluded when tmax is +inf).
+// Otherwise rt_trace_rays: cast_ray(ray) and the fields of its HitInfo.  Rays with non-finite components run like any other ray
+// (no usable octant: the compiler's generic loop); what they return is unspecified, other lanes' results are not affected.
+template <bool ANYHIT>
+__global__ __launch_bounds__(kQueryBlock, 8) void query_kernel(const RenderParams p, const QueryParams q)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth) + 1][kQueryBlock]
+    const int32_t slot0 = (int32_t)blockIdx.x * kQueryBlock;    // (< n <= INT32_MAX: no overflow)
+    if (slot0 + (int32_t)threadIdx.x >= q.n) return;
+    int32_t i = query_ray(q, slot0 + (int32_t)threadIdx.x);
+    const size_t i3 = (size_t)i * 3;
+    const V3 org = v3(q.org[i3], q.org[i3 + 1], q.org[i3 + 2]);
+    const V3 dir = v3(q.dir[i3], q.dir[i3 + 1], q.dir[i3 + 2]);
+    const float tmax = (ANYHIT && q.tmax) ? q.tmax[i] : FLT_MAX;
+    int spill[kMaxStack - kLdsStack];
+    QueryStack stack;
+    // (the thread's index lives on as the address of its LDS stack column only, as in render_ex_kernel)
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    int pops = 0;
+    const Hit hit = cast_ray_ex<!ANYHIT, true, ANYHIT, QueryStack, true, false, false, true>(p, org, dir, stack, pops, tmax);
+    asm volatile("" : "+v"(stack.lds));
+    i = query_ray(q, slot0 + (int32_t)(stack.lds - (lds_int*)lds_stack));
+    if constexpr (ANYHIT) {
+        q.occluded[i] = any_hit_done(hit, q.tmax ? q.tmax[i] : FLT_MAX) ? 1 : 0;
+    } else {
+        const bool got = hit.instance >= 0;
+        if (q.t) q.t[i] = hit.min;
+        if (q.instance) q.instance[i] = hit.instance;
+        if (q.triangle) q.triangle[i] = got ? p.tri_id[hit.slot] : -1;
+        if (q.pops) q.pops[i] = pops;
+        const size_t o3 = (size_t)i * 3;
+        if (q.location) { q.location[o3] = hit.loc.x; q.location[o3 + 1] = hit.loc.y; q.location[o3 + 2] = hit.loc.z; }
+        if (q.normal) {
+            const V3 n = got ? hit_normal(p, hit) : v3(0.0f, 0.0f, 0.0f);
+            q.normal[o3] = n.x; q.normal[o3 + 1] = n.y; q.normal[o3 + 2] = n.z;
+        }
+        if (q.uv) {
+            // TrianglePrimitive::point_inside's interpolated uv, as base_colour derives it (exact-uv meshes: the hit carries it)
+            float2 uv = make_float2(0.0f, 0.0f);
+            if (got) {
+                uv = make_float2(hit.u, hit.v);
+                if (!p.instances[hit.instance].exact_uv) {
+                    const float* t = p.tri_uv + (size_t)hit.slot * 6;
+                    const float w = 1.0f - hit.u - hit.v;
+                    uv.x = (w * t[0] + hit.v * t[2]) + hit.u * t[4];
+                    uv.y = (w * t[1] + hit.v * t[3]) + hit.u * t[5];
+                }
+            }
+            q.uv[(size_t)i * 2] = uv.x; q.uv[(size_t)i * 2 + 1] = uv.y;
+        }
+    }
+}
+
+// Octant binning: a wave of arbitrary rays almost never shares a sign octant, and a wave that does not leaves the hand-written loop.
+// The two passes below sort the ray indices by the sign octant of their WORLD direction (a counting sort of 8 buckets; rays of
+// rotated instances may still differ in mesh space -- those waves fall back per instance, as they would unsorted).  Each workgroup
+// takes a chunk of kBinChunk rays; per wave a ballot per bucket, one atomic per bucket per workgroup.  The order within a bucket
+// depends on which workgroup reserves first -- only the order of the work, never what a ray computes.
+constexpr int kBinBlock = 256, kBinChunk = 4096;
+__device__ __forceinline__ int world_octant(const QueryParams& q, int32_t i)
+{
+    const size_t i3 = (size_t)i * 3;
+    return (int)(__float_as_uint(q.dir[i3]) >> 31) | (int)((__float_as_uint(q.dir[i3 + 1]) >> 31) << 1) |
+           (int)((__float_as_uint(q.dir[i3 + 2]) >> 31) << 2);
+}
+
+// this workgroup's rays per octant -> counts[8] (LDS); lane 0 of each wave adds its wave's popcounts
+__device__ __forceinline__ void bin_chunk_counts(const QueryParams& q, int32_t first, int32_t last, int* counts)
+{
+    if (threadIdx.x < 8) counts[threadIdx.x] = 0;
+    __syncthreads();
+    int mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int32_t k = first + (int32_t)threadIdx.x; k - (int32_t)threadIdx.x < last; k += kBinBlock) {
+        const int oct = k < last ? world_octant(q, k) : -1;
+        for (int b = 0; b < 8; b++) mine[b] += __popcll(__ballot(oct == b));
+    }
+    if ((threadIdx.x & 63) == 0)
+        for (int b = 0; b < 8; b++) if (mine[b]) atomicAdd(&counts[b], mine[b]);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kBinBlock) void bin_count_kernel(const QueryParams q)
+{
+    __shared__ int counts[8];
+    const int32_t first = (int32_t)((int64_t)blockIdx.x * kBinChunk), last = (int32_t)std::min<int64_t>((int64_t)first + kBinChunk, q.n);
+    bin_chunk_counts(q, first, last, counts);
+    if (threadIdx.x < 8 && counts[threadIdx.x]) atomicAdd(&q.bins[threadIdx.x], counts[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(kBinBlock) void bin_scatter_kernel(const QueryParams q, int32_t* order)
+{
+    __shared__ int counts[8], base[8], wave_counts[kBinBlock / 64][8];
+    const int32_t first = (int32_t)((int64_t)blockIdx.x * kBinChunk), last = (int32_t)std::min<int64_t>((int64_t)first + kBinChunk, q.n);
+    bin_chunk_counts(q, first, last, counts);
+    if (threadIdx.x < 8) {
+        int start = 0;                                          // the bucket's first index: the rays of the octants before it
+        for (int b = 0; b < (int)threadIdx.x; b++) start += q.bins[b];
+        base[threadIdx.x] = start + (counts[threadIdx.x] ? atomicAdd(&q.bins[8 + threadIdx.x], counts[threadIdx.x]) : 0);
+    }
+    __syncthreads();
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int32_t k0 = first; k0 < last; k0 += kBinBlock) {
+        const int32_t k = k0 + (int32_t)threadIdx.x;
+        const int oct = k < last ? world_octant(q, k) : -1;
+        int rank = 0;
+        for (int b = 0; b < 8; b++) {
+            const unsigned long long m = __ballot(oct == b);
+            if (lane == 0) wave_counts[wave][b] = __popcll(m);
+            if (oct == b) rank = __popcll(m & below);
+        }
+        __syncthreads();
+        if (oct >= 0) {
+            int at = base[oct] + rank;
+            for (int w = 0; w < wave; w++) at += wave_counts[w][oct];
+            order[at] = k;
+        }
+        __syncthreads();
+        if (threadIdx.x < 8) {
+            int add = 0;
+            for (int w = 0; w < kBinBlock / 64; w++) add += wave_counts[w][threadIdx.x];
+            base[threadIdx.x] += add;
+        }
+        __syncthreads();
+    }
+}
+
+// rt_camera_rays: the primary ray of every pixel, exactly as render_pixel makes it (raycast.cu:156-188), row-major y * width + x
+__global__ __launch_bounds__(256) void camera_rays_kernel(const FrameParams f, int32_t width, size_t npix, float* org, float* dir)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= npix) return;
+    const int x = (int)(k % (size_t)width), y = (int)(k / (size_t)width);
+    const V3 d = camera_direction(f, (float)x, (float)y);
+    org[k * 3] = f.origin[0]; org[k * 3 + 1] = f.origin[1]; org[k * 3 + 2] = f.origin[2];
+    dir[k * 3] = d.x; dir[k * 3 + 1] = d.y; dir[k * 3 + 2] = d.z;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -2401,6 +2572,25 @@ int32_t leaf_ref(int64_t slot, int count) { return kLeafFlag | ((count <= 30 ? c
 
 bool camera_ok(const RtCameraParams* cam) { return cam && cam->width > 0 && cam->height > 0; }
 
+// the camera of one frame (Camera.cu:23-36: the by-value arguments of render<<<>>>)
+void fill_frame(FrameParams& f, const RtCameraParams* cam)
+{
+    memcpy(f.kinv, cam->K_inv, sizeof f.kinv);
+    memcpy(f.D, cam->D, sizeof f.D);
+    f.origin[0] = cam->camera_pose[0]; f.origin[1] = cam->camera_pose[1]; f.origin[2] = cam->camera_pose[2];
+    f.q_cam = euler2quat(v3(cam->inv_camera_pose[3], cam->inv_camera_pose[4], cam->inv_camera_pose[5]));
+}
+
+// the scene's part of the launch parameters
+void fill_scene(RenderParams& p, const RtScene* s)
+{
+    p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
+    p.leaf_count = s->d_leaf_count; p.mesh_flags = s->d_mesh_flags;
+    p.instances = s->d_instances; p.materials = s->d_materials;
+    p.num_instances = (int32_t)s->instances.size();
+    p.stack_depth = s->max_stack;
+}
+
 // count cameras (same width/height) -> the per-frame part of the launch parameters
 int fill_params(RenderParams& p, const RtScene* s, const RtCameraParams* cams, uint8_t* const* d_imgs, int count, size_t pitch)
 {
@@ -2412,18 +2602,11 @@ int fill_params(RenderParams& p, const RtScene* s, const RtCameraParams* cams, u
         const RtCameraParams* cam = &cams[i];
         if (cam->width != p.width || cam->height != p.height || !d_imgs[i]) return RT_E_INVALID;
         FrameParams& f = p.frames[i];
-        memcpy(f.kinv, cam->K_inv, sizeof f.kinv);
-        memcpy(f.D, cam->D, sizeof f.D);
-        f.origin[0] = cam->camera_pose[0]; f.origin[1] = cam->camera_pose[1]; f.origin[2] = cam->camera_pose[2];
-        f.q_cam = euler2quat(v3(cam->inv_camera_pose[3], cam->inv_camera_pose[4], cam->inv_camera_pose[5]));
+        fill_frame(f, cam);
         f.img = d_imgs[i];
         f.rank = 0; f.local_rows = p.height;
     }
-    p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
-    p.leaf_count = s->d_leaf_count; p.mesh_flags = s->d_mesh_flags;
-    p.instances = s->d_instances; p.materials = s->d_materials;
-    p.num_instances = (int32_t)s->instances.size();
-    p.stack_depth = s->max_stack;
+    fill_scene(p, s);
     p.pitch = pitch;
     p.local_rows = p.height; p.stripe_rows = p.height; p.rank = 0; p.num_ranks = 1;
     return RT_OK;
@@ -3781,6 +3964,84 @@ int rt_unstripe(const uint8_t* d_gathered, size_t local_pitch, size_t rank_strid
                 int32_t width, int32_t height, int32_t stripe_rows, int32_t num_ranks, void* stream)
 {
     return rt_unstripe_batch(d_gathered, local_pitch, rank_stride, 0, d_img, pitch, 0, 1, width, height, stripe_rows, num_ranks, stream);
+}
+
+// ---- ray queries ------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t kQueryBinsBytes = 256;                          // the workspace's counters (16 ints), then the permutation
+
+int launch_query(RtScene* s, QueryParams& q, bool anyhit, void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (!s || q.n < 0 || (q.n > 0 && (!q.org || !q.dir))) return RT_E_INVALID;
+    if (d_workspace && workspace_bytes < rt_trace_workspace_bytes(q.n)) return RT_E_INVALID;
+    if (q.n == 0) return RT_OK;                                  // nothing launched
+    const hipStream_t st = (hipStream_t)stream;
+    {
+        RT_SCENE_CALL(s);
+        RenderParams p;
+        memset(&p, 0, sizeof p);
+        fill_scene(p, s);
+        p.num_frames = 1;
+        const unsigned groups = (unsigned)(((int64_t)q.n + kQueryBlock - 1) / kQueryBlock);
+        if (d_workspace) {
+            q.bins = (int32_t*)d_workspace;
+            int32_t* order = (int32_t*)((char*)d_workspace + kQueryBinsBytes);
+            const unsigned chunks = (unsigned)(((int64_t)q.n + kBinChunk - 1) / kBinChunk);
+            RT_HIP(hipMemsetAsync(q.bins, 0, 16 * sizeof(int32_t), st));
+            hipLaunchKernelGGL(bin_count_kernel, dim3(chunks), dim3(kBinBlock), 0, st, q);
+            hipLaunchKernelGGL(bin_scatter_kernel, dim3(chunks), dim3(kBinBlock), 0, st, q, order);
+            q.order = order;
+        }
+        const size_t lds = (size_t)(lds_rows(p.stack_depth) + 1) * kQueryBlock * sizeof(int);     // (+ the optimistic stack's spare row)
+        if (anyhit) hipLaunchKernelGGL(query_kernel<true>, dim3(groups), dim3(kQueryBlock), lds, st, p, q);
+        else hipLaunchKernelGGL(query_kernel<false>, dim3(groups), dim3(kQueryBlock), lds, st, p, q);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+}  // namespace
+
+size_t rt_trace_workspace_bytes(int32_t n)
+{
+    return n < 0 ? 0 : kQueryBinsBytes + (size_t)n * sizeof(int32_t);
+}
+
+int rt_trace_rays(RtScene* s, const float* d_origins, const float* d_directions, int32_t n, const RtRayHits* out,
+                  void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (!out) return RT_E_INVALID;
+    QueryParams q;
+    memset(&q, 0, sizeof q);
+    q.org = d_origins; q.dir = d_directions; q.n = n;
+    q.t = out->t; q.instance = out->instance; q.triangle = out->triangle;
+    q.location = out->location; q.normal = out->normal; q.uv = out->uv; q.pops = out->pops;
+    return launch_query(s, q, false, d_workspace, workspace_bytes, stream, synchronize);
+}
+
+int rt_occluded(RtScene* s, const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, uint8_t* d_occluded,
+                void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (n > 0 && !d_occluded) return RT_E_INVALID;
+    QueryParams q;
+    memset(&q, 0, sizeof q);
+    q.org = d_origins; q.dir = d_directions; q.tmax = d_tmax; q.n = n; q.occluded = d_occluded;
+    return launch_query(s, q, true, d_workspace, workspace_bytes, stream, synchronize);
+}
+
+int rt_camera_rays(const RtCameraParams* cam, float* d_origins, float* d_directions, void* stream, int synchronize)
+{
+    if (!camera_ok(cam) || !d_origins || !d_directions) return RT_E_INVALID;
+    FrameParams f;
+    memset(&f, 0, sizeof f);
+    fill_frame(f, cam);
+    const size_t npix = (size_t)cam->width * (size_t)cam->height;
+    if ((npix + 255) / 256 > (size_t)INT32_MAX) return RT_E_INVALID;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, cam->width, npix,
+                       d_origins, d_directions);
+    RT_HIP(hipGetLastError());
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
 }
 
 int rt_timer_create(RtTimer** t)

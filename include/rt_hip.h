@@ -383,6 +383,41 @@ int rt_render_tiled_all(RtScene *const *scenes, RtComm *const *comms, int32_t nu
                         const RtRenderOptions *opts, uint8_t *d_img, size_t pitch, int32_t stripe_rows, int32_t root,
                         void *const *streams, int synchronize);
 
+/* ---- ray queries (replaces a call of cast_ray, raycast.cu:21-142, on rays the CALLER chooses; DESIGN.md "Ray queries").
+ *      Closest hit = the reference's cast_ray(ray) bit for bit, quirks included: directions are not normalised, `t` is the
+ *      Euclidean world distance from the origin to the accepted hit (HitInfo::min), not a ray parameter; back faces are never
+ *      hit (same_dir < 0, :107-109); there is no t-min; a box is pruned by comparing its MESH-space distance with the world
+ *      min; of equal distances the first visited wins.  Rays are DEVICE arrays [n][3] float; outputs are tight DEVICE arrays
+ *      of n rows, indexed like the rays.  Rays with a non-finite component do not fault and do not change other rays'
+ *      results; their own results are unspecified.  Zero direction components are ordinary input.
+ *      Octant binning: with a workspace of rt_trace_workspace_bytes(n) device bytes the rays are first sorted by the sign
+ *      octant of their direction (a counting sort on the device) and traced in that order -- the results are the same bit for
+ *      bit, only the order of the work changes; NULL traces in input order.  A workspace serves one call at a time.
+ *      Asynchronous on `stream` unless synchronize != 0; nothing is launched when n == 0.  Calls on one scene may overlap each
+ *      other and renders on other streams (no scene scratch is used).  RT_E_INVALID: NULL scene, n < 0, NULL rays (or
+ *      outputs) with n > 0, a non-NULL workspace smaller than rt_trace_workspace_bytes(n). ------------------------------ */
+typedef struct RtRayHits {      /* every pointer optional (NULL = not wanted) */
+    float   *t;                 /* HitInfo::min: world distance origin -> accepted hit; FLT_MAX on a miss               */
+    int32_t *instance;          /* index into the scene's instances, -1 on a miss                                        */
+    int32_t *triangle;          /* index into that mesh's triangles as uploaded (rt_render_ids' numbering), -1 on a miss */
+    float   *location;          /* [n][3] world location of the ACCEPTED hit (raycast.cu:98-102 for it); 0 on a miss     */
+    float   *normal;            /* [n][3] world normal, raycast.cu:115-122; 0 on a miss                                  */
+    float   *uv;                /* [n][2] interpolated texture uv, TrianglePrimitive::point_inside; 0 on a miss          */
+    int32_t *pops;              /* [n] node pops of the cast (raycast.cu:61)                                             */
+} RtRayHits;
+size_t rt_trace_workspace_bytes(int32_t n);
+int rt_trace_rays(RtScene *scene, const float *d_origins, const float *d_directions, int32_t n, const RtRayHits *out,
+                  void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+/* Occlusion: cast_ray(ray, lighting_pass = true, light_distance = tmax[i]) with the early return of raycast.cu:129-133 restored
+ * (the rule of the extension's shadow rays).  d_occluded[i] = 1 exactly when that cast accepts a hit at a distance below
+ * tmax[i] -- i.e. when it returns min < tmax[i], except that a miss is not occluded when tmax[i] is +inf.  d_tmax NULL = FLT_MAX
+ * for every ray. */
+int rt_occluded(RtScene *scene, const float *d_origins, const float *d_directions, const float *d_tmax, int32_t n,
+                uint8_t *d_occluded, void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+/* The primary ray of every pixel of a camera, exactly as the render kernels make it (raycast.cu:156-188, the fp64 island
+ * included): DEVICE arrays [height * width][3], row-major (y * width + x); every origin is the camera position. */
+int rt_camera_rays(const RtCameraParams *cam, float *d_origins, float *d_directions, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
