@@ -3328,6 +3328,8 @@ int refit_mesh(RtScene* s, int32_t mesh_index, const float* vertices, const floa
             RT_HIP(hipMalloc((void**)&s->d_refit_scratch, need));
             s->refit_scratch_bytes = need;
         }
+        // (behind the previous host-array refit's last read of the scratch when that one ran on another stream; see RtScene)
+        if (s->refit_scratch_done && s->refit_scratch_stream != st) RT_HIP(hipStreamWaitEvent(st, s->refit_scratch_done, 0));
         // (the host arrays may be pageable: the copies return once the bytes are staged, and stay ordered on the stream)
         RT_HIP(hipMemcpyAsync(s->d_refit_scratch, vertices, nv * sizeof(float), hipMemcpyHostToDevice, st));
         RT_HIP(hipMemcpyAsync(s->d_refit_scratch + nv, normals, nn * sizeof(float), hipMemcpyHostToDevice, st));
@@ -3369,6 +3371,11 @@ int refit_mesh(RtScene* s, int32_t mesh_index, const float* vertices, const floa
     }
     flush();
     RT_HIP(hipGetLastError());
+    if (!on_device) {                                           // the last read of the scratch has been queued
+        if (!s->refit_scratch_done) RT_HIP(hipEventCreateWithFlags(&s->refit_scratch_done, hipEventDisableTiming));
+        RT_HIP(hipEventRecord(s->refit_scratch_done, st));
+        s->refit_scratch_stream = st;
+    }
     return RT_OK;
 }
 }  // namespace
@@ -3420,6 +3427,7 @@ int rt_scene_destroy(RtScene* s)
     }
     if (s->order.sort_stream) (void)hipStreamDestroy(s->order.sort_stream);
     for (auto& rf : s->mesh_refit) (void)hipFree(rf.d_sched);
+    if (s->refit_scratch_done) (void)hipEventDestroy(s->refit_scratch_done);
     (void)hipFree(s->d_refit_scratch);
     (void)hipFree(s->d_ex_scratch);
     for (auto& sl : s->view.slot) if (sl.done) (void)hipEventDestroy(sl.done);

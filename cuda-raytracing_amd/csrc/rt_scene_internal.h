@@ -44,6 +44,12 @@ struct RtScene {
     std::vector<MeshRefit> mesh_refit;
     float* d_refit_scratch = nullptr;            // vertices + normals of the mesh being refitted (grow-only)
     size_t refit_scratch_bytes = 0;
+    // One staging buffer serves every host-array refit of the scene, so a refit must not copy into it before the previous one's
+    // last kernel has read it.  On one stream that is stream order; a refit on ANOTHER stream waits for this event first (two
+    // meshes refitted on two streams would otherwise fold one mesh's vertices into the other's boxes: call_mu orders the host
+    // side only).  Recorded after the last kernel of every host-array refit, on its stream.
+    hipEvent_t refit_scratch_done = nullptr;
+    hipStream_t refit_scratch_stream = nullptr;
     int32_t num_materials = 0;
     int32_t max_stack = 1;
     size_t device_bytes = 0;

@@ -150,7 +150,9 @@ int rt_scene_update_instance_async(RtScene *scene, int32_t index, const RtInstan
  * gets the exact bounds of its triangles (what BVHTree::fill's bounds pass, BVHTree.hpp:206-209, would compute for that
  * node), triangle records are recomputed as at upload.  Ordered on `stream`: renders issued on it before the call see the
  * old mesh, renders after it the new one; the host arrays must stay valid until the stream has passed the call
- * (rt_stream_synchronize, or any later synchronising call).  No counterpart in the reference. */
+ * (rt_stream_synchronize, or any later synchronising call).  Host-array refits of one scene on different streams (of different
+ * meshes) are ordered against each other by the library; renders on other streams are still not ordered against a refit.
+ * No counterpart in the reference. */
 int rt_scene_refit_mesh(RtScene *scene, int32_t mesh_index, const float *vertices, const float *normals,
                         int32_t num_triangles, void *stream);
 /* the same with DEVICE arrays (a deformation computed on the GPU: skinning, simulation): no copy, the arrays are read by
