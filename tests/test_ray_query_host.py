@@ -109,3 +109,49 @@ def test_python_wrappers_check_before_the_device(rt, monkeypatch):
             s.trace_rays(a, b)
     assert not touched
     s.close()
+
+
+@pytest.mark.parametrize("seed", [0, 3, 5, 8])
+def test_query_fuzz_rules_on_the_oracle(orc, scenes, seed):
+    """What test_gpu_ray_query_fuzz.py relies on, pinned on the oracle (so that a GPU failure of these rules points at the kernel):
+    the ray families and bounds of test_fuzz_adversarial_queries[seed] are the same on every draw, every family is non-empty and hits
+    something; for every hit at t, occluded(tmax = t) is 0 and occluded(tmax = nextafter(t, +inf)) is 1, and a miss is never occluded."""
+    import query_rays as qr
+    desc, W, H, K, cam_pose, info = qr.query_scene(scenes, seed)
+    so = desc.build_oracle(orc)
+    try:
+        cam = ray_oracle.camera_rays(W, H, K, scenes.D_REF, cam_pose)
+        draws = []
+        for _ in range(2):
+            rng = np.random.default_rng(89000 + seed)
+            fams = qr.families(rng, so, cam, n=600)
+            o, d = qr.flatten(fams)
+            ref = ray_oracle.cast_rays(so, o, d)
+            tf = qr.tmax_families(rng, orc, desc, o, d, ref["t"])
+            draws.append((fams, tf))
+        (fa, ta), (fb, tb) = draws
+        assert [f[0] for f in fa] == [f[0] for f in fb] and [t[0] for t in ta] == [t[0] for t in tb]
+        for x, y in zip(fa, fb):
+            assert np.array_equal(x[1].view(np.uint32), y[1].view(np.uint32)) and np.array_equal(x[2].view(np.uint32), y[2].view(np.uint32)), x[0]
+        for x, y in zip(ta, tb):
+            assert np.array_equal(x[1].view(np.uint32), y[1].view(np.uint32)), x[0]
+        assert len(ta) == 4 + 3 * len(desc.instances)
+        # the octant blocks are whole waves of an unbinned call: the rays are a multiple of 64 long, and at least half the blocks'
+        # aligned 64-ray slots hold one world octant with no zero direction component
+        fo, fd = qr.flatten(fa)
+        assert len(fo) % 64 == 0 and fa[-1][0] == "octant_blocks" and len(fa[-1][1]) % 64 == 0
+        waves = fd.reshape(-1, 64, 3)
+        coherent = (np.signbit(waves) == np.signbit(waves[:, :1])).all(axis=(1, 2)) & (waves != 0).all(axis=(1, 2))
+        assert coherent[-len(fa[-1][1]) // 64:].sum() >= len(fa[-1][1]) // 128, info
+        for name, fo, fd in fa:
+            assert len(fo) > 0 and np.isfinite(fo).all() and np.isfinite(fd).all(), (info, name)
+            assert (ray_oracle.cast_rays(so, fo, fd)["instance"] >= 0).any(), (info, name)
+        hit = ref["instance"] >= 0
+        t = ref["t"]
+        at = ray_oracle.cast_rays(so, o, d, lighting_pass=1, tmax=t)["occluded"]
+        above = ray_oracle.cast_rays(so, o, d, lighting_pass=1, tmax=qr.around(t)[2])["occluded"]
+        assert not at[hit].any() and above[hit].all() and not above[~hit].any(), info
+        anyt = qr.special_tmax(np.random.default_rng(seed), len(o))
+        assert not ray_oracle.cast_rays(so, o, d, lighting_pass=1, tmax=anyt)["occluded"][~hit].any(), info
+    finally:
+        so.close()
