@@ -57,6 +57,10 @@ class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers,
     _fields_ = [(n, _vp) for n in ("t", "instance", "triangle", "location", "normal", "uv", "pops")]
 
 
+class RtPointHits(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL)
+    _fields_ = [(n, _vp) for n in ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "pops")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -70,7 +74,8 @@ RT_HIP_SYMBOLS = [
     "rt_render_debug", "rt_render_ids", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
-    "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays"]
+    "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
+    "rt_closest_points"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -200,6 +205,7 @@ def _declare(h, s):
     h.rt_trace_workspace_bytes.argtypes = [C.c_int32]
     h.rt_trace_rays.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtRayHits), _vp, C.c_size_t, _vp, C.c_int]
     h.rt_occluded.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_closest_points.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtPointHits), _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
     h.rt_timer_start.argtypes = [_vp, _vp]
@@ -499,6 +505,23 @@ class Scene:
         raycast.cu:129-133 -- uint8 [...], 1 where the cast accepts a hit closer than tmax (None: FLT_MAX for every ray; a
         float32 array of the rays' leading shape otherwise).  Arguments and paths as in trace_rays."""
         return _ray_query(self, origins, directions, tmax, ("occluded",), stream, binning)["occluded"]
+
+    POINT_OUTPUTS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "pops")    # the fields of RtPointHits
+
+    def closest_points(self, points, max_distance=None, outputs=("distance", "instance", "triangle"), stream=None):
+        """The nearest point of the scene's triangles to each of the caller's points (rt_closest_points; the rule, bit for bit a
+        brute-force minimum over every instance and triangle, is in include/rt_hip.h): dict of the wanted POINT_OUTPUTS --
+        distance [...] float32 (FLT_MAX on a miss), instance / triangle [...] int32 (-1 on a miss), point / normal [..., 3] float32
+        (world position of the closest point, world face normal), barycentric [..., 2] float32 (weights of v1 and v2), uv [..., 2]
+        float32, pops [...] int32 (interior nodes visited).  points: float32 [..., 3], contiguous.  max_distance: None (+inf) or
+        float32 of the points' leading shape; a triangle farther than it is no candidate (inclusive), NaN or negative = a miss.
+        torch tensors on the scene's (current) device: outputs are allocated there and the call is enqueued on `stream` (a
+        torch.cuda.Stream or a raw hipStream_t; default torch.cuda.current_stream()) without a synchronise.  numpy arrays: copied
+        to the device and back, the call synchronises."""
+        bad = [o for o in outputs if o not in self.POINT_OUTPUTS]
+        if bad or not outputs:
+            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.POINT_OUTPUTS, tuple(outputs)))
+        return _point_query(self, points, max_distance, tuple(outputs), stream)
 
     def info(self):
         b = C.c_size_t(0)
@@ -859,6 +882,71 @@ def _ray_query(scene, origins, directions, tmax, outputs, stream, binning):
         else:
             hits = RtRayHits(*[ptr.get(k) for k in Scene.RAY_OUTPUTS])
             check(h.rt_trace_rays(handle, args[0], args[1], n, C.byref(hits), args[3], ws_bytes, st, sync), "rt_trace_rays")
+        if torch_in:
+            return out
+        return {k: b.to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0]) for k, b in bufs.items()}
+    finally:
+        for b in keep:
+            b.free()
+
+
+def _point_query(scene, points, max_distance, outputs, stream):
+    """Scene.closest_points: every argument is checked before any device call."""
+    torch_in = type(points).__module__.split(".")[0] == "torch"
+    if max_distance is not None and torch_in != (type(max_distance).__module__.split(".")[0] == "torch"):
+        raise ValueError("points and max_distance must both be torch tensors or both numpy arrays")
+    if not torch_in and not all(isinstance(a, np.ndarray) for a in (points,) + (() if max_distance is None else (max_distance,))):
+        raise ValueError("points must be a numpy array or a torch tensor")
+    arrays = (points,) + (() if max_distance is None else (max_distance,))
+    for name, a in zip(("points", "max_distance"), arrays):
+        if str(a.dtype) not in ("float32", "torch.float32"):
+            raise ValueError("%s must be float32, got %s" % (name, a.dtype))
+        contiguous = a.is_contiguous() if torch_in else a.flags["C_CONTIGUOUS"]
+        if not contiguous:
+            raise ValueError("%s must be contiguous" % name)
+    if len(points.shape) < 1 or points.shape[-1] != 3:
+        raise ValueError("points must have the shape [..., 3], got %s" % (tuple(points.shape),))
+    lead = tuple(points.shape[:-1])
+    if max_distance is not None and tuple(max_distance.shape) != lead:
+        raise ValueError("max_distance must have the points' leading shape %s, got %s" % (lead, tuple(max_distance.shape)))
+    n = int(np.prod(lead, dtype=np.int64))
+    if n > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 points per call, got %d" % n)
+    if torch_in:
+        import torch
+        for name, a in zip(("points", "max_distance"), arrays):
+            if not a.is_cuda:
+                raise ValueError("%s is on %s: torch points must be on the scene's GPU" % (name, a.device))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        for name, a in zip(("points", "max_distance"), arrays):
+            if a.device != dev:
+                raise ValueError("%s is on %s, the scene's device is %s" % (name, a.device, dev))
+    h = libs()[0]
+    handle = scene.device_handle
+    shapes = dict(distance=(lead, np.float32), instance=(lead, np.int32), triangle=(lead, np.int32), point=(lead + (3,), np.float32),
+                  normal=(lead + (3,), np.float32), barycentric=(lead + (2,), np.float32), uv=(lead + (2,), np.float32),
+                  pops=(lead, np.int32))
+    if torch_in:
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        out = {k: torch.empty(shapes[k][0], dtype=tdt[shapes[k][1]], device=dev) for k in outputs}
+        ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        st = ts.cuda_stream
+        ptr = {k: v.data_ptr() for k, v in out.items()}
+        args = (points.data_ptr(), None if max_distance is None else max_distance.data_ptr())
+        sync, keep = 0, []
+    else:
+        keep = [DeviceBuffer(nbytes=max(a.nbytes, 1)) for a in arrays]
+        for b, a in zip(keep, arrays):
+            if a.nbytes:
+                check(h.rt_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes, stream), "rt_memcpy_h2d")
+        bufs = {k: DeviceBuffer(nbytes=max(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize, 1)) for k in outputs}
+        keep += list(bufs.values())
+        ptr = {k: b.ptr for k, b in bufs.items()}
+        args = (keep[0].ptr, keep[1].ptr if max_distance is not None else None)
+        st, sync = stream, 1
+    try:
+        hits = RtPointHits(*[ptr.get(k) for k in Scene.POINT_OUTPUTS])
+        check(h.rt_closest_points(handle, args[0], args[1], n, C.byref(hits), st, sync), "rt_closest_points")
         if torch_in:
             return out
         return {k: b.to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0]) for k, b in bufs.items()}

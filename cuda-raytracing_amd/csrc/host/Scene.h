@@ -15,6 +15,7 @@
 
 struct RtScene;
 struct RtRayHits;
+struct RtPointHits;
 
 class Scene {
 public:
@@ -53,6 +54,10 @@ public:
                    size_t workspace_bytes = 0, void* stream = nullptr, bool synchronize = false);
     int occluded(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, uint8_t* d_occluded,
                  void* d_workspace = nullptr, size_t workspace_bytes = 0, void* stream = nullptr, bool synchronize = false);
+    // Closest-point queries on the device scene: rt_closest_points of include/rt_hip.h, where the semantics are.  Points, bounds
+    // (optional, NULL = +inf) and outputs are DEVICE arrays.  Returns the status (also in last_error).
+    int closest_points(const float* d_points, const float* d_max_distance, int32_t n, const RtPointHits& out, void* stream = nullptr,
+                       bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

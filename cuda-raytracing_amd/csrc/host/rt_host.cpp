@@ -612,6 +612,12 @@ int Scene::occluded(const float* d_origins, const float* d_directions, const flo
     return last_error;
 }
 
+int Scene::closest_points(const float* d_points, const float* d_max_distance, int32_t n, const RtPointHits& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_closest_points(d_scene, d_points, d_max_distance, n, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

@@ -2516,6 +2516,235 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const FrameParams f, i
     dir[k * 3] = d.x; dir[k * 3 + 1] = d.y; dir[k * 3 + 2] = d.z;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Closest-point queries (rt_closest_points): the nearest point of the scene's triangles to each of the caller's points, equal bit for
+// bit to a brute-force minimum over every (instance, triangle) -- the rule is in include/rt_hip.h, the pruning argument in DESIGN.md
+// section 11.  One wave per workgroup, one point per lane, a nearest-first traversal of each instance's tree on the general stack.
+// ---------------------------------------------------------------------------------------------------------
+struct PointParams {
+    const float4* records;
+    const float* tri_uv;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* pts;           // [n][3] world points
+    const float* max_distance;  // [n] or null (= +inf)
+    int32_t n;
+    float* distance;            // outputs, each optional (null = not wanted)
+    int32_t *instance, *triangle;
+    float *point, *normal, *barycentric, *uv;
+    int32_t* pops;
+};
+constexpr int kPointBlock = 64;
+typedef StackT<kPointBlock> PointStack;
+
+// Ericson's closest point on triangle (A, A + AB, A + AC) to q (Real-Time Collision Detection 5.1.5), returned as the weights (b1, b2) of
+// AB and AC, in one fixed fp32 sequence.  An edge ratio whose denominator is not > 0 is 0 (and a ratio is never above 1).  Where the
+// classification reaches the face region with a negative va, vb or vc or a sum that is not > 0 (rounding on nearly degenerate
+// triangles; NaN input), the weights are those of the nearest of the three edges AB, AC, BC instead (first of equals in that order),
+// each the clamped projection onto its segment.  The weights are always finite, in [0, 1], and b1 + b2 <= 1 up to rounding.
+__device__ __forceinline__ float pq_ratio(float a, float b) { return b > 0.0f ? fminf(a / b, 1.0f) : 0.0f; }
+__device__ __forceinline__ float pq_d2(V3 d) { return (d.x * d.x + d.y * d.y) + d.z * d.z; }
+__device__ __forceinline__ V3 pq_combine(V3 a, V3 ab, V3 ac, float b1, float b2)
+{
+    return v3((a.x + b1 * ab.x) + b2 * ac.x, (a.y + b1 * ab.y) + b2 * ac.y, (a.z + b1 * ab.z) + b2 * ac.z);
+}
+// the clamped projection of q onto the segment p0 + t * d, t in [0, 1] (0 for a zero-length d)
+__device__ __forceinline__ float pq_segment(V3 q, V3 p0, V3 d)
+{
+    const float dd = dot(d, d);
+    const float t = dd > 0.0f ? dot(q - p0, d) / dd : 0.0f;
+    return t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;         // (a NaN t gives 0)
+}
+__device__ __noinline__ float2 pq_fallback(V3 q, V3 a, V3 ab, V3 ac)
+{
+    const float t0 = pq_segment(q, a, ab), t1 = pq_segment(q, a, ac), t2 = pq_segment(q, a + ab, ac - ab);
+    float2 w = make_float2(t0, 0.0f);
+    float best = pq_d2(q - pq_combine(a, ab, ac, t0, 0.0f));
+    const float e1 = pq_d2(q - pq_combine(a, ab, ac, 0.0f, t1));
+    if (e1 < best) { best = e1; w = make_float2(0.0f, t1); }
+    const float s = 1.0f - t2;
+    const float e2 = pq_d2(q - pq_combine(a, ab, ac, s, t2));
+    if (e2 < best) w = make_float2(s, t2);
+    return w;
+}
+__device__ __forceinline__ float2 pq_weights(V3 q, V3 a, V3 ab, V3 ac)
+{
+    const V3 ap = q - a;
+    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+    if (d1 <= 0.0f && d2 <= 0.0f) return make_float2(0.0f, 0.0f);                          // vertex A
+    const V3 bp = ap - ab;
+    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+    if (d3 >= 0.0f && d4 <= d3) return make_float2(1.0f, 0.0f);                            // vertex B
+    const float vc = d1 * d4 - d3 * d2;
+    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) return make_float2(pq_ratio(d1, d1 - d3), 0.0f);         // edge AB
+    const V3 cp = ap - ac;
+    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+    if (d6 >= 0.0f && d5 <= d6) return make_float2(0.0f, 1.0f);                            // vertex C
+    const float vb = d5 * d2 - d1 * d6;
+    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) return make_float2(0.0f, pq_ratio(d2, d2 - d6));         // edge AC
+    const float va = d3 * d6 - d5 * d4;
+    const float e43 = d4 - d3, e56 = d5 - d6;
+    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f) {                                        // edge BC
+        const float w = pq_ratio(e43, e43 + e56);
+        return make_float2(1.0f - w, w);
+    }
+    const float sum = (va + vb) + vc;
+    if (va >= 0.0f && vb >= 0.0f && vc >= 0.0f && sum > 0.0f) {                             // face
+        return make_float2(vb / sum, vc / sum);                                             // (each <= 1: vb, vc <= sum)
+    }
+    return pq_fallback(q, a, ab, ac);
+}
+
+// A triangle record's (A, AB, AC) in scaled mesh space: v0, e1 = v1 - v0 and e0 = v2 - v0 as stored, times the instance's scale
+__device__ __forceinline__ void pq_triangle(float4 t0, float4 t1, float4 t2, V3 s, V3& a, V3& ab, V3& ac)
+{
+    a = v3(t0.x * s.x, t0.y * s.y, t0.z * s.z);
+    ab = v3(t2.y * s.x, t2.z * s.y, t2.w * s.z);
+    ac = v3(t1.z * s.x, t1.w * s.y, t2.x * s.z);
+}
+
+// A lower bound of d2 (the same fp32 sum of squares) for every triangle whose vertices lie in the mesh-space box lo..hi (DESIGN.md
+// section 11): the box is scaled (a negative scale swaps the ends), widened by 2^-16 of its largest coordinate magnitude plus FLT_MIN,
+// and the gap per axis is taken only where a compare says it is positive, so a NaN anywhere gives 0 on that axis, never a prune.
+__device__ __forceinline__ float pq_gap(float lo, float hi, float s, float q)
+{
+    const float x = lo * s, y = hi * s;
+    const float l = s < 0.0f ? y : x, h = s < 0.0f ? x : y;
+    const float m = fmaxf(fabsf(l), fabsf(h)) * 0x1p-16f + 0x1p-126f;
+    const float a = (l - m) - q, b = q - (h + m);
+    return a > 0.0f ? a : (b > 0.0f ? b : 0.0f);
+}
+__device__ __forceinline__ float pq_box_lb(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 q)
+{
+    const float gx = pq_gap(lx, hx, s.x, q.x), gy = pq_gap(ly, hy, s.y, q.y), gz = pq_gap(lz, hz, s.z, q.z);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// The candidate bound in d2: the largest float x with sqrtf(x) <= max_distance (sqrtf is monotone, so sqrtf(d2) <= max_distance exactly
+// when d2 <= x), found by bisection over the bit patterns of [0, +inf]; -1 when no d2 passes (NaN or negative bound).
+__device__ __forceinline__ float pq_cut2(float maxd)
+{
+    if (!(0.0f <= maxd)) return -1.0f;                          // (sqrtf(0) = 0; -0 counts as 0)
+    const float inf = __int_as_float(0x7f800000);
+    if (sqrtf(inf) <= maxd) return inf;
+    uint32_t lo = 0u, hi = 0x7f800000u;                         // sqrtf(lo) <= maxd < sqrtf(hi)
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (sqrtf(__uint_as_float(mid)) <= maxd) lo = mid; else hi = mid;
+    }
+    return __uint_as_float(lo);
+}
+
+// world normal of triangle `slot` of instance `in`, as hit_normal gives it (raycast.cu:115-122)
+__device__ __forceinline__ V3 pq_normal(const PointParams& p, const DevInstance& in, int32_t slot)
+{
+    const float4* t = p.records + (size_t)slot * 4;
+    const float4 t0 = t[0], t1 = t[1];
+    V3 n = apply_quat(in.q_inv_rot, v3(t0.w, t1.x, t1.y));
+    n.x *= in.scale[0]; n.y *= in.scale[1]; n.z *= in.scale[2];
+    return normalize(n);
+}
+
+__global__ __launch_bounds__(kPointBlock, 8) void closest_point_kernel(const PointParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kPointBlock]
+    const int32_t i = (int32_t)blockIdx.x * kPointBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const size_t i3 = (size_t)i * 3;
+    const V3 w = v3(p.pts[i3], p.pts[i3 + 1], p.pts[i3 + 2]);
+    const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
+    int spill[kMaxStack - kLdsStack];
+    PointStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    // the best candidate so far by (d2, instance, tri_id); best_inst < 0 = none yet
+    float best = 0.0f, b1 = 0.0f, b2 = 0.0f;
+    int32_t best_inst = -1, best_slot = 0, best_tid = 0, pops = 0;
+    for (int32_t k = 0; k < p.num_instances && cut2 >= 0.0f; k++) {
+        const DevInstance& in = p.instances[k];
+        // the query point in scaled mesh space: to_mesh_space's origin before its inv_scale multiply
+        const V3 q = apply_quat(in.q_pose, v3(w.x - in.pose_xyz[0], w.y - in.pose_xyz[1], w.z - in.pose_xyz[2]));
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: both child boxes, nearer first
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const float la = pq_box_lb(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, q);
+                const float lb = pq_box_lb(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, q);
+                const float lim = best_inst >= 0 ? best : cut2;
+                const bool pa = !(prune && la > lim), pb = !(prune && lb > lim);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                const bool a_near = !(lb < la);
+                if (pa && pb) stack.push(a_near ? rb : ra);
+                cur = (pa && pb) ? (a_near ? ra : rb) : (pa ? ra : (pb ? rb : kNeedPop));
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    const float4 t0 = rec[0], t1 = rec[1], t2 = rec[2];
+                    V3 a, ab, ac;
+                    pq_triangle(t0, t1, t2, s, a, ab, ac);
+                    const float2 bw = pq_weights(q, a, ab, ac);
+                    const float d2 = pq_d2(q - pq_combine(a, ab, ac, bw.x, bw.y));
+                    if (d2 <= (best_inst >= 0 ? best : cut2)) {     // (NaN fails)
+                        const int32_t tid = p.tri_id[slot];
+                        if (best_inst < 0 || d2 < best || (best_inst == k && tid < best_tid)) {
+                            best = d2; b1 = bw.x; b2 = bw.y; best_inst = k; best_slot = slot; best_tid = tid;
+                        }
+                    }
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel);
+    }
+    const bool got = best_inst >= 0;
+    if (p.distance) p.distance[i] = got ? sqrtf(best) : FLT_MAX;
+    if (p.instance) p.instance[i] = got ? best_inst : -1;
+    if (p.triangle) p.triangle[i] = got ? best_tid : -1;
+    if (p.pops) p.pops[i] = pops;
+    if (p.barycentric) { p.barycentric[(size_t)i * 2] = got ? b1 : 0.0f; p.barycentric[(size_t)i * 2 + 1] = got ? b2 : 0.0f; }
+    if (!got) {
+        if (p.point) { p.point[i3] = 0.0f; p.point[i3 + 1] = 0.0f; p.point[i3 + 2] = 0.0f; }
+        if (p.normal) { p.normal[i3] = 0.0f; p.normal[i3 + 1] = 0.0f; p.normal[i3 + 2] = 0.0f; }
+        if (p.uv) { p.uv[(size_t)i * 2] = 0.0f; p.uv[(size_t)i * 2 + 1] = 0.0f; }
+        return;
+    }
+    const DevInstance& in = p.instances[best_inst];
+    if (p.point) {                                              // the winner's point again (same sequence), to world: apply_lre(inv_pose, c)
+        const float4* rec = p.records + (size_t)best_slot * 4;
+        V3 a, ab, ac;
+        pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+        const V3 c = pq_combine(a, ab, ac, b1, b2);
+        const V3 o = apply_quat(in.q_inv_pose, v3(c.x - in.inv_pose_xyz[0], c.y - in.inv_pose_xyz[1], c.z - in.inv_pose_xyz[2]));
+        p.point[i3] = o.x; p.point[i3 + 1] = o.y; p.point[i3 + 2] = o.z;
+    }
+    if (p.normal) {
+        const V3 n = pq_normal(p, in, best_slot);
+        p.normal[i3] = n.x; p.normal[i3 + 1] = n.y; p.normal[i3 + 2] = n.z;
+    }
+    if (p.uv) {                                                 // w = (1 - b2) - b1, uv = (w uv0 + b1 uv1) + b2 uv2 (base_colour's order)
+        const float* t = p.tri_uv + (size_t)best_slot * 6;
+        const float u0 = (1.0f - b2) - b1;
+        p.uv[(size_t)i * 2] = (u0 * t[0] + b1 * t[2]) + b2 * t[4];
+        p.uv[(size_t)i * 2 + 1] = (u0 * t[1] + b1 * t[3]) + b2 * t[5];
+    }
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -4035,6 +4264,34 @@ int rt_occluded(RtScene* s, const float* d_origins, const float* d_directions, c
     memset(&q, 0, sizeof q);
     q.org = d_origins; q.dir = d_directions; q.tmax = d_tmax; q.n = n; q.occluded = d_occluded;
     return launch_query(s, q, true, d_workspace, workspace_bytes, stream, synchronize);
+}
+
+int rt_closest_points(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, const RtPointHits* out, void* stream,
+                      int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_points || !out))) return RT_E_INVALID;
+    if (n > 0 && !(out->distance || out->instance || out->triangle || out->point || out->normal || out->barycentric || out->uv || out->pops))
+        return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    const hipStream_t st = (hipStream_t)stream;
+    {
+        RT_SCENE_CALL(s);
+        PointParams p;
+        memset(&p, 0, sizeof p);
+        p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
+        p.leaf_count = s->d_leaf_count; p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
+        p.num_instances = (int32_t)s->instances.size();
+        p.stack_depth = s->max_stack;
+        p.pts = d_points; p.max_distance = d_max_distance; p.n = n;
+        p.distance = out->distance; p.instance = out->instance; p.triangle = out->triangle;
+        p.point = out->point; p.normal = out->normal; p.barycentric = out->barycentric; p.uv = out->uv; p.pops = out->pops;
+        const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
+        const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
+        hipLaunchKernelGGL(closest_point_kernel, dim3(groups), dim3(kPointBlock), lds, st, p);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
 }
 
 int rt_camera_rays(const RtCameraParams* cam, float* d_origins, float* d_directions, void* stream, int synchronize)

@@ -420,6 +420,41 @@ int rt_occluded(RtScene *scene, const float *d_origins, const float *d_direction
  * included): DEVICE arrays [height * width][3], row-major (y * width + x); every origin is the camera position. */
 int rt_camera_rays(const RtCameraParams *cam, float *d_origins, float *d_directions, void *stream, int synchronize);
 
+/* ---- closest-point queries: the nearest point of the scene's triangles to each of the caller's points.
+ *      The result equals a brute-force minimum over every (instance, triangle) bit for bit; it does not depend on the tree
+ *      (host-built, device-built or refitted) nor on the order of traversal.  For world point p (fp32) and instance i:
+ *      1. q = apply_lre(pose_i, p): the value the ray casts compute for an origin before the inv_scale multiply.  This "scaled
+ *         mesh space" is world space rotated and translated, so distances there are world distances (any scale, mirrors too).
+ *      2. Per triangle, the stored fp32 v0, e1 = v1 - v0, e0 = v2 - v0 scaled componentwise: A = v0*s, AB = e1*s, AC = e0*s.
+ *         The closest point c = (A + b1*AB) + b2*AC per component, (b1, b2) from Ericson's region classification (Real-Time
+ *         Collision Detection 5.1.5) over A, AB, AC, one fixed fp32 sequence without contraction.  An edge ratio whose
+ *         denominator is not > 0 is 0, and none exceeds 1; the face weights are vb / sum and vc / sum.  Where the classification
+ *         reaches the face region with va, vb or vc < 0 or sum <= 0 (nearly degenerate triangles, NaN), (b1, b2) is instead the
+ *         nearest of the clamped projections onto the edges AB, AC, BC (first of equals in that order; a zero-length edge
+ *         projects to its start).  So degenerate triangles never divide by zero and finite input gives a finite point.
+ *      3. d2 = (dx*dx + dy*dy) + dz*dz in fp32 with d = q - c.
+ *      4. A triangle is a candidate when d2 is not NaN and sqrtf(d2) <= max_distance[j] (inclusive; NULL = +inf).  A NaN or
+ *         negative bound gives a miss (-0 counts as 0).  An overflowed d2 = +inf is a candidate under an infinite bound only.
+ *      5. The winner is the candidate with the smallest (d2, instance index, triangle index), compared in that order; the
+ *         triangle index is the caller's (rt_render_ids' and rt_trace_rays' numbering).
+ *      Points are a DEVICE array [n][3]; outputs are optional tight DEVICE arrays indexed like the points.  Points with a
+ *      non-finite component do not fault and do not change other points' results; their own results are unspecified.
+ *      Asynchronous on `stream` unless synchronize != 0; nothing is launched when n == 0.  No scene scratch is used: calls may
+ *      overlap each other and renders on other streams; a scene change on another stream is not ordered against them.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL points or no output at all with n > 0. ------------------------------------------- */
+typedef struct RtPointHits {    /* every pointer optional (NULL = not wanted) */
+    float   *distance;          /* sqrtf(d2) of the winner; FLT_MAX on a miss                                           */
+    int32_t *instance;          /* the winner's instance index, -1 on a miss                                            */
+    int32_t *triangle;          /* the winner's triangle index as uploaded (rt_render_ids' numbering), -1 on a miss     */
+    float   *point;             /* [n][3] world position of c: apply_lre(inv_pose_i, c), raycast.cu:98-102's map; 0 on a miss */
+    float   *normal;            /* [n][3] world face normal, as rt_trace_rays gives it; 0 on a miss                     */
+    float   *barycentric;       /* [n][2] (b1, b2): the weights of v1 and v2; 0 on a miss                               */
+    float   *uv;                /* [n][2] texture uv: w = (1 - b2) - b1, (w*uv0 + b1*uv1) + b2*uv2 per component; 0 on a miss */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic, not part of the bit-exact contract)         */
+} RtPointHits;
+int rt_closest_points(RtScene *scene, const float *d_points, const float *d_max_distance, int32_t n, const RtPointHits *out,
+                      void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
