@@ -61,6 +61,10 @@ class RtPointHits(C.Structure):             # include/rt_hip.h (device pointers,
     _fields_ = [(n, _vp) for n in ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "pops")]
 
 
+class RtCrossings(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL)
+    _fields_ = [(n, _vp) for n in ("count", "winding", "pops")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -75,7 +79,7 @@ RT_HIP_SYMBOLS = [
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
-    "rt_closest_points"]
+    "rt_closest_points", "rt_count_crossings", "rt_winding_numbers", "rt_signed_distance"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -206,6 +210,9 @@ def _declare(h, s):
     h.rt_trace_rays.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtRayHits), _vp, C.c_size_t, _vp, C.c_int]
     h.rt_occluded.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_closest_points.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtPointHits), _vp, C.c_int]
+    h.rt_count_crossings.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(RtCrossings), _vp, C.c_int]
+    h.rt_winding_numbers.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_int]
+    h.rt_signed_distance.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
     h.rt_timer_start.argtypes = [_vp, _vp]
@@ -522,6 +529,44 @@ class Scene:
         if bad or not outputs:
             raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.POINT_OUTPUTS, tuple(outputs)))
         return _point_query(self, points, max_distance, tuple(outputs), stream)
+
+    CROSSING_OUTPUTS = ("count", "winding", "pops")     # the fields of RtCrossings
+
+    def count_crossings(self, origins, directions, tmax=None, outputs=("count", "winding"), stream=None):
+        """Crossings of the scene's triangles along each of the caller's rays (rt_count_crossings; the rule, equal to a brute-force
+        count over every instance and triangle, is in include/rt_hip.h): dict of the wanted CROSSING_OUTPUTS, each int32 of the rays'
+        leading shape -- count (triangles crossed at 0 < t <= tmax, both faces), winding (+1 per crossing leaving a mesh wound
+        counter-clockwise seen from outside, -1 per crossing entering it), pops (interior nodes visited).  origins / directions:
+        float32 [..., 3], contiguous.  tmax: None (+inf) or float32 of the rays' leading shape, a ray parameter (with directions
+        b - a and tmax 1, count is the crossings of the segment ab).  torch tensors: asynchronous on `stream` (default the current
+        stream); numpy arrays: copied to the device and back, the call synchronises."""
+        bad = [o for o in outputs if o not in self.CROSSING_OUTPUTS]
+        if bad or not outputs:
+            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.CROSSING_OUTPUTS, tuple(outputs)))
+        outputs = tuple(outputs)
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            c = RtCrossings(*[ptr.get(k) for k in Scene.CROSSING_OUTPUTS])
+            check(h.rt_count_crossings(handle, ins[0], ins[1], ins[2], n, C.byref(c), st, sync), "rt_count_crossings")
+        return _device_query(self, [("origins", origins), ("directions", directions), ("tmax", tmax)],
+                               {k: ((), np.int32) for k in outputs}, call, stream)
+
+    def winding_numbers(self, points, stream=None):
+        """The winding number of each of the caller's points (rt_winding_numbers): int32 of the points' leading shape, the median of
+        the windings along three fixed directions (include/rt_hip.h rule 6); nonzero = inside.  points: float32 [..., 3].  Paths as
+        in count_crossings."""
+        def call(h, handle, ins, ptr, n, st, sync):
+            check(h.rt_winding_numbers(handle, ins[0], n, ptr["winding"], st, sync), "rt_winding_numbers")
+        return _device_query(self, [("points", points)], {"winding": ((), np.int32)}, call, stream)["winding"]
+
+    def signed_distance(self, points, max_distance=None, stream=None):
+        """Signed distance of each of the caller's points (rt_signed_distance): float32 of the points' leading shape, closest_points'
+        distance (same points, same max_distance) negated where winding_numbers is not 0 -- so -0.0 and -FLT_MAX occur.  points:
+        float32 [..., 3]; max_distance: None (+inf) or float32 of the points' leading shape.  Paths as in count_crossings."""
+        def call(h, handle, ins, ptr, n, st, sync):
+            check(h.rt_signed_distance(handle, ins[0], ins[1], n, ptr["sdf"], None, st, sync), "rt_signed_distance")
+        return _device_query(self, [("points", points), ("max_distance", max_distance)], {"sdf": ((), np.float32)}, call,
+                               stream)["sdf"]
 
     def info(self):
         b = C.c_size_t(0)
@@ -891,62 +936,82 @@ def _ray_query(scene, origins, directions, tmax, outputs, stream, binning):
 
 
 def _point_query(scene, points, max_distance, outputs, stream):
-    """Scene.closest_points: every argument is checked before any device call."""
-    torch_in = type(points).__module__.split(".")[0] == "torch"
-    if max_distance is not None and torch_in != (type(max_distance).__module__.split(".")[0] == "torch"):
-        raise ValueError("points and max_distance must both be torch tensors or both numpy arrays")
-    if not torch_in and not all(isinstance(a, np.ndarray) for a in (points,) + (() if max_distance is None else (max_distance,))):
-        raise ValueError("points must be a numpy array or a torch tensor")
-    arrays = (points,) + (() if max_distance is None else (max_distance,))
-    for name, a in zip(("points", "max_distance"), arrays):
+    """Scene.closest_points: every argument is checked before any device call (_device_query)."""
+    shapes = dict(distance=((), np.float32), instance=((), np.int32), triangle=((), np.int32), point=((3,), np.float32),
+                  normal=((3,), np.float32), barycentric=((2,), np.float32), uv=((2,), np.float32), pops=((), np.int32))
+
+    def call(h, handle, ins, ptr, n, st, sync):
+        hits = RtPointHits(*[ptr.get(k) for k in Scene.POINT_OUTPUTS])
+        check(h.rt_closest_points(handle, ins[0], ins[1], n, C.byref(hits), st, sync), "rt_closest_points")
+    return _device_query(scene, [("points", points), ("max_distance", max_distance)], {k: shapes[k] for k in outputs}, call, stream)
+
+
+def _device_query(scene, inputs, outs, call, stream):
+    """Scene.closest_points / count_crossings / winding_numbers / signed_distance: every argument is checked before any device
+    call.  inputs: (name, array) pairs, the first [..., 3], "directions" of the same shape, the others of the leading shape; None =
+    not given.  outs: name -> (trailing shape, dtype).  call(h, handle, input pointers, output pointers, n, stream, synchronize) makes the C-ABI call."""
+    given = [(k, a) for k, a in inputs if a is not None]
+    torch_in = type(given[0][1]).__module__.split(".")[0] == "torch"
+    if any((type(a).__module__.split(".")[0] == "torch") != torch_in for _k, a in given):
+        raise ValueError("%s must all be torch tensors or all numpy arrays" % ", ".join(k for k, _a in given))
+    if not torch_in and not all(isinstance(a, np.ndarray) for _k, a in given):
+        raise ValueError("%s must be numpy arrays or torch tensors" % ", ".join(k for k, _a in given))
+    for name, a in given:
         if str(a.dtype) not in ("float32", "torch.float32"):
             raise ValueError("%s must be float32, got %s" % (name, a.dtype))
         contiguous = a.is_contiguous() if torch_in else a.flags["C_CONTIGUOUS"]
         if not contiguous:
             raise ValueError("%s must be contiguous" % name)
-    if len(points.shape) < 1 or points.shape[-1] != 3:
-        raise ValueError("points must have the shape [..., 3], got %s" % (tuple(points.shape),))
-    lead = tuple(points.shape[:-1])
-    if max_distance is not None and tuple(max_distance.shape) != lead:
-        raise ValueError("max_distance must have the points' leading shape %s, got %s" % (lead, tuple(max_distance.shape)))
+    first, a0 = given[0]
+    if len(a0.shape) < 1 or a0.shape[-1] != 3:
+        raise ValueError("%s must have the shape [..., 3], got %s" % (first, tuple(a0.shape)))
+    lead = tuple(a0.shape[:-1])
+    for name, a in inputs[1:]:
+        if a is None:
+            continue
+        want = tuple(a0.shape) if name == "directions" else lead
+        if tuple(a.shape) != want:
+            raise ValueError("%s must have the shape %s, got %s" % (name, want, tuple(a.shape)))
     n = int(np.prod(lead, dtype=np.int64))
     if n > 2 ** 31 - 1:
-        raise ValueError("at most 2^31 - 1 points per call, got %d" % n)
+        raise ValueError("at most 2^31 - 1 queries per call, got %d" % n)
     if torch_in:
         import torch
-        for name, a in zip(("points", "max_distance"), arrays):
+        for name, a in given:
             if not a.is_cuda:
-                raise ValueError("%s is on %s: torch points must be on the scene's GPU" % (name, a.device))
+                raise ValueError("%s is on %s: torch inputs must be on the scene's GPU" % (name, a.device))
         dev = torch.device("cuda", torch.cuda.current_device())
-        for name, a in zip(("points", "max_distance"), arrays):
+        for name, a in given:
             if a.device != dev:
                 raise ValueError("%s is on %s, the scene's device is %s" % (name, a.device, dev))
     h = libs()[0]
     handle = scene.device_handle
-    shapes = dict(distance=(lead, np.float32), instance=(lead, np.int32), triangle=(lead, np.int32), point=(lead + (3,), np.float32),
-                  normal=(lead + (3,), np.float32), barycentric=(lead + (2,), np.float32), uv=(lead + (2,), np.float32),
-                  pops=(lead, np.int32))
+    shapes = {k: (lead + tr, dt) for k, (tr, dt) in outs.items()}
     if torch_in:
         tdt = {np.float32: torch.float32, np.int32: torch.int32}
-        out = {k: torch.empty(shapes[k][0], dtype=tdt[shapes[k][1]], device=dev) for k in outputs}
+        out = {k: torch.empty(shapes[k][0], dtype=tdt[shapes[k][1]], device=dev) for k in outs}
         ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
         st = ts.cuda_stream
         ptr = {k: v.data_ptr() for k, v in out.items()}
-        args = (points.data_ptr(), None if max_distance is None else max_distance.data_ptr())
+        ins = [None if a is None else a.data_ptr() for _k, a in inputs]
         sync, keep = 0, []
     else:
-        keep = [DeviceBuffer(nbytes=max(a.nbytes, 1)) for a in arrays]
-        for b, a in zip(keep, arrays):
+        keep, ins = [], []
+        for _k, a in inputs:
+            if a is None:
+                ins.append(None)
+                continue
+            b = DeviceBuffer(nbytes=max(a.nbytes, 1))
+            keep.append(b)
             if a.nbytes:
                 check(h.rt_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes, stream), "rt_memcpy_h2d")
-        bufs = {k: DeviceBuffer(nbytes=max(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize, 1)) for k in outputs}
+            ins.append(b.ptr)
+        bufs = {k: DeviceBuffer(nbytes=max(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize, 1)) for k in outs}
         keep += list(bufs.values())
         ptr = {k: b.ptr for k, b in bufs.items()}
-        args = (keep[0].ptr, keep[1].ptr if max_distance is not None else None)
         st, sync = stream, 1
     try:
-        hits = RtPointHits(*[ptr.get(k) for k in Scene.POINT_OUTPUTS])
-        check(h.rt_closest_points(handle, args[0], args[1], n, C.byref(hits), st, sync), "rt_closest_points")
+        call(h, handle, ins, ptr, n, st, sync)
         if torch_in:
             return out
         return {k: b.to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0]) for k, b in bufs.items()}

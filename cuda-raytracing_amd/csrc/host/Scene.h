@@ -16,6 +16,7 @@
 struct RtScene;
 struct RtRayHits;
 struct RtPointHits;
+struct RtCrossings;
 
 class Scene {
 public:
@@ -58,6 +59,13 @@ public:
     // (optional, NULL = +inf) and outputs are DEVICE arrays.  Returns the status (also in last_error).
     int closest_points(const float* d_points, const float* d_max_distance, int32_t n, const RtPointHits& out, void* stream = nullptr,
                        bool synchronize = false);
+    // Crossing counts, winding numbers and signed distance on the device scene: rt_count_crossings / rt_winding_numbers /
+    // rt_signed_distance of include/rt_hip.h, where the semantics are.  Inputs and outputs are DEVICE arrays.  Return the status.
+    int count_crossings(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, const RtCrossings& out,
+                        void* stream = nullptr, bool synchronize = false);
+    int winding_numbers(const float* d_points, int32_t n, int32_t* d_winding, void* stream = nullptr, bool synchronize = false);
+    int signed_distance(const float* d_points, const float* d_max_distance, int32_t n, float* d_sdf, int32_t* d_winding = nullptr,
+                        void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

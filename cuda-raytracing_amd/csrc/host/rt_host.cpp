@@ -618,6 +618,27 @@ int Scene::closest_points(const float* d_points, const float* d_max_distance, in
     return last_error;
 }
 
+int Scene::count_crossings(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, const RtCrossings& out,
+                           void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_count_crossings(d_scene, d_origins, d_directions, d_tmax, n, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::winding_numbers(const float* d_points, int32_t n, int32_t* d_winding, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_winding_numbers(d_scene, d_points, n, d_winding, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::signed_distance(const float* d_points, const float* d_max_distance, int32_t n, float* d_sdf, int32_t* d_winding, void* stream,
+                           bool synchronize)
+{
+    last_error = d_scene ? rt_signed_distance(d_scene, d_points, d_max_distance, n, d_sdf, d_winding, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

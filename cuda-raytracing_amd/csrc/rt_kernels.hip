@@ -2745,6 +2745,209 @@ __global__ __launch_bounds__(kPointBlock, 8) void closest_point_kernel(const Poi
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Ray crossing counts and winding numbers (rt_count_crossings / rt_winding_numbers / rt_signed_distance): every triangle a ray
+// crosses within (0, tmax], both faces, with the sign of the crossing -- equal to a brute-force count over every (instance,
+// triangle); the rule is in include/rt_hip.h, the pruning argument in DESIGN.md section 12.  One wave per workgroup, one ray (or
+// point) per lane, an unordered traversal of each instance's tree on the general stack: every child the ray may cross is visited.
+// ---------------------------------------------------------------------------------------------------------
+struct CrossParams {
+    const float4* records;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* org;           // [n][3] ray origins (the point form: the points)
+    const float* dir;           // [n][3] ray directions (the point form: unused)
+    const float* tmax;          // [n] or null (= +inf; the point form: unused)
+    int32_t n;
+    int32_t *count, *winding, *pops;    // outputs, each optional (the point form: winding = the median winding; no count, no pops)
+    float* sdf;                 // the point form: holds rt_closest_points' distance, negated where the winding is not 0
+};
+constexpr int kCrossBlock = 64;
+typedef StackT<kCrossBlock> CrossStack;
+
+__device__ __forceinline__ float xq_sel(V3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+
+// The exact signs of U, V, W when the fp32 ones hold a zero: the products of fp32 values are exact in fp64, and a nonzero difference
+// that rounds to 0 in fp32 (below 2^-150) becomes +-2^-149, so the sign survives the rounding (rare: out of line)
+__device__ __forceinline__ float xq_narrow(double x)
+{
+    const float f = (float)x;
+    return f == 0.0f && x != 0.0 ? (x > 0.0 ? 0x1p-149f : -0x1p-149f) : f;
+}
+__device__ __noinline__ float3 xq_edges64(float ax, float ay, float bx, float by, float cx, float cy)
+{
+    return make_float3(xq_narrow((double)cx * (double)by - (double)cy * (double)bx), xq_narrow((double)ax * (double)cy - (double)ay * (double)cx),
+                       xq_narrow((double)bx * (double)ay - (double)by * (double)ax));
+}
+
+// The ray in one instance's scaled mesh space, set up for the watertight test (Woop, Benthin, Wald, JCGT 2(1) 2013)
+struct XqRay {
+    V3 o;                       // o' = apply_lre(pose, o)
+    float ox, oy, oz;           // o' permuted to (kx, ky, kz)
+    float sx, sy, sz;           // the shear constants
+    V3 inv;                     // 1 / d' per axis (the slab test)
+    int kx, ky, kz;
+    float omax;                 // max_k |o'_k| (NaN-free: fmaxf)
+    bool zero;                  // d' == 0
+};
+
+__device__ __forceinline__ XqRay xq_ray(const DevInstance& in, V3 w, V3 d)
+{
+    XqRay r;
+    r.o = apply_quat(in.q_pose, v3(w.x - in.pose_xyz[0], w.y - in.pose_xyz[1], w.z - in.pose_xyz[2]));
+    const V3 dd = apply_quat(in.q_pose, d);
+    const float ax = fabsf(dd.x), ay = fabsf(dd.y), az = fabsf(dd.z);
+    int kz = 0;
+    float m = ax;
+    if (ay > m) { kz = 1; m = ay; }
+    if (az > m) kz = 2;
+    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+    const float dz = xq_sel(dd, kz);
+    r.zero = dz == 0.0f;
+    if (dz < 0.0f) { const int t = kx; kx = ky; ky = t; }
+    r.kx = kx; r.ky = ky; r.kz = kz;
+    r.sx = xq_sel(dd, kx) / dz; r.sy = xq_sel(dd, ky) / dz; r.sz = 1.0f / dz;
+    r.ox = xq_sel(r.o, kx); r.oy = xq_sel(r.o, ky); r.oz = xq_sel(r.o, kz);
+    r.inv = v3(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z);
+    r.omax = fmaxf(fmaxf(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z));
+    return r;
+}
+
+// rule 3 of include/rt_hip.h on the triangle (A, A + AB, A + AC): 0 = not counted, else the sign of the crossing (+1 leaving)
+__device__ __forceinline__ int xq_triangle(const XqRay& r, V3 a, V3 ab, V3 ac, float tmax)
+{
+    const V3 b = a + ab, c = a + ac;
+    const float az = xq_sel(a, r.kz) - r.oz, bz = xq_sel(b, r.kz) - r.oz, cz = xq_sel(c, r.kz) - r.oz;
+    const float ax = (xq_sel(a, r.kx) - r.ox) - r.sx * az, ay = (xq_sel(a, r.ky) - r.oy) - r.sy * az;
+    const float bx = (xq_sel(b, r.kx) - r.ox) - r.sx * bz, by = (xq_sel(b, r.ky) - r.oy) - r.sy * bz;
+    const float cx = (xq_sel(c, r.kx) - r.ox) - r.sx * cz, cy = (xq_sel(c, r.ky) - r.oy) - r.sy * cz;
+    float u = cx * by - cy * bx, v = ax * cy - ay * cx, w = bx * ay - by * ax;
+    if (u == 0.0f || v == 0.0f || w == 0.0f) {
+        const float3 e = xq_edges64(ax, ay, bx, by, cx, cy);
+        u = e.x; v = e.y; w = e.z;
+    }
+    const bool neg = u <= 0.0f && v <= 0.0f && w <= 0.0f, pos = u >= 0.0f && v >= 0.0f && w >= 0.0f;
+    const float det = (u + v) + w;
+    if (!(neg || pos) || det == 0.0f) return 0;
+    const float T = (u * (r.sz * az) + v * (r.sz * bz)) + w * (r.sz * cz);
+    const float t = T / det;
+    if (!(t > 0.0f && t <= tmax)) return 0;
+    return det < 0.0f ? 1 : -1;
+}
+
+// Whether a counted triangle may lie in the mesh-space box lo..hi: the box is scaled (a negative scale swaps
+// the ends) and widened by 2^-16 of (its largest coordinate magnitude + the origin's) plus FLT_MIN; it is kept when the ray's line
+// meets it (an axis whose slab gives a NaN does not constrain) and its kz slab is not wholly behind the origin.  Boxes with a
+// coordinate magnitude above 2^60 (or a NaN one) are always kept.
+__device__ __forceinline__ bool xq_box(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, const XqRay& r)
+{
+    const float x0 = lx * s.x, x1 = hx * s.x, y0 = ly * s.y, y1 = hy * s.y, z0 = lz * s.z, z1 = hz * s.z;
+    const float bmax = fmaxf(fmaxf(fmaxf(fabsf(x0), fabsf(x1)), fmaxf(fabsf(y0), fabsf(y1))), fmaxf(fabsf(z0), fabsf(z1)));
+    if (!(bmax <= 0x1p60f)) return true;
+    const float m = (bmax + r.omax) * 0x1p-16f + 0x1p-126f;
+    float tn = -__int_as_float(0x7f800000), tf = __int_as_float(0x7f800000), fz = tf;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float a = k == 0 ? x0 : (k == 1 ? y0 : z0), b = k == 0 ? x1 : (k == 1 ? y1 : z1);
+        const float o = k == 0 ? r.o.x : (k == 1 ? r.o.y : r.o.z), inv = k == 0 ? r.inv.x : (k == 1 ? r.inv.y : r.inv.z);
+        const float t1 = ((fminf(a, b) - m) - o) * inv, t2 = ((fmaxf(a, b) + m) - o) * inv;
+        if (t1 == t1 && t2 == t2) {                             // (a NaN slab: no constraint)
+            tn = fmaxf(tn, fminf(t1, t2));
+            const float f = fmaxf(t1, t2);
+            tf = fminf(tf, f);
+            if (k == r.kz) fz = f;
+        }
+    }
+    return !(tn > tf) && !(fz < 0.0f);
+}
+
+// One ray through every instance: count, winding and pops of rule 5
+__device__ __forceinline__ void xq_trace(const CrossParams& p, CrossStack& stack, V3 w, V3 d, float tmax, int32_t& count,
+                                         int32_t& winding, int32_t& pops)
+{
+    for (int32_t k = 0; k < p.num_instances; k++) {
+        const DevInstance& in = p.instances[k];
+        const XqRay r = xq_ray(in, w, d);
+        if (r.zero) continue;                                   // (a zero d' counts nothing)
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        // (unordered / NaN boxes, or an origin beyond 2^60: no pruning in this instance)
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0 && r.omax <= 0x1p60f;
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: every child the ray may cross, no order
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const bool pa = !prune || xq_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, r);
+                const bool pb = !prune || xq_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, r);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                if (pa && pb) stack.push(rb);
+                cur = pa ? ra : (pb ? rb : kNeedPop);
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    V3 a, ab, ac;
+                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
+                    const int sign = xq_triangle(r, a, ab, ac, tmax);
+                    count += sign != 0 ? 1 : 0;
+                    winding += sign;
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel);
+    }
+}
+
+// POINT = false: rt_count_crossings, one ray per lane.  POINT = true: rt_winding_numbers / rt_signed_distance, one point per lane,
+// the median of the windings along RT_WINDING_D1..D3 (one kernel, two instantiations: the point form only adds the loop over the
+// three directions around the same traversal).
+template <bool POINT>
+__global__ __launch_bounds__(kCrossBlock, 8) void crossing_kernel(const CrossParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kCrossBlock]
+    const int32_t i = (int32_t)blockIdx.x * kCrossBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const size_t i3 = (size_t)i * 3;
+    const V3 w = v3(p.org[i3], p.org[i3 + 1], p.org[i3 + 2]);
+    int spill[kMaxStack - kLdsStack];
+    CrossStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    int32_t count = 0, winding = 0, pops = 0;
+    if constexpr (!POINT) {
+        const float tmax = p.tmax ? p.tmax[i] : __int_as_float(0x7f800000);
+        xq_trace(p, stack, w, v3(p.dir[i3], p.dir[i3 + 1], p.dir[i3 + 2]), tmax, count, winding, pops);
+        if (p.count) p.count[i] = count;
+        if (p.winding) p.winding[i] = winding;
+        if (p.pops) p.pops[i] = pops;
+    } else {
+        constexpr float d1[3] = RT_WINDING_D1, d2[3] = RT_WINDING_D2, d3[3] = RT_WINDING_D3;
+        int32_t w0 = 0, w1 = 0, w2 = 0;
+#pragma unroll 1
+        for (int j = 0; j < 3; j++) {
+            const V3 d = j == 0 ? v3(d1[0], d1[1], d1[2]) : (j == 1 ? v3(d2[0], d2[1], d2[2]) : v3(d3[0], d3[1], d3[2]));
+            int32_t c = 0, wj = 0;
+            xq_trace(p, stack, w, d, __int_as_float(0x7f800000), c, wj, pops);
+            w0 = j == 0 ? wj : w0; w1 = j == 1 ? wj : w1; w2 = j == 2 ? wj : w2;
+        }
+        const int32_t med = max(min(w0, w1), min(max(w0, w1), w2));
+        if (p.winding) p.winding[i] = med;
+        if (p.sdf && med != 0) p.sdf[i] = -p.sdf[i];
+    }
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -4288,6 +4491,81 @@ int rt_closest_points(RtScene* s, const float* d_points, const float* d_max_dist
         const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
         const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
         hipLaunchKernelGGL(closest_point_kernel, dim3(groups), dim3(kPointBlock), lds, st, p);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+extern "C++" {
+namespace {
+CrossParams crossing_params(const RtScene* s)
+{
+    CrossParams p;
+    memset(&p, 0, sizeof p);
+    p.records = s->d_records; p.leaf_count = s->d_leaf_count; p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
+    p.num_instances = (int32_t)s->instances.size();
+    p.stack_depth = s->max_stack;
+    return p;
+}
+template <bool POINT>
+void launch_crossings(const CrossParams& p, hipStream_t st)
+{
+    const unsigned groups = (unsigned)(((int64_t)p.n + kCrossBlock - 1) / kCrossBlock);
+    const size_t lds = (size_t)lds_rows(p.stack_depth) * kCrossBlock * sizeof(int);
+    hipLaunchKernelGGL(crossing_kernel<POINT>, dim3(groups), dim3(kCrossBlock), lds, st, p);
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_count_crossings(RtScene* s, const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n,
+                       const RtCrossings* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_origins || !d_directions || !out))) return RT_E_INVALID;
+    if (n > 0 && !(out->count || out->winding || out->pops)) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    {
+        RT_SCENE_CALL(s);
+        CrossParams p = crossing_params(s);
+        p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n;
+        p.count = out->count; p.winding = out->winding; p.pops = out->pops;
+        launch_crossings<false>(p, (hipStream_t)stream);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_winding_numbers(RtScene* s, const float* d_points, int32_t n, int32_t* d_winding, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_points || !d_winding))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;
+    {
+        RT_SCENE_CALL(s);
+        CrossParams p = crossing_params(s);
+        p.org = d_points; p.n = n; p.winding = d_winding;
+        launch_crossings<true>(p, (hipStream_t)stream);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_signed_distance(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, float* d_sdf, int32_t* d_winding,
+                       void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_points || !d_sdf))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;
+    {
+        RT_SCENE_CALL(s);
+        RtPointHits hits;
+        memset(&hits, 0, sizeof hits);
+        hits.distance = d_sdf;                                   // the distance first, then negated in place where inside
+        const int rc = rt_closest_points(s, d_points, d_max_distance, n, &hits, stream, 0);
+        if (rc != RT_OK) return rc;
+        CrossParams p = crossing_params(s);
+        p.org = d_points; p.n = n; p.winding = d_winding; p.sdf = d_sdf;
+        launch_crossings<true>(p, (hipStream_t)stream);
         RT_HIP(hipGetLastError());
     }
     RT_WAIT_IF(synchronize, stream);

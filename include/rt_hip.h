@@ -455,6 +455,59 @@ typedef struct RtPointHits {    /* every pointer optional (NULL = not wanted) */
 int rt_closest_points(RtScene *scene, const float *d_points, const float *d_max_distance, int32_t n, const RtPointHits *out,
                       void *stream, int synchronize);
 
+/* ---- ray crossing counts, winding numbers and signed distance.  Integer results equal a brute-force
+ *      count over every (instance, triangle), whatever the tree (host-built, device-built or refitted) and the order of traversal.
+ *      For a ray (o, d), world fp32, and instance i:
+ *      1. o' = apply_lre(pose_i, o), the map of rt_closest_points step 1; d' = apply_quat(q_pose_i, d), the direction rotated by
+ *         the POSE quaternion.  (rt_trace_rays rotates d by the instance's `rotation` instead; the two agree for every instance
+ *         made through the host API, whose rotation is the pose's ypr.  A C-ABI caller passing another rotation gets the
+ *         geometry rt_closest_points sees.)
+ *      2. The triangle A = v0*s, B = A + AB, C = A + AC, with A, AB, AC as in rt_closest_points step 2; the sums are fp32.
+ *      3. The watertight ray/triangle test of Woop, Benthin and Wald (JCGT 2(1), 2013), one fixed fp32 sequence, no contraction:
+ *         kz = the axis of the largest |d'| (first of equals in x, y, z order), kx = kz+1 mod 3, ky = kx+1 mod 3, kx and ky
+ *         swapped when d'[kz] < 0.  Sx = d'[kx] / d'[kz], Sy = d'[ky] / d'[kz], Sz = 1 / d'[kz].  Per vertex P, p = P - o',
+ *         px = p[kx] - Sx*p[kz], py = p[ky] - Sy*p[kz], pz = Sz*p[kz].  With a, b, c the vertices A, B, C:
+ *         U = cx*by - cy*bx, V = ax*cy - ay*cx, W = bx*ay - by*ax; if any of U, V, W is 0, all three are recomputed in fp64
+ *         from the same fp32 px, py and rounded to fp32, a nonzero value that rounds to 0 becoming +-2^-149 (the products are
+ *         exact in fp64, so the signs are exact, and they survive the rounding).  A crossing
+ *         needs (U, V, W all >= 0 or all <= 0; NaN fails both) and det = (U + V) + W != 0; then T = (U*az + V*bz) + W*cz and
+ *         t = T / det.  The triangle is COUNTED when t > 0 and t <= tmax (NaN fails both).  Both faces count (rt_trace_rays
+ *         never hits a back face).  A zero d' counts nothing.
+ *      4. The sign of a counted triangle is +1 when det < 0, else -1: a ray LEAVING a closed mesh whose triangles are counter-
+ *         clockwise seen from outside (the OBJ convention) counts +1, one entering it -1.  A mirrored instance (an odd number of
+ *         negative scale components) flips that, as it flips its world triangles.
+ *      5. count = the number of counted (instance, triangle) pairs, winding = the sum of their signs.  tmax is a ray PARAMETER
+ *         (not a Euclidean distance as in rt_occluded): with d = b - a and tmax = 1, count is the number of crossings of the
+ *         segment ab.  d_tmax NULL = +inf.  Rays with a non-finite component do not fault and do not change other rays'
+ *         results; their own results are unspecified.
+ *      6. The winding number of a point is the MEDIAN of its windings along RT_WINDING_D1..D3 (world directions, tmax = +inf).
+ *         Triangles are stored as v0 and edge vectors, so B = A + AB can differ by rounding from the neighbouring triangle's
+ *         vertex (always so with s != 1): a ray through such a shared edge can leak or count twice.  The test is not watertight
+ *         across shared edges; the median of three fixed directions makes a wrong point need two unlucky rays.  Inside is
+ *         winding != 0 (the nonzero rule); overlapping instances add up; a mirrored instance gives -1 inside.
+ *      7. sdf = winding != 0 ? -distance : distance (fp32), distance exactly rt_closest_points' for the same point and
+ *         max_distance, so -0.0 (a point on the surface counted inside) and -FLT_MAX (inside, no triangle within max_distance)
+ *         occur.  The sign follows rule 6, not the nearest triangle's normal (normals give wrong signs at edges and vertices).
+ *      Inputs are DEVICE arrays [n][3] (tmax / max_distance [n]); outputs are optional tight DEVICE arrays indexed like them.
+ *      Asynchronous on `stream` unless synchronize != 0; nothing is launched when n == 0.  No workspace and no scene scratch: calls
+ *      may overlap each other and renders on other streams; a scene change on another stream is not ordered against them.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL inputs or no output with n > 0. ---------------------------------------------------- */
+#define RT_WINDING_D1 { 0x1.24b5dcp-1f, 0x1.3e5c92p-2f, 0x1.84c2f8p-1f }    /* ( 0.5717, 0.3109,  0.7593) */
+#define RT_WINDING_D2 { -0x1.3f212ep-1f, 0x1.6d9e84p-1f, 0x1.46594ap-2f }   /* (-0.6233, 0.7141,  0.3187) */
+#define RT_WINDING_D3 { 0x1.2809d4p-2f, 0x1.488ce8p-1f, -0x1.6bac72p-1f }   /* ( 0.2891, 0.6417, -0.7103) */
+typedef struct RtCrossings {    /* every pointer optional (NULL = not wanted) */
+    int32_t *count;             /* [n] counted (instance, triangle) pairs                                              */
+    int32_t *winding;           /* [n] the sum of their signs                                                          */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic, not part of the exact contract)            */
+} RtCrossings;
+int rt_count_crossings(RtScene *scene, const float *d_origins, const float *d_directions, const float *d_tmax, int32_t n,
+                       const RtCrossings *out, void *stream, int synchronize);
+int rt_winding_numbers(RtScene *scene, const float *d_points, int32_t n, int32_t *d_winding, void *stream, int synchronize);
+/* d_sdf required; d_winding optional (the median winding of rule 6).  Runs rt_closest_points' kernel, then the winding kernel, on
+ * `stream`. */
+int rt_signed_distance(RtScene *scene, const float *d_points, const float *d_max_distance, int32_t n, float *d_sdf,
+                       int32_t *d_winding, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
