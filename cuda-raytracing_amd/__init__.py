@@ -65,6 +65,10 @@ class RtCrossings(C.Structure):             # include/rt_hip.h (device pointers,
     _fields_ = [(n, _vp) for n in ("count", "winding", "pops")]
 
 
+class RtCrossingList(C.Structure):          # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in ("t", "instance", "triangle", "sign", "barycentric", "uv", "point", "count")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -79,7 +83,8 @@ RT_HIP_SYMBOLS = [
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
-    "rt_closest_points", "rt_count_crossings", "rt_winding_numbers", "rt_signed_distance"]
+    "rt_closest_points", "rt_count_crossings", "rt_winding_numbers", "rt_signed_distance", "rt_crossing_offsets_workspace_bytes",
+    "rt_crossing_offsets", "rt_list_crossings"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -213,6 +218,10 @@ def _declare(h, s):
     h.rt_count_crossings.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(RtCrossings), _vp, C.c_int]
     h.rt_winding_numbers.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_int]
     h.rt_signed_distance.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int]
+    h.rt_crossing_offsets_workspace_bytes.restype = C.c_size_t
+    h.rt_crossing_offsets_workspace_bytes.argtypes = [C.c_int32]
+    h.rt_crossing_offsets.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_list_crossings.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtCrossingList), _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
     h.rt_timer_start.argtypes = [_vp, _vp]
@@ -567,6 +576,27 @@ class Scene:
             check(h.rt_signed_distance(handle, ins[0], ins[1], n, ptr["sdf"], None, st, sync), "rt_signed_distance")
         return _device_query(self, [("points", points), ("max_distance", max_distance)], {"sdf": ((), np.float32)}, call,
                                stream)["sdf"]
+
+    CROSSING_LIST_OUTPUTS = ("t", "instance", "triangle", "sign", "barycentric", "uv", "point")     # the fields of RtCrossingList
+
+    def list_crossings(self, origins, directions, tmax=None, max_hits=None, outputs=CROSSING_LIST_OUTPUTS, stream=None):
+        """Every triangle each of the caller's rays crosses, sorted by (t, instance, triangle) (rt_crossing_offsets /
+        rt_list_crossings; the pairs are exactly count_crossings' pairs, include/rt_hip.h rule 8).  Fields: t (float32, a ray
+        parameter), instance / triangle (int32), sign (int8, +1 leaving a mesh wound counter-clockwise seen from outside), barycentric
+        / uv ([2] float32), point ([3] float32, world).  origins / directions / tmax as in count_crossings.
+        max_hits=None (CSR): dict of `offsets` (int64 [n + 1], ray j's hits at offsets[j]:offsets[j+1]), the wanted fields over all
+        hits ([total], [total, 2], [total, 3]), `ray` (int32 [total], the flat index of each hit's ray) and `count` (int32 of the
+        rays' leading shape).  On torch this makes exactly ONE host synchronisation (reading offsets[n] to size the outputs).
+        max_hits=K >= 1: the first K hits of each ray, fields [..., K] / [..., K, 2|3] padded with t = inf, instance = triangle = -1,
+        sign 0 and float 0, plus `count` (the full count, so count > K means truncated); on torch fully asynchronous on `stream`.
+        numpy arrays: copied to the device and back, the call synchronises."""
+        bad = [o for o in outputs if o not in self.CROSSING_LIST_OUTPUTS]
+        if bad or not outputs:
+            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.CROSSING_LIST_OUTPUTS, tuple(outputs)))
+        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not
+                                     1 <= int(max_hits) <= 2 ** 31 - 1):
+            raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
+        return _list_query(self, origins, directions, tmax, None if max_hits is None else int(max_hits), tuple(outputs), stream)
 
     def info(self):
         b = C.c_size_t(0)
@@ -946,10 +976,10 @@ def _point_query(scene, points, max_distance, outputs, stream):
     return _device_query(scene, [("points", points), ("max_distance", max_distance)], {k: shapes[k] for k in outputs}, call, stream)
 
 
-def _device_query(scene, inputs, outs, call, stream):
-    """Scene.closest_points / count_crossings / winding_numbers / signed_distance: every argument is checked before any device
-    call.  inputs: (name, array) pairs, the first [..., 3], "directions" of the same shape, the others of the leading shape; None =
-    not given.  outs: name -> (trailing shape, dtype).  call(h, handle, input pointers, output pointers, n, stream, synchronize) makes the C-ABI call."""
+def _query_inputs(inputs):
+    """The argument checks of _device_query and _list_query, before any device call -> (torch_in, leading shape, n, device).
+    inputs: (name, array) pairs, the first [..., 3], "directions" of the same shape, the others of the leading shape; None = not
+    given."""
     given = [(k, a) for k, a in inputs if a is not None]
     torch_in = type(given[0][1]).__module__.split(".")[0] == "torch"
     if any((type(a).__module__.split(".")[0] == "torch") != torch_in for _k, a in given):
@@ -975,6 +1005,7 @@ def _device_query(scene, inputs, outs, call, stream):
     n = int(np.prod(lead, dtype=np.int64))
     if n > 2 ** 31 - 1:
         raise ValueError("at most 2^31 - 1 queries per call, got %d" % n)
+    dev = None
     if torch_in:
         import torch
         for name, a in given:
@@ -984,6 +1015,106 @@ def _device_query(scene, inputs, outs, call, stream):
         for name, a in given:
             if a.device != dev:
                 raise ValueError("%s is on %s, the scene's device is %s" % (name, a.device, dev))
+    return torch_in, lead, n, dev
+
+
+_LIST_FIELDS = dict(t=((), np.float32), instance=((), np.int32), triangle=((), np.int32), sign=((), np.int8),
+                    barycentric=((2,), np.float32), uv=((2,), np.float32), point=((3,), np.float32))
+
+
+def _list_query(scene, origins, directions, tmax, max_hits, outputs, stream):
+    """Scene.list_crossings: every argument is checked before any device call (_query_inputs).  t, instance and triangle are always
+    filled (the room keeps the keys, so the kernel inserts rather than selects); the ones not wanted are dropped."""
+    inputs = [("origins", origins), ("directions", directions), ("tmax", tmax)]
+    torch_in, lead, n, dev = _query_inputs(inputs)
+    h = libs()[0]
+    handle = scene.device_handle
+    fields = tuple(k for k in Scene.CROSSING_LIST_OUTPUTS if k in outputs or k in ("t", "instance", "triangle"))
+    csr = max_hits is None
+    if torch_in:
+        import torch
+        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int8: torch.int8}
+        ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        st = ts.cuda_stream
+        ins = [None if a is None else a.data_ptr() for _k, a in inputs]
+        count = torch.empty(lead, dtype=torch.int32, device=dev)
+        offsets = None
+        if csr:
+            with torch.cuda.stream(ts):
+                offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+                ws = torch.empty(max(int(h.rt_crossing_offsets_workspace_bytes(n)), 1), dtype=torch.uint8, device=dev)
+                check(h.rt_crossing_offsets(handle, ins[0], ins[1], ins[2], n, offsets.data_ptr(), ws.data_ptr(), ws.numel(), st, 0),
+                      "rt_crossing_offsets")
+                total = int(offsets[n].item())                  # the one host synchronisation: the size of the outputs
+            rows = (total,)
+        else:
+            rows = lead + (max_hits,)
+        with torch.cuda.stream(ts):
+            out = {k: torch.empty(rows + _LIST_FIELDS[k][0], dtype=tdt[_LIST_FIELDS[k][1]], device=dev) for k in fields}
+            lst = RtCrossingList(*[out[k].data_ptr() if k in out else None for k in Scene.CROSSING_LIST_OUTPUTS], count.data_ptr())
+            check(h.rt_list_crossings(handle, ins[0], ins[1], ins[2], n, None if offsets is None else offsets.data_ptr(),
+                                      0 if csr else max_hits, C.byref(lst), st, 0), "rt_list_crossings")
+            res = {k: out[k] for k in Scene.CROSSING_LIST_OUTPUTS if k in outputs}
+            if csr:
+                res["offsets"] = offsets
+                res["ray"] = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev), offsets[1:] - offsets[:-1],
+                                                     output_size=total)
+        res["count"] = count
+        return res
+    keep, ins = [], []
+    try:
+        for _k, a in inputs:
+            if a is None:
+                ins.append(None)
+                continue
+            b = DeviceBuffer(nbytes=max(a.nbytes, 1))
+            keep.append(b)
+            if a.nbytes:
+                check(h.rt_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes, stream), "rt_memcpy_h2d")
+            ins.append(b.ptr)
+
+        def buf(nbytes):
+            b = DeviceBuffer(nbytes=max(int(nbytes), 1))
+            keep.append(b)
+            return b
+        offsets = None
+        if csr:
+            ob = buf((n + 1) * 8)
+            if n > 0:
+                wsb = int(h.rt_crossing_offsets_workspace_bytes(n))
+                ws = buf(wsb)
+                check(h.rt_crossing_offsets(handle, ins[0], ins[1], ins[2], n, ob.ptr, ws.ptr, wsb, stream, 1), "rt_crossing_offsets")
+                offsets = ob.to_host(np.int64)[:n + 1]
+            else:
+                offsets = np.zeros(1, np.int64)
+            rows = (int(offsets[n]),)
+        else:
+            rows = lead + (max_hits,)
+        shapes = {k: (rows + _LIST_FIELDS[k][0], _LIST_FIELDS[k][1]) for k in fields}
+        bufs = {k: buf(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize) for k in fields}
+        cb = buf(n * 4)
+        lst = RtCrossingList(*[bufs[k].ptr if k in bufs else None for k in Scene.CROSSING_LIST_OUTPUTS], cb.ptr)
+        check(h.rt_list_crossings(handle, ins[0], ins[1], ins[2], n, ob.ptr if csr else None, 0 if csr else max_hits, C.byref(lst),
+                                  stream, 1), "rt_list_crossings")
+        res = {k: bufs[k].to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0])
+               for k in Scene.CROSSING_LIST_OUTPUTS if k in outputs}
+        res["count"] = cb.to_host(np.int32)[:n].reshape(lead)
+        if csr:
+            res["offsets"] = offsets
+            res["ray"] = np.repeat(np.arange(n, dtype=np.int32), np.diff(offsets))
+        return res
+    finally:
+        for b in keep:
+            b.free()
+
+
+def _device_query(scene, inputs, outs, call, stream):
+    """Scene.closest_points / count_crossings / winding_numbers / signed_distance: every argument is checked before any device
+    call.  inputs: (name, array) pairs, the first [..., 3], "directions" of the same shape, the others of the leading shape; None =
+    not given.  outs: name -> (trailing shape, dtype).  call(h, handle, input pointers, output pointers, n, stream, synchronize) makes the C-ABI call."""
+    torch_in, lead, n, dev = _query_inputs(inputs)
+    if torch_in:
+        import torch
     h = libs()[0]
     handle = scene.device_handle
     shapes = {k: (lead + tr, dt) for k, (tr, dt) in outs.items()}

@@ -17,6 +17,7 @@ struct RtScene;
 struct RtRayHits;
 struct RtPointHits;
 struct RtCrossings;
+struct RtCrossingList;
 
 class Scene {
 public:
@@ -66,6 +67,12 @@ public:
     int winding_numbers(const float* d_points, int32_t n, int32_t* d_winding, void* stream = nullptr, bool synchronize = false);
     int signed_distance(const float* d_points, const float* d_max_distance, int32_t n, float* d_sdf, int32_t* d_winding = nullptr,
                         void* stream = nullptr, bool synchronize = false);
+    // Crossing lists on the device scene: rt_crossing_offsets / rt_list_crossings of include/rt_hip.h (rule 8, rooms), where the
+    // semantics are.  Inputs, offsets, workspace and outputs are DEVICE arrays.  Return the status.
+    int crossing_offsets(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, int64_t* d_offsets,
+                         void* d_workspace, size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
+    int list_crossings(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, const int64_t* d_offsets,
+                       int32_t max_hits, const RtCrossingList& out, void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

@@ -639,6 +639,23 @@ int Scene::signed_distance(const float* d_points, const float* d_max_distance, i
     return last_error;
 }
 
+int Scene::crossing_offsets(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, int64_t* d_offsets,
+                            void* d_workspace, size_t workspace_bytes, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_crossing_offsets(d_scene, d_origins, d_directions, d_tmax, n, d_offsets, d_workspace, workspace_bytes, stream,
+                                               synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::list_crossings(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, const int64_t* d_offsets,
+                          int32_t max_hits, const RtCrossingList& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_list_crossings(d_scene, d_origins, d_directions, d_tmax, n, d_offsets, max_hits, &out, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

@@ -2948,6 +2948,294 @@ __global__ __launch_bounds__(kCrossBlock, 8) void crossing_kernel(const CrossPar
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Crossing lists (rt_crossing_offsets / rt_list_crossings): every counted (instance, triangle) pair of rt_count_crossings, in the
+// order (t, instance, triangle), written into the ray's own room of the output (include/rt_hip.h rule 8).
+// The traversal is xq_trace's (same XqRay, xq_box and pruning), so the set of pairs is count_crossings' set.
+// ---------------------------------------------------------------------------------------------------------
+struct CrossListParams {
+    const float4* records;
+    const float* tri_uv;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* org;           // [n][3] ray origins
+    const float* dir;           // [n][3] ray directions
+    const float* tmax;          // [n] or null (= +inf)
+    int32_t n;
+    const int64_t* offsets;     // [n + 1] (CSR rooms) or null: fixed rooms of max_hits
+    int32_t max_hits;
+    float* t;                   // outputs, each optional (indexed by room slot; count by ray)
+    int32_t *instance, *triangle;
+    int8_t* sign;
+    float *barycentric, *uv, *point;
+    int32_t* count;
+};
+
+// xq_triangle with what the list needs of the test: the same fp32 sequence and fp64 fallback; on a counted triangle also t, V, W
+// and det (b1 = V / det, b2 = W / det)
+__device__ __forceinline__ int xq_triangle_uvw(const XqRay& r, V3 a, V3 ab, V3 ac, float tmax, float& t_out, float& v_out, float& w_out,
+                                               float& det_out)
+{
+    const V3 b = a + ab, c = a + ac;
+    const float az = xq_sel(a, r.kz) - r.oz, bz = xq_sel(b, r.kz) - r.oz, cz = xq_sel(c, r.kz) - r.oz;
+    const float ax = (xq_sel(a, r.kx) - r.ox) - r.sx * az, ay = (xq_sel(a, r.ky) - r.oy) - r.sy * az;
+    const float bx = (xq_sel(b, r.kx) - r.ox) - r.sx * bz, by = (xq_sel(b, r.ky) - r.oy) - r.sy * bz;
+    const float cx = (xq_sel(c, r.kx) - r.ox) - r.sx * cz, cy = (xq_sel(c, r.ky) - r.oy) - r.sy * cz;
+    float u = cx * by - cy * bx, v = ax * cy - ay * cx, w = bx * ay - by * ax;
+    if (u == 0.0f || v == 0.0f || w == 0.0f) {
+        const float3 e = xq_edges64(ax, ay, bx, by, cx, cy);
+        u = e.x; v = e.y; w = e.z;
+    }
+    const bool neg = u <= 0.0f && v <= 0.0f && w <= 0.0f, pos = u >= 0.0f && v >= 0.0f && w >= 0.0f;
+    const float det = (u + v) + w;
+    if (!(neg || pos) || det == 0.0f) return 0;
+    const float T = (u * (r.sz * az) + v * (r.sz * bz)) + w * (r.sz * cz);
+    const float t = T / det;
+    if (!(t > 0.0f && t <= tmax)) return 0;
+    t_out = t; v_out = v; w_out = w; det_out = det;
+    return det < 0.0f ? 1 : -1;
+}
+
+// xq_trace's traversal, calling hit(k, slot, t, v, w, det, sign) at each counted triangle (instances in ascending order, triangles of
+// one instance in tree order).  The ray is read again at each instance, so it is not held in registers across the traversal.
+template <typename Hit>
+__device__ __forceinline__ void xl_trace(const CrossListParams& p, CrossStack& stack, size_t i3, float tmax, Hit&& hit)
+{
+    for (int32_t k = 0; k < p.num_instances; k++) {
+        const DevInstance& in = p.instances[k];
+        const XqRay r = xq_ray(in, v3(p.org[i3], p.org[i3 + 1], p.org[i3 + 2]), v3(p.dir[i3], p.dir[i3 + 1], p.dir[i3 + 2]));
+        if (r.zero) continue;
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0 && r.omax <= 0x1p60f;
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const bool pa = !prune || xq_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, r);
+                const bool pb = !prune || xq_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, r);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                if (pa && pb) stack.push(rb);
+                cur = pa ? ra : (pb ? rb : kNeedPop);
+            } else {
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    V3 a, ab, ac;
+                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
+                    float t = 0.0f, tv = 0.0f, tw = 0.0f, det = 1.0f;
+                    const int sign = xq_triangle_uvw(r, a, ab, ac, tmax, t, tv, tw, det);
+                    if (sign != 0) hit(k, slot, t, tv, tw, det, sign);
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel);
+    }
+}
+
+// ray i's room: start and size (CSR: offsets[i] and offsets[i+1] - offsets[i], 0 when not positive; fixed: i*K and K)
+__device__ __forceinline__ void xl_room(const CrossListParams& p, int32_t i, size_t& start, uint64_t& room)
+{
+    if (p.offsets) {
+        const int64_t s0 = p.offsets[i], s1 = p.offsets[i + 1];
+        start = (size_t)s0;
+        room = s1 > s0 ? (uint64_t)s1 - (uint64_t)s0 : 0u;
+    } else {
+        start = (size_t)i * (size_t)p.max_hits;
+        room = (uint64_t)p.max_hits;
+    }
+}
+
+// one entry of a room: slot j (absolute) <- the counted pair (k, slot) of ray i
+__device__ __forceinline__ void xl_store(const CrossListParams& p, size_t j, int32_t i, int32_t k, int32_t slot, int32_t tid, float t, float b1,
+                                         float b2, int sign)
+{
+    if (p.t) p.t[j] = t;
+    if (p.instance) p.instance[j] = k;
+    if (p.triangle) p.triangle[j] = tid;
+    if (p.sign) p.sign[j] = (int8_t)sign;
+    if (p.barycentric) { p.barycentric[2 * j] = b1; p.barycentric[2 * j + 1] = b2; }
+    if (p.uv) {                                                 // w = (1 - b2) - b1, uv = (w uv0 + b1 uv1) + b2 uv2 (rt_closest_points')
+        const float* q = p.tri_uv + (size_t)slot * 6;
+        const float u0 = (1.0f - b2) - b1;
+        p.uv[2 * j] = (u0 * q[0] + b1 * q[2]) + b2 * q[4];
+        p.uv[2 * j + 1] = (u0 * q[1] + b1 * q[3]) + b2 * q[5];
+    }
+    if (p.point) {                                              // o + t*d per component, world
+        const size_t i3 = (size_t)i * 3;
+        for (int c = 0; c < 3; c++) p.point[3 * j + c] = p.org[i3 + c] + t * p.dir[i3 + c];
+    }
+}
+
+// SELECT = false (t, instance and triangle all given): one traversal, each counted pair inserted into the room, which stays sorted
+// by (t, instance, triangle) -- lane-private, no atomics; once the room is full a pair enters only below the last entry.
+// SELECT = true (a key field not given, so the room cannot hold the keys): one traversal per filled slot, each finding the least key
+// above the previous slot's, kept in registers.  Both then pad the rest of the room and write the full count.
+template <bool SELECT>
+__global__ __launch_bounds__(kCrossBlock, 8) void crossing_list_kernel(const CrossListParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kCrossBlock]
+    const int32_t i = (int32_t)blockIdx.x * kCrossBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const size_t i3 = (size_t)i * 3;
+    const float tmax = p.tmax ? p.tmax[i] : __int_as_float(0x7f800000);
+    int spill[kMaxStack - kLdsStack];
+    CrossStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    int32_t total = 0, filled = 0;                              // (filled <= total: int32)
+    if constexpr (!SELECT) {
+        xl_trace(p, stack, i3, tmax, [&](int32_t k, int32_t slot, float t, float tv, float tw, float det, int sign) {
+            total++;
+            size_t start;
+            uint64_t room;
+            xl_room(p, i, start, room);                         // (read again per pair: not held across the traversal)
+            if (room == 0) return;
+            int32_t tid;
+            uint64_t pos;
+            if ((uint64_t)filled < room) {
+                pos = (uint64_t)filled++;
+                tid = p.tri_id[slot];
+            } else {                                            // full: enter only below the last entry
+                const size_t last = start + (size_t)(room - 1);
+                const float lt = p.t[last];
+                if (t > lt) return;
+                if (t == lt) {
+                    if (k > p.instance[last]) return;           // (instances arrive in ascending order: k >= the last's)
+                    tid = p.tri_id[slot];
+                    if (tid > p.triangle[last]) return;
+                } else {
+                    tid = p.tri_id[slot];
+                }
+                pos = room - 1;
+            }
+            while (pos > 0) {                                   // shift the greater keys up by one slot
+                const size_t q = start + (size_t)(pos - 1);
+                const float qt = p.t[q];
+                if (qt < t) break;
+                if (qt == t) {
+                    const int32_t qi = p.instance[q];
+                    if (qi < k || (qi == k && p.triangle[q] < tid)) break;
+                }
+                p.t[q + 1] = qt;
+                p.instance[q + 1] = p.instance[q];
+                p.triangle[q + 1] = p.triangle[q];
+                if (p.sign) p.sign[q + 1] = p.sign[q];
+                if (p.barycentric) { p.barycentric[2 * q + 2] = p.barycentric[2 * q]; p.barycentric[2 * q + 3] = p.barycentric[2 * q + 1]; }
+                if (p.uv) { p.uv[2 * q + 2] = p.uv[2 * q]; p.uv[2 * q + 3] = p.uv[2 * q + 1]; }
+                if (p.point) {
+                    p.point[3 * q + 3] = p.point[3 * q]; p.point[3 * q + 4] = p.point[3 * q + 1]; p.point[3 * q + 5] = p.point[3 * q + 2];
+                }
+                pos--;
+            }
+            xl_store(p, start + (size_t)pos, i, k, slot, tid, t, tv / det, tw / det, sign);
+        });
+    } else {
+        // pass j finds the least key (t, instance, triangle) above the last one stored; pass 0 also counts.  min(count, room)
+        // passes, at least one.  The winner's b1, b2 and sign come from testing its triangle again (the same sequence).
+        float lt = 0.0f;
+        int32_t lk = -1, ltid = -1;
+        for (;;) {
+            float bt = 0.0f;
+            int32_t bk = -1, bslot = 0, btid = 0;
+            const bool first = filled == 0 && lk < 0;
+            xl_trace(p, stack, i3, tmax, [&](int32_t k, int32_t slot, float t, float, float, float, int) {
+                if (first) total++;
+                if (lk >= 0) {                                  // above the last key?
+                    if (t < lt || (t == lt && k < lk)) return;
+                    if (t == lt && k == lk && p.tri_id[slot] <= ltid) return;
+                }
+                if (bk >= 0 && (t > bt || (t == bt && k > bk))) return;
+                const int32_t tid = p.tri_id[slot];
+                if (bk >= 0 && t == bt && k == bk && tid > btid) return;
+                bt = t; bk = k; bslot = slot; btid = tid;
+            });
+            size_t start;
+            uint64_t room;
+            xl_room(p, i, start, room);
+            if (bk < 0 || (uint64_t)filled >= room) break;
+            const DevInstance& in = p.instances[bk];
+            const XqRay r = xq_ray(in, v3(p.org[i3], p.org[i3 + 1], p.org[i3 + 2]), v3(p.dir[i3], p.dir[i3 + 1], p.dir[i3 + 2]));
+            const float4* rec = p.records + (size_t)bslot * 4;
+            V3 a, ab, ac;
+            pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+            float t = 0.0f, tv = 0.0f, tw = 0.0f, det = 1.0f;
+            const int sign = xq_triangle_uvw(r, a, ab, ac, tmax, t, tv, tw, det);
+            xl_store(p, start + (size_t)filled, i, bk, bslot, btid, bt, tv / det, tw / det, sign);
+            filled++;
+            if ((uint64_t)filled >= room || filled >= total) break;
+            lt = bt; lk = bk; ltid = btid;
+        }
+    }
+    size_t start;
+    uint64_t room;
+    xl_room(p, i, start, room);
+    for (uint64_t j = (uint64_t)filled; j < room; j++) {        // padding
+        const size_t q = start + (size_t)j;
+        if (p.t) p.t[q] = __int_as_float(0x7f800000);
+        if (p.instance) p.instance[q] = -1;
+        if (p.triangle) p.triangle[q] = -1;
+        if (p.sign) p.sign[q] = 0;
+        if (p.barycentric) { p.barycentric[2 * q] = 0.0f; p.barycentric[2 * q + 1] = 0.0f; }
+        if (p.uv) { p.uv[2 * q] = 0.0f; p.uv[2 * q + 1] = 0.0f; }
+        if (p.point) { p.point[3 * q] = 0.0f; p.point[3 * q + 1] = 0.0f; p.point[3 * q + 2] = 0.0f; }
+    }
+    if (p.count) p.count[i] = total;
+}
+
+// Exclusive int64 scan for rt_crossing_offsets: out[j] = the sum of in[..j) within blocks of kScanBlock elements (in[j] = 0 for
+// j >= n_in), sums[block] = the block's total.  In place is allowed (each thread reads its elements before any is written).
+constexpr int kScanThreads = 256, kScanItems = 4, kScanBlock = kScanThreads * kScanItems;
+template <typename T>
+__global__ __launch_bounds__(kScanThreads) void scan_block_kernel(const T* in, int64_t n_in, int64_t* out, int64_t m, int64_t* sums)
+{
+    __shared__ long long part[kScanThreads / 64];
+    const int64_t base = (int64_t)blockIdx.x * kScanBlock + (int64_t)threadIdx.x * kScanItems;
+    long long v[kScanItems], s = 0;
+#pragma unroll
+    for (int k = 0; k < kScanItems; k++) {
+        v[k] = base + k < n_in ? (long long)in[base + k] : 0;
+        s += v[k];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long x = s;                                            // inclusive scan over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const long long y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) part[wave] = x;
+    __syncthreads();
+    long long run = x - s;
+    for (int k = 0; k < wave; k++) run += part[k];
+#pragma unroll
+    for (int k = 0; k < kScanItems; k++) {
+        if (base + k < m) out[base + k] = run;
+        run += v[k];
+    }
+    if (threadIdx.x == kScanThreads - 1) sums[blockIdx.x] = run;
+}
+__global__ __launch_bounds__(kScanThreads) void scan_add_kernel(int64_t* out, int64_t m, const int64_t* sums)
+{
+    const int64_t base = (int64_t)blockIdx.x * kScanBlock + (int64_t)threadIdx.x * kScanItems;
+    const int64_t add = sums[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kScanItems; k++)
+        if (base + k < m) out[base + k] += add;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -4566,6 +4854,100 @@ int rt_signed_distance(RtScene* s, const float* d_points, const float* d_max_dis
         CrossParams p = crossing_params(s);
         p.org = d_points; p.n = n; p.winding = d_winding; p.sdf = d_sdf;
         launch_crossings<true>(p, (hipStream_t)stream);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+extern "C++" {
+namespace {
+// rt_crossing_offsets' workspace: the counts (int32 [n]), then the block totals of each level of the scan over n + 1 elements
+constexpr size_t kScanAlign = 256;
+size_t scan_align(size_t b) { return (b + kScanAlign - 1) / kScanAlign * kScanAlign; }
+size_t crossing_offsets_bytes(int64_t n, int64_t* level_blocks, int* levels)
+{
+    size_t bytes = scan_align((size_t)n * sizeof(int32_t));
+    int64_t m = n + 1;
+    int l = 0;
+    for (;;) {
+        const int64_t b = (m + kScanBlock - 1) / kScanBlock;
+        if (level_blocks) level_blocks[l] = b;
+        bytes += scan_align((size_t)b * sizeof(int64_t));
+        l++;
+        if (b == 1) break;
+        m = b;
+    }
+    if (levels) *levels = l;
+    return bytes;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t rt_crossing_offsets_workspace_bytes(int32_t n)
+{
+    return n > 0 ? crossing_offsets_bytes(n, nullptr, nullptr) : 0;
+}
+
+int rt_crossing_offsets(RtScene* s, const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, int64_t* d_offsets,
+                        void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_origins || !d_directions || !d_offsets || !d_workspace))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
+    int64_t blocks[8];
+    int levels = 0;
+    if (workspace_bytes < crossing_offsets_bytes(n, blocks, &levels)) return RT_E_INVALID;
+    {
+        RT_SCENE_CALL(s);
+        const hipStream_t st = (hipStream_t)stream;
+        int32_t* counts = (int32_t*)d_workspace;
+        int64_t* sums[8];
+        char* at = (char*)d_workspace + scan_align((size_t)n * sizeof(int32_t));
+        for (int l = 0; l < levels; l++) { sums[l] = (int64_t*)at; at += scan_align((size_t)blocks[l] * sizeof(int64_t)); }
+        CrossParams p = crossing_params(s);
+        p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n; p.count = counts;
+        launch_crossings<false>(p, st);
+        // level 0: the counts into d_offsets[0..n]; level l > 0: level l - 1's block totals, in place
+        hipLaunchKernelGGL(scan_block_kernel<int32_t>, dim3((unsigned)blocks[0]), dim3(kScanThreads), 0, st, counts, (int64_t)n, d_offsets,
+                           (int64_t)n + 1, sums[0]);
+        for (int l = 1; l < levels; l++)
+            hipLaunchKernelGGL(scan_block_kernel<int64_t>, dim3((unsigned)blocks[l]), dim3(kScanThreads), 0, st, sums[l - 1], blocks[l - 1],
+                               sums[l - 1], blocks[l - 1], sums[l]);
+        for (int l = levels - 1; l >= 1; l--)                   // down again: each block of level l - 1 adds its scanned total
+            hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)blocks[l - 1]), dim3(kScanThreads), 0, st, l >= 2 ? sums[l - 2] : d_offsets,
+                               l >= 2 ? blocks[l - 2] : (int64_t)n + 1, sums[l - 1]);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_list_crossings(RtScene* s, const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, const int64_t* d_offsets,
+                      int32_t max_hits, const RtCrossingList* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_origins || !d_directions || !out))) return RT_E_INVALID;
+    if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
+    if (n > 0 && !(out->t || out->instance || out->triangle || out->sign || out->barycentric || out->uv || out->point || out->count))
+        return RT_E_INVALID;
+    if (n == 0) return RT_OK;
+    {
+        RT_SCENE_CALL(s);
+        CrossListParams p;
+        memset(&p, 0, sizeof p);
+        p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id; p.leaf_count = s->d_leaf_count;
+        p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
+        p.num_instances = (int32_t)s->instances.size();
+        p.stack_depth = s->max_stack;
+        p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n;
+        p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
+        p.t = out->t; p.instance = out->instance; p.triangle = out->triangle; p.sign = out->sign;
+        p.barycentric = out->barycentric; p.uv = out->uv; p.point = out->point; p.count = out->count;
+        const unsigned groups = (unsigned)(((int64_t)n + kCrossBlock - 1) / kCrossBlock);
+        const size_t lds = (size_t)lds_rows(p.stack_depth) * kCrossBlock * sizeof(int);
+        if (p.t && p.instance && p.triangle)                    // the room holds the keys: insertion
+            hipLaunchKernelGGL(crossing_list_kernel<false>, dim3(groups), dim3(kCrossBlock), lds, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL(crossing_list_kernel<true>, dim3(groups), dim3(kCrossBlock), lds, (hipStream_t)stream, p);
         RT_HIP(hipGetLastError());
     }
     RT_WAIT_IF(synchronize, stream);

@@ -508,6 +508,51 @@ int rt_winding_numbers(RtScene *scene, const float *d_points, int32_t n, int32_t
 int rt_signed_distance(RtScene *scene, const float *d_points, const float *d_max_distance, int32_t n, float *d_sdf,
                        int32_t *d_winding, void *stream, int synchronize);
 
+/* ---- crossing lists: every counted (instance, triangle) pair of a ray, sorted.
+ *      8. The pairs of a ray are exactly those rules 1-5 count for rt_count_crossings (same tmax, d_tmax NULL = +inf).  Per pair:
+ *         t = T / det of rule 3 in fp32 (a ray PARAMETER, the value compared with tmax); instance; triangle (the uploaded
+ *         numbering of rt_render_ids / rt_trace_rays / rt_closest_points); sign (+-1, rule 4); barycentric (b1, b2) = the weights of
+ *         v1 and v2 (rt_closest_points' convention), b1 = V / det and b2 = W / det in fp32 from the U, V, W the test used (after the
+ *         fp64 fallback); uv: w = (1 - b2) - b1, then (w*uv0 + b1*uv1) + b2*uv2 per component (rt_closest_points' order and uv
+ *         source); point: o_k + t*d_k per component in fp32, the WORLD point (scaled mesh space is world space rotated and
+ *         translated, so a mesh-space t is a world parameter too).
+ *         ORDER: a ray's pairs sorted by (t, instance, triangle) ascending.  A counted t is never NaN and is > 0, so the order is
+ *         total and the list depends neither on the tree nor on the traversal.  Ties at one t are real (a shared edge, coincident
+ *         triangles, overlapping instances).
+ *         ROOMS: ray i owns the slots [start_i, start_i + room_i) of every output field and gets the first min(count_i, room_i)
+ *         pairs of its sorted list.  The slots after those are padding: t = +inf, instance = triangle = -1, sign = 0, the float
+ *         fields 0.  Nothing is ever written outside a ray's room, for any input (non-finite rays included, whose own contents are
+ *         unspecified).  CSR: d_offsets int64 [n + 1], room_i = offsets[i+1] - offsets[i] (0 or less writes nothing), start_i =
+ *         offsets[i].  Fixed: d_offsets NULL and max_hits = K >= 1, start_i = i*K (size_t), room_i = K (K = 1: the nearest crossing
+ *         of either face, with exact barycentrics).
+ *      rt_crossing_offsets writes offsets[0] = 0 and offsets[i+1] = offsets[i] + count_i (offsets[n] is the total; int64, so totals
+ *      above 2^31 cannot overflow): the count traversal into the workspace, then an exclusive scan on the device.  Its workspace is
+ *      DEVICE memory of at least rt_crossing_offsets_workspace_bytes(n) bytes (0 for n <= 0).  With n == 0 nothing is launched and
+ *      d_offsets is not written.
+ *      rt_list_crossings fills the rooms.  Every field of RtCrossingList is optional, at least one must be given; count[n] is each
+ *      ray's FULL count, equal to rt_count_crossings' even when the room truncated the list (how a caller detects truncation).
+ *      Given t, instance and triangle, one traversal inserts each pair into the sorted room; without one of them the room cannot
+ *      hold the keys, and the kernel makes one traversal per filled slot instead (same result, slower).
+ *      Both calls: inputs as for rt_count_crossings; asynchronous on `stream` unless synchronize != 0; no host synchronisation,
+ *      allocation or copy to the host; no scene scratch (calls may overlap each other and renders); nothing launched when n == 0.
+ *      RT_E_INVALID: the cases of rt_count_crossings; rt_crossing_offsets: d_offsets or d_workspace NULL, or a workspace too small,
+ *      with n > 0; rt_list_crossings: both or neither of d_offsets and max_hits >= 1, no output field with n > 0. ------------- */
+typedef struct RtCrossingList { /* every pointer optional (NULL = not wanted), at least one given; fields indexed by room slot */
+    float *t;                   /* [slots]                                                                              */
+    int32_t *instance;          /* [slots]                                                                              */
+    int32_t *triangle;          /* [slots]                                                                              */
+    int8_t *sign;               /* [slots] +1 / -1, 0 = padding                                                         */
+    float *barycentric;         /* [slots][2] (b1, b2)                                                                  */
+    float *uv;                  /* [slots][2]                                                                           */
+    float *point;               /* [slots][3] world                                                                     */
+    int32_t *count;             /* [n] the full count of each ray                                                       */
+} RtCrossingList;
+size_t rt_crossing_offsets_workspace_bytes(int32_t n);
+int rt_crossing_offsets(RtScene *scene, const float *d_origins, const float *d_directions, const float *d_tmax, int32_t n,
+                        int64_t *d_offsets, void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+int rt_list_crossings(RtScene *scene, const float *d_origins, const float *d_directions, const float *d_tmax, int32_t n,
+                      const int64_t *d_offsets, int32_t max_hits, const RtCrossingList *out, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
