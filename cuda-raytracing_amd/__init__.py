@@ -69,6 +69,10 @@ class RtCrossingList(C.Structure):          # include/rt_hip.h (device pointers,
     _fields_ = [(n, _vp) for n in ("t", "instance", "triangle", "sign", "barycentric", "uv", "point", "count")]
 
 
+class RtNearbyList(C.Structure):            # include/rt_hip.h (device pointers; distance, instance, triangle required)
+    _fields_ = [(n, _vp) for n in ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "count", "pops")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -84,7 +88,7 @@ RT_HIP_SYMBOLS = [
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
     "rt_closest_points", "rt_count_crossings", "rt_winding_numbers", "rt_signed_distance", "rt_crossing_offsets_workspace_bytes",
-    "rt_crossing_offsets", "rt_list_crossings"]
+    "rt_crossing_offsets", "rt_list_crossings", "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -222,6 +226,10 @@ def _declare(h, s):
     h.rt_crossing_offsets_workspace_bytes.argtypes = [C.c_int32]
     h.rt_crossing_offsets.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_crossings.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtCrossingList), _vp, C.c_int]
+    h.rt_nearby_offsets_workspace_bytes.restype = C.c_size_t
+    h.rt_nearby_offsets_workspace_bytes.argtypes = [C.c_int32]
+    h.rt_nearby_offsets.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_list_nearby.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtNearbyList), _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
     h.rt_timer_start.argtypes = [_vp, _vp]
@@ -596,7 +604,39 @@ class Scene:
         if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not
                                      1 <= int(max_hits) <= 2 ** 31 - 1):
             raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
-        return _list_query(self, origins, directions, tmax, None if max_hits is None else int(max_hits), tuple(outputs), stream)
+        return _list_query(self, _CROSSING_LIST, [("origins", origins), ("directions", directions), ("tmax", tmax)],
+                           None if max_hits is None else int(max_hits), tuple(outputs), ("count",), stream)
+
+    NEARBY_LIST_OUTPUTS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv")     # the slot fields of RtNearbyList
+
+    def list_nearby(self, points, max_distance=None, max_hits=None, outputs=("distance", "instance", "triangle"), stream=None):
+        """Every triangle within max_distance of each of the caller's points, sorted by (d2, instance, triangle) -- slot 0 is
+        closest_points' winner (rt_nearby_offsets / rt_list_nearby, include/rt_hip.h rule 9).  Fields as closest_points gives them
+        for each triangle: distance (float32), instance / triangle (int32), point / normal ([3] float32, world), barycentric / uv
+        ([2] float32).  points / max_distance as in closest_points (inclusive; NaN or negative = no triangle).
+        max_hits=None (CSR): dict of `offsets` (int64 [n + 1], point j's triangles at offsets[j]:offsets[j+1]), the wanted fields
+        over all pairs ([total], [total, 2|3]), `point_index` (int32 [total], the flat index of each pair's point) and `count`
+        (int32 of the points' leading shape, from the offsets); "pops" in outputs adds the interior nodes visited by the fill.  On
+        torch this makes exactly ONE host synchronisation (reading offsets[n] to size the outputs).
+        max_hits=K >= 1: the K nearest within the bound, fields [..., K] / [..., K, 2|3] padded with distance = FLT_MAX, instance =
+        triangle = -1 and float 0; `count` (the full number, so count > K means truncated) and `pops` only when in outputs --
+        without count the traversal prunes by the K-th distance (k-nearest), with the same rooms.  On torch fully asynchronous on
+        `stream`.  max_distance and max_hits must not both be None (every triangle for every point).
+        numpy arrays: copied to the device and back, the call synchronises."""
+        slots = tuple(o for o in outputs if o not in ("count", "pops"))
+        bad = [o for o in slots if o not in self.NEARBY_LIST_OUTPUTS]
+        if bad or not slots or len(set(outputs)) != len(tuple(outputs)):
+            raise ValueError("outputs must be a non-empty subset of %s, optionally with count and pops, got %r"
+                             % (self.NEARBY_LIST_OUTPUTS, tuple(outputs)))
+        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not
+                                     1 <= int(max_hits) <= 2 ** 31 - 1):
+            raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
+        if max_distance is None and max_hits is None:
+            raise ValueError("max_distance and max_hits are both None: that lists every triangle for every point")
+        csr = max_hits is None
+        per_point = tuple(k for k in ("count", "pops") if k in outputs and not (csr and k == "count"))
+        return _list_query(self, _NEARBY_LIST, [("points", points), ("max_distance", max_distance)],
+                           None if csr else int(max_hits), slots, per_point, stream)
 
     def info(self):
         b = C.c_size_t(0)
@@ -1020,16 +1060,29 @@ def _query_inputs(inputs):
 
 _LIST_FIELDS = dict(t=((), np.float32), instance=((), np.int32), triangle=((), np.int32), sign=((), np.int8),
                     barycentric=((2,), np.float32), uv=((2,), np.float32), point=((3,), np.float32))
+_NEARBY_FIELDS = dict(distance=((), np.float32), instance=((), np.int32), triangle=((), np.int32), point=((3,), np.float32),
+                      normal=((3,), np.float32), barycentric=((2,), np.float32), uv=((2,), np.float32))
 
 
-def _list_query(scene, origins, directions, tmax, max_hits, outputs, stream):
-    """Scene.list_crossings: every argument is checked before any device call (_query_inputs).  t, instance and triangle are always
-    filled (the room keeps the keys, so the kernel inserts rather than selects); the ones not wanted are dropped."""
-    inputs = [("origins", origins), ("directions", directions), ("tmax", tmax)]
+class _ListKind:
+    """What _list_query needs of one list query: the slot fields in struct order and their (trailing shape, dtype), the key fields
+    (always filled: the room keeps them), the struct (slot fields, then the per-point fields `tail`), the three C-ABI calls and the
+    name of the per-slot query index of the CSR form"""
+
+    def __init__(self, names, fields, keys, struct, tail, ws, offsets, fill, index):
+        self.names, self.fields, self.keys, self.struct, self.tail = names, fields, keys, struct, tail
+        self.ws, self.offsets, self.fill, self.index = ws, offsets, fill, index
+
+
+def _list_query(scene, kind, inputs, max_hits, outputs, per_point, stream):
+    """Scene.list_crossings / Scene.list_nearby: every argument is checked before any device call (_query_inputs).  inputs: (name,
+    array) pairs in the C-ABI's order.  The key fields are always filled (the room keeps the keys, so the kernel inserts rather than
+    selects); the ones not wanted are dropped.  per_point: the fields of kind.tail the kernel fills ([...] int32 each, returned);
+    in CSR form `count` is taken from the offsets when the kernel does not fill it."""
     torch_in, lead, n, dev = _query_inputs(inputs)
     h = libs()[0]
     handle = scene.device_handle
-    fields = tuple(k for k in Scene.CROSSING_LIST_OUTPUTS if k in outputs or k in ("t", "instance", "triangle"))
+    fields = tuple(k for k in kind.names if k in outputs or k in kind.keys)
     csr = max_hits is None
     if torch_in:
         import torch
@@ -1037,29 +1090,31 @@ def _list_query(scene, origins, directions, tmax, max_hits, outputs, stream):
         ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
         st = ts.cuda_stream
         ins = [None if a is None else a.data_ptr() for _k, a in inputs]
-        count = torch.empty(lead, dtype=torch.int32, device=dev)
+        pp = {k: torch.empty(lead, dtype=torch.int32, device=dev) for k in per_point}
         offsets = None
         if csr:
             with torch.cuda.stream(ts):
                 offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-                ws = torch.empty(max(int(h.rt_crossing_offsets_workspace_bytes(n)), 1), dtype=torch.uint8, device=dev)
-                check(h.rt_crossing_offsets(handle, ins[0], ins[1], ins[2], n, offsets.data_ptr(), ws.data_ptr(), ws.numel(), st, 0),
-                      "rt_crossing_offsets")
+                ws = torch.empty(max(int(getattr(h, kind.ws)(n)), 1), dtype=torch.uint8, device=dev)
+                check(getattr(h, kind.offsets)(handle, *ins, n, offsets.data_ptr(), ws.data_ptr(), ws.numel(), st, 0), kind.offsets)
                 total = int(offsets[n].item())                  # the one host synchronisation: the size of the outputs
             rows = (total,)
         else:
             rows = lead + (max_hits,)
         with torch.cuda.stream(ts):
-            out = {k: torch.empty(rows + _LIST_FIELDS[k][0], dtype=tdt[_LIST_FIELDS[k][1]], device=dev) for k in fields}
-            lst = RtCrossingList(*[out[k].data_ptr() if k in out else None for k in Scene.CROSSING_LIST_OUTPUTS], count.data_ptr())
-            check(h.rt_list_crossings(handle, ins[0], ins[1], ins[2], n, None if offsets is None else offsets.data_ptr(),
-                                      0 if csr else max_hits, C.byref(lst), st, 0), "rt_list_crossings")
-            res = {k: out[k] for k in Scene.CROSSING_LIST_OUTPUTS if k in outputs}
+            out = {k: torch.empty(rows + kind.fields[k][0], dtype=tdt[kind.fields[k][1]], device=dev) for k in fields}
+            lst = kind.struct(*[out[k].data_ptr() if k in out else None for k in kind.names],
+                              *[pp[k].data_ptr() if k in pp else None for k in kind.tail])
+            check(getattr(h, kind.fill)(handle, *ins, n, None if offsets is None else offsets.data_ptr(), 0 if csr else max_hits,
+                                        C.byref(lst), st, 0), kind.fill)
+            res = {k: out[k] for k in kind.names if k in outputs}
             if csr:
                 res["offsets"] = offsets
-                res["ray"] = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev), offsets[1:] - offsets[:-1],
-                                                     output_size=total)
-        res["count"] = count
+                res[kind.index] = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev), offsets[1:] - offsets[:-1],
+                                                          output_size=total)
+                if "count" not in pp:
+                    pp["count"] = (offsets[1:] - offsets[:-1]).to(torch.int32).reshape(lead)
+        res.update(pp)
         return res
     keep, ins = [], []
     try:
@@ -1081,31 +1136,38 @@ def _list_query(scene, origins, directions, tmax, max_hits, outputs, stream):
         if csr:
             ob = buf((n + 1) * 8)
             if n > 0:
-                wsb = int(h.rt_crossing_offsets_workspace_bytes(n))
+                wsb = int(getattr(h, kind.ws)(n))
                 ws = buf(wsb)
-                check(h.rt_crossing_offsets(handle, ins[0], ins[1], ins[2], n, ob.ptr, ws.ptr, wsb, stream, 1), "rt_crossing_offsets")
+                check(getattr(h, kind.offsets)(handle, *ins, n, ob.ptr, ws.ptr, wsb, stream, 1), kind.offsets)
                 offsets = ob.to_host(np.int64)[:n + 1]
             else:
                 offsets = np.zeros(1, np.int64)
             rows = (int(offsets[n]),)
         else:
             rows = lead + (max_hits,)
-        shapes = {k: (rows + _LIST_FIELDS[k][0], _LIST_FIELDS[k][1]) for k in fields}
+        shapes = {k: (rows + kind.fields[k][0], kind.fields[k][1]) for k in fields}
         bufs = {k: buf(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize) for k in fields}
-        cb = buf(n * 4)
-        lst = RtCrossingList(*[bufs[k].ptr if k in bufs else None for k in Scene.CROSSING_LIST_OUTPUTS], cb.ptr)
-        check(h.rt_list_crossings(handle, ins[0], ins[1], ins[2], n, ob.ptr if csr else None, 0 if csr else max_hits, C.byref(lst),
-                                  stream, 1), "rt_list_crossings")
+        pb = {k: buf(n * 4) for k in per_point}
+        lst = kind.struct(*[bufs[k].ptr if k in bufs else None for k in kind.names], *[pb[k].ptr if k in pb else None for k in kind.tail])
+        check(getattr(h, kind.fill)(handle, *ins, n, ob.ptr if csr else None, 0 if csr else max_hits, C.byref(lst), stream, 1), kind.fill)
         res = {k: bufs[k].to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0])
-               for k in Scene.CROSSING_LIST_OUTPUTS if k in outputs}
-        res["count"] = cb.to_host(np.int32)[:n].reshape(lead)
+               for k in kind.names if k in outputs}
+        res.update({k: pb[k].to_host(np.int32)[:n].reshape(lead) for k in per_point})
         if csr:
             res["offsets"] = offsets
-            res["ray"] = np.repeat(np.arange(n, dtype=np.int32), np.diff(offsets))
+            res[kind.index] = np.repeat(np.arange(n, dtype=np.int32), np.diff(offsets))
+            if "count" not in res:
+                res["count"] = np.diff(offsets).astype(np.int32).reshape(lead)
         return res
     finally:
         for b in keep:
             b.free()
+
+
+_CROSSING_LIST = _ListKind(Scene.CROSSING_LIST_OUTPUTS, _LIST_FIELDS, ("t", "instance", "triangle"), RtCrossingList, ("count",),
+                           "rt_crossing_offsets_workspace_bytes", "rt_crossing_offsets", "rt_list_crossings", "ray")
+_NEARBY_LIST = _ListKind(Scene.NEARBY_LIST_OUTPUTS, _NEARBY_FIELDS, ("distance", "instance", "triangle"), RtNearbyList, ("count", "pops"),
+                         "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby", "point_index")
 
 
 def _device_query(scene, inputs, outs, call, stream):

@@ -18,6 +18,7 @@ struct RtRayHits;
 struct RtPointHits;
 struct RtCrossings;
 struct RtCrossingList;
+struct RtNearbyList;
 
 class Scene {
 public:
@@ -73,6 +74,12 @@ public:
                          void* d_workspace, size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
     int list_crossings(const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, const int64_t* d_offsets,
                        int32_t max_hits, const RtCrossingList& out, void* stream = nullptr, bool synchronize = false);
+    // Nearby-triangle lists on the device scene: rt_nearby_offsets / rt_list_nearby of include/rt_hip.h (rule 9, rooms), where the
+    // semantics are.  Inputs, offsets, workspace and outputs are DEVICE arrays.  Return the status.
+    int nearby_offsets(const float* d_points, const float* d_max_distance, int32_t n, int64_t* d_offsets, void* d_workspace,
+                       size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
+    int list_nearby(const float* d_points, const float* d_max_distance, int32_t n, const int64_t* d_offsets, int32_t max_hits,
+                    const RtNearbyList& out, void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

@@ -656,6 +656,23 @@ int Scene::list_crossings(const float* d_origins, const float* d_directions, con
     return last_error;
 }
 
+int Scene::nearby_offsets(const float* d_points, const float* d_max_distance, int32_t n, int64_t* d_offsets, void* d_workspace,
+                          size_t workspace_bytes, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_nearby_offsets(d_scene, d_points, d_max_distance, n, d_offsets, d_workspace, workspace_bytes, stream,
+                                             synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::list_nearby(const float* d_points, const float* d_max_distance, int32_t n, const int64_t* d_offsets, int32_t max_hits,
+                       const RtNearbyList& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_list_nearby(d_scene, d_points, d_max_distance, n, d_offsets, max_hits, &out, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

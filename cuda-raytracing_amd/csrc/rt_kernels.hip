@@ -2639,8 +2639,9 @@ __device__ __forceinline__ float pq_cut2(float maxd)
     return __uint_as_float(lo);
 }
 
-// world normal of triangle `slot` of instance `in`, as hit_normal gives it (raycast.cu:115-122)
-__device__ __forceinline__ V3 pq_normal(const PointParams& p, const DevInstance& in, int32_t slot)
+// world normal of triangle `slot` of instance `in`, as hit_normal gives it (raycast.cu:115-122); P: PointParams or NearbyParams
+template <typename P>
+__device__ __forceinline__ V3 pq_normal(const P& p, const DevInstance& in, int32_t slot)
 {
     const float4* t = p.records + (size_t)slot * 4;
     const float4 t0 = t[0], t1 = t[1];
@@ -3046,8 +3047,10 @@ __device__ __forceinline__ void xl_trace(const CrossListParams& p, CrossStack& s
     }
 }
 
-// ray i's room: start and size (CSR: offsets[i] and offsets[i+1] - offsets[i], 0 when not positive; fixed: i*K and K)
-__device__ __forceinline__ void xl_room(const CrossListParams& p, int32_t i, size_t& start, uint64_t& room)
+// ray i's room: start and size (CSR: offsets[i] and offsets[i+1] - offsets[i], 0 when not positive; fixed: i*K and K); P:
+// CrossListParams or NearbyParams
+template <typename P>
+__device__ __forceinline__ void xl_room(const P& p, int32_t i, size_t& start, uint64_t& room)
 {
     if (p.offsets) {
         const int64_t s0 = p.offsets[i], s1 = p.offsets[i + 1];
@@ -3234,6 +3237,216 @@ __global__ __launch_bounds__(kScanThreads) void scan_add_kernel(int64_t* out, in
 #pragma unroll
     for (int k = 0; k < kScanItems; k++)
         if (base + k < m) out[base + k] += add;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Nearby-triangle lists (rt_nearby_offsets / rt_list_nearby): every (instance, triangle) whose d2 (rules 1-3 of rt_closest_points) is
+// a candidate under rule 4, in the order (d2, instance, triangle) of rule 5, written into the point's own room (include/rt_hip.h
+// rule 9).  The traversal is closest_point_kernel's: the same q, pq_box_lb and pruning argument.
+// ---------------------------------------------------------------------------------------------------------
+struct NearbyParams {
+    const float4* records;
+    const float* tri_uv;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* pts;           // [n][3] world points
+    const float* max_distance;  // [n] or null (= +inf)
+    int32_t n;
+    const int64_t* offsets;     // [n + 1] (CSR rooms) or null: fixed rooms of max_hits
+    int32_t max_hits;
+    float* distance;            // the keys, required by the list kernel (d2 while it runs, sqrtf(d2) at its end); indexed by room slot
+    int32_t *instance, *triangle;
+    float *point, *normal, *barycentric, *uv;   // optional, indexed by room slot
+    int32_t *count, *pops;      // optional, [n] (the count kernel: count = the workspace)
+};
+
+// closest_point_kernel's nearest-first traversal of every instance for point i, calling leaf(k, slot, d2, b1, b2) at each triangle with
+// d2 <= lim() (NaN fails).  lim() is read at every box and triangle: the list kernel lowers it while the traversal runs.  The point is
+// read again at each instance, so it is not held in registers across the traversal.  Returns the interior nodes visited.
+template <typename Lim, typename Leaf>
+__device__ __forceinline__ int32_t nb_trace(const NearbyParams& p, PointStack& stack, size_t i3, Lim&& lim, Leaf&& leaf)
+{
+    int32_t pops = 0;
+    for (int32_t k = 0; k < p.num_instances; k++) {
+        const DevInstance& in = p.instances[k];
+        const V3 q = apply_quat(in.q_pose, v3(p.pts[i3] - in.pose_xyz[0], p.pts[i3 + 1] - in.pose_xyz[1], p.pts[i3 + 2] - in.pose_xyz[2]));
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: both child boxes, nearer first
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const float la = pq_box_lb(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, q);
+                const float lb = pq_box_lb(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, q);
+                const float l = lim();
+                const bool pa = !(prune && la > l), pb = !(prune && lb > l);      // (equality is kept: a tie may still enter)
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                const bool a_near = !(lb < la);
+                if (pa && pb) stack.push(a_near ? rb : ra);
+                cur = (pa && pb) ? (a_near ? ra : rb) : (pa ? ra : (pb ? rb : kNeedPop));
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    V3 a, ab, ac;
+                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
+                    const float2 bw = pq_weights(q, a, ab, ac);
+                    const float d2 = pq_d2(q - pq_combine(a, ab, ac, bw.x, bw.y));
+                    if (d2 <= lim()) leaf(k, slot, d2, bw.x, bw.y);
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel);
+    }
+    return pops;
+}
+
+// rt_nearby_offsets' first step: the number of pairs of each point into count (the workspace), with the fixed limit cut2
+__global__ __launch_bounds__(kPointBlock, 8) void nearby_count_kernel(const NearbyParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kPointBlock]
+    const int32_t i = (int32_t)blockIdx.x * kPointBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
+    int spill[kMaxStack - kLdsStack];
+    PointStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    int32_t total = 0;
+    if (cut2 >= 0.0f)
+        nb_trace(p, stack, (size_t)i * 3, [&] { return cut2; }, [&](int32_t, int32_t, float, float, float) { total++; });
+    p.count[i] = total;
+}
+
+// slot j (absolute) of a room <- the pair (instance k, record slot, triangle tid) at d2 with weights (b1, b2); each optional field exactly
+// as closest_point_kernel writes its winner's
+__device__ __forceinline__ void nb_store(const NearbyParams& p, size_t j, int32_t k, int32_t slot, int32_t tid, float d2, float b1, float b2)
+{
+    p.distance[j] = d2;
+    p.instance[j] = k;
+    p.triangle[j] = tid;
+    if (p.barycentric) { p.barycentric[2 * j] = b1; p.barycentric[2 * j + 1] = b2; }
+    if (!(p.point || p.normal || p.uv)) return;
+    const DevInstance& in = p.instances[k];
+    if (p.point) {                                              // c again (same sequence), to world: apply_lre(inv_pose, c)
+        const float4* rec = p.records + (size_t)slot * 4;
+        V3 a, ab, ac;
+        pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+        const V3 c = pq_combine(a, ab, ac, b1, b2);
+        const V3 o = apply_quat(in.q_inv_pose, v3(c.x - in.inv_pose_xyz[0], c.y - in.inv_pose_xyz[1], c.z - in.inv_pose_xyz[2]));
+        p.point[3 * j] = o.x; p.point[3 * j + 1] = o.y; p.point[3 * j + 2] = o.z;
+    }
+    if (p.normal) {
+        const V3 nn = pq_normal(p, in, slot);
+        p.normal[3 * j] = nn.x; p.normal[3 * j + 1] = nn.y; p.normal[3 * j + 2] = nn.z;
+    }
+    if (p.uv) {                                                 // w = (1 - b2) - b1, uv = (w uv0 + b1 uv1) + b2 uv2
+        const float* t = p.tri_uv + (size_t)slot * 6;
+        const float u0 = (1.0f - b2) - b1;
+        p.uv[2 * j] = (u0 * t[0] + b1 * t[2]) + b2 * t[4];
+        p.uv[2 * j + 1] = (u0 * t[1] + b1 * t[3]) + b2 * t[5];
+    }
+}
+
+// One traversal; each pair is inserted into the point's room, which stays sorted by (d2, instance, triangle) -- lane-private, no
+// atomics; once the room is full a pair enters only below the last key.  In fixed rooms without count the pruning limit then drops
+// from cut2 to the last key's d2 (k-nearest): a box whose lower bound is above it holds only pairs that sort after the last key.
+// Equal bounds are not pruned (a tie may still win on (instance, triangle)).  With count, or in CSR rooms, the limit stays cut2 and
+// count is the full number of pairs.  distance holds d2 until the end, then sqrtf(d2) over the filled slots; the rest is padding.
+__global__ __launch_bounds__(kPointBlock, 8) void nearby_list_kernel(const NearbyParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kPointBlock]
+    const int32_t i = (int32_t)blockIdx.x * kPointBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
+    int spill[kMaxStack - kLdsStack];
+    PointStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const bool knn = !p.offsets && !p.count;
+    float lim = cut2;
+    int32_t total = 0, filled = 0, pops = 0;                    // (filled <= total: int32)
+    if (cut2 >= 0.0f)
+        pops = nb_trace(p, stack, (size_t)i * 3, [&] { return lim; }, [&](int32_t k, int32_t slot, float d2, float b1, float b2) {
+            total++;
+            size_t start;
+            uint64_t room;
+            xl_room(p, i, start, room);                         // (read again per pair: not held across the traversal)
+            if (room == 0) return;
+            int32_t tid;
+            uint64_t pos;
+            if ((uint64_t)filled < room) {
+                pos = (uint64_t)filled++;
+                tid = p.tri_id[slot];
+            } else {                                            // full: enter only below the last key
+                const size_t last = start + (size_t)(room - 1);
+                const float ld = p.distance[last];
+                if (d2 > ld) return;
+                if (d2 == ld) {
+                    if (k > p.instance[last]) return;           // (instances arrive in ascending order: k >= the last's)
+                    tid = p.tri_id[slot];
+                    if (tid > p.triangle[last]) return;
+                } else {
+                    tid = p.tri_id[slot];
+                }
+                pos = room - 1;
+            }
+            while (pos > 0) {                                   // shift the greater keys up by one slot
+                const size_t q = start + (size_t)(pos - 1);
+                const float qd = p.distance[q];
+                if (qd < d2) break;
+                if (qd == d2) {
+                    const int32_t qi = p.instance[q];
+                    if (qi < k || (qi == k && p.triangle[q] < tid)) break;
+                }
+                p.distance[q + 1] = qd;
+                p.instance[q + 1] = p.instance[q];
+                p.triangle[q + 1] = p.triangle[q];
+                if (p.barycentric) { p.barycentric[2 * q + 2] = p.barycentric[2 * q]; p.barycentric[2 * q + 3] = p.barycentric[2 * q + 1]; }
+                if (p.uv) { p.uv[2 * q + 2] = p.uv[2 * q]; p.uv[2 * q + 3] = p.uv[2 * q + 1]; }
+                if (p.point) {
+                    p.point[3 * q + 3] = p.point[3 * q]; p.point[3 * q + 4] = p.point[3 * q + 1]; p.point[3 * q + 5] = p.point[3 * q + 2];
+                }
+                if (p.normal) {
+                    p.normal[3 * q + 3] = p.normal[3 * q]; p.normal[3 * q + 4] = p.normal[3 * q + 1]; p.normal[3 * q + 5] = p.normal[3 * q + 2];
+                }
+                pos--;
+            }
+            nb_store(p, start + (size_t)pos, k, slot, tid, d2, b1, b2);
+            if (knn && (uint64_t)filled >= room) lim = p.distance[start + (size_t)(room - 1)];     // (<= cut2: only candidates enter)
+        });
+    size_t start;
+    uint64_t room;
+    xl_room(p, i, start, room);
+    for (uint64_t j = 0; j < room; j++) {
+        const size_t q = start + (size_t)j;
+        if (j < (uint64_t)filled) {
+            p.distance[q] = sqrtf(p.distance[q]);
+            continue;
+        }
+        p.distance[q] = FLT_MAX;                                // padding: a closest-point miss
+        p.instance[q] = -1;
+        p.triangle[q] = -1;
+        if (p.barycentric) { p.barycentric[2 * q] = 0.0f; p.barycentric[2 * q + 1] = 0.0f; }
+        if (p.uv) { p.uv[2 * q] = 0.0f; p.uv[2 * q + 1] = 0.0f; }
+        if (p.point) { p.point[3 * q] = 0.0f; p.point[3 * q + 1] = 0.0f; p.point[3 * q + 2] = 0.0f; }
+        if (p.normal) { p.normal[3 * q] = 0.0f; p.normal[3 * q + 1] = 0.0f; p.normal[3 * q + 2] = 0.0f; }
+    }
+    if (p.count) p.count[i] = total;
+    if (p.pops) p.pops[i] = pops;
 }
 
 }  // namespace
@@ -4881,6 +5094,24 @@ size_t crossing_offsets_bytes(int64_t n, int64_t* level_blocks, int* levels)
     if (levels) *levels = l;
     return bytes;
 }
+// the exclusive int64 scan of the counts at the workspace's start (int32 [n]) into d_offsets[0..n], the block totals of each level in
+// the rest of the workspace (crossing_offsets_bytes' layout): level 0 scans the counts, level l > 0 level l - 1's block totals in
+// place, then each block of level l - 1 adds its scanned total on the way down
+void scan_offsets(void* d_workspace, int32_t n, int64_t* d_offsets, const int64_t* blocks, int levels, hipStream_t st)
+{
+    const int32_t* counts = (const int32_t*)d_workspace;
+    int64_t* sums[8];
+    char* at = (char*)d_workspace + scan_align((size_t)n * sizeof(int32_t));
+    for (int l = 0; l < levels; l++) { sums[l] = (int64_t*)at; at += scan_align((size_t)blocks[l] * sizeof(int64_t)); }
+    hipLaunchKernelGGL(scan_block_kernel<int32_t>, dim3((unsigned)blocks[0]), dim3(kScanThreads), 0, st, counts, (int64_t)n, d_offsets,
+                       (int64_t)n + 1, sums[0]);
+    for (int l = 1; l < levels; l++)
+        hipLaunchKernelGGL(scan_block_kernel<int64_t>, dim3((unsigned)blocks[l]), dim3(kScanThreads), 0, st, sums[l - 1], blocks[l - 1],
+                           sums[l - 1], blocks[l - 1], sums[l]);
+    for (int l = levels - 1; l >= 1; l--)
+        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)blocks[l - 1]), dim3(kScanThreads), 0, st, l >= 2 ? sums[l - 2] : d_offsets,
+                           l >= 2 ? blocks[l - 2] : (int64_t)n + 1, sums[l - 1]);
+}
 }  // namespace
 }  // extern "C++"
 
@@ -4900,22 +5131,10 @@ int rt_crossing_offsets(RtScene* s, const float* d_origins, const float* d_direc
     {
         RT_SCENE_CALL(s);
         const hipStream_t st = (hipStream_t)stream;
-        int32_t* counts = (int32_t*)d_workspace;
-        int64_t* sums[8];
-        char* at = (char*)d_workspace + scan_align((size_t)n * sizeof(int32_t));
-        for (int l = 0; l < levels; l++) { sums[l] = (int64_t*)at; at += scan_align((size_t)blocks[l] * sizeof(int64_t)); }
         CrossParams p = crossing_params(s);
-        p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n; p.count = counts;
+        p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n; p.count = (int32_t*)d_workspace;
         launch_crossings<false>(p, st);
-        // level 0: the counts into d_offsets[0..n]; level l > 0: level l - 1's block totals, in place
-        hipLaunchKernelGGL(scan_block_kernel<int32_t>, dim3((unsigned)blocks[0]), dim3(kScanThreads), 0, st, counts, (int64_t)n, d_offsets,
-                           (int64_t)n + 1, sums[0]);
-        for (int l = 1; l < levels; l++)
-            hipLaunchKernelGGL(scan_block_kernel<int64_t>, dim3((unsigned)blocks[l]), dim3(kScanThreads), 0, st, sums[l - 1], blocks[l - 1],
-                               sums[l - 1], blocks[l - 1], sums[l]);
-        for (int l = levels - 1; l >= 1; l--)                   // down again: each block of level l - 1 adds its scanned total
-            hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)blocks[l - 1]), dim3(kScanThreads), 0, st, l >= 2 ? sums[l - 2] : d_offsets,
-                               l >= 2 ? blocks[l - 2] : (int64_t)n + 1, sums[l - 1]);
+        scan_offsets(d_workspace, n, d_offsets, blocks, levels, st);
         RT_HIP(hipGetLastError());
     }
     RT_WAIT_IF(synchronize, stream);
@@ -4948,6 +5167,73 @@ int rt_list_crossings(RtScene* s, const float* d_origins, const float* d_directi
             hipLaunchKernelGGL(crossing_list_kernel<false>, dim3(groups), dim3(kCrossBlock), lds, (hipStream_t)stream, p);
         else
             hipLaunchKernelGGL(crossing_list_kernel<true>, dim3(groups), dim3(kCrossBlock), lds, (hipStream_t)stream, p);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+extern "C++" {
+namespace {
+NearbyParams nearby_params(const RtScene* s, const float* d_points, const float* d_max_distance, int32_t n)
+{
+    NearbyParams p;
+    memset(&p, 0, sizeof p);
+    p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id; p.leaf_count = s->d_leaf_count;
+    p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
+    p.num_instances = (int32_t)s->instances.size();
+    p.stack_depth = s->max_stack;
+    p.pts = d_points; p.max_distance = d_max_distance; p.n = n;
+    return p;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t rt_nearby_offsets_workspace_bytes(int32_t n)
+{
+    return n > 0 ? crossing_offsets_bytes(n, nullptr, nullptr) : 0;
+}
+
+int rt_nearby_offsets(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, int64_t* d_offsets, void* d_workspace,
+                      size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_points || !d_offsets || !d_workspace))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
+    int64_t blocks[8];
+    int levels = 0;
+    if (workspace_bytes < crossing_offsets_bytes(n, blocks, &levels)) return RT_E_INVALID;
+    {
+        RT_SCENE_CALL(s);
+        const hipStream_t st = (hipStream_t)stream;
+        NearbyParams p = nearby_params(s, d_points, d_max_distance, n);
+        p.count = (int32_t*)d_workspace;
+        const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
+        const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
+        hipLaunchKernelGGL(nearby_count_kernel, dim3(groups), dim3(kPointBlock), lds, st, p);
+        scan_offsets(d_workspace, n, d_offsets, blocks, levels, st);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_list_nearby(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, const int64_t* d_offsets, int32_t max_hits,
+                   const RtNearbyList* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_points || !out))) return RT_E_INVALID;
+    if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
+    if (n > 0 && !(out->distance && out->instance && out->triangle)) return RT_E_INVALID;     // the room holds the keys
+    if (n == 0) return RT_OK;
+    {
+        RT_SCENE_CALL(s);
+        NearbyParams p = nearby_params(s, d_points, d_max_distance, n);
+        p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
+        p.distance = out->distance; p.instance = out->instance; p.triangle = out->triangle;
+        p.point = out->point; p.normal = out->normal; p.barycentric = out->barycentric; p.uv = out->uv;
+        p.count = out->count; p.pops = out->pops;
+        const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
+        const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
+        hipLaunchKernelGGL(nearby_list_kernel, dim3(groups), dim3(kPointBlock), lds, (hipStream_t)stream, p);
         RT_HIP(hipGetLastError());
     }
     RT_WAIT_IF(synchronize, stream);

@@ -553,6 +553,49 @@ int rt_crossing_offsets(RtScene *scene, const float *d_origins, const float *d_d
 int rt_list_crossings(RtScene *scene, const float *d_origins, const float *d_directions, const float *d_tmax, int32_t n,
                       const int64_t *d_offsets, int32_t max_hits, const RtCrossingList *out, void *stream, int synchronize);
 
+/* ---- nearby-triangle lists: every (instance, triangle) within a radius of a point, sorted; k nearest.
+ *      9. The pairs of point j are every (instance, triangle) whose d2, computed by rules 1-3 of rt_closest_points exactly, is a
+ *         candidate under rule 4 with bound max_distance[j] (d_max_distance NULL = +inf; inclusive; a NaN or negative bound gives
+ *         no pairs; a NaN d2 is never a pair; an overflowed d2 = +inf is a pair under an infinite bound only).
+ *         ORDER: a point's pairs sorted by (d2, instance, triangle) ascending, rule 5's key, so slot 0 is rt_closest_points' winner.
+ *         Per slot: distance = sqrtf(d2); instance; triangle (the uploaded numbering); point, normal, barycentric and uv each
+ *         exactly as rt_closest_points computes them for that triangle.  The list depends neither on the tree (host-built,
+ *         device-built or refitted) nor on the order of traversal.
+ *         ROOMS: those of rule 8.  Point i owns the slots [start_i, start_i + room_i) of every output field and gets the first
+ *         min(count_i, room_i) pairs of its sorted list; the slots after those are padding: distance = FLT_MAX, instance = triangle
+ *         = -1, the other floats 0 (a closest-point miss).  Nothing is ever written outside a point's room, for any input
+ *         (non-finite points and bounds included, whose own contents are unspecified).  CSR: d_offsets int64 [n + 1], room_i =
+ *         offsets[i+1] - offsets[i] (0 or less writes nothing), start_i = offsets[i].  Fixed: d_offsets NULL and max_hits = K >= 1,
+ *         start_i = i*K (size_t), room_i = K (K nearest within the bound; K = 1: rt_closest_points' winner).
+ *      rt_nearby_offsets writes offsets[0] = 0 and offsets[i+1] = offsets[i] + count_i (int64): the count traversal into the
+ *      workspace, then rt_crossing_offsets' exclusive scan on the device.  Its workspace is DEVICE memory of at least
+ *      rt_nearby_offsets_workspace_bytes(n) bytes (0 for n <= 0).  With n == 0 nothing is launched and d_offsets is not written.
+ *      rt_list_nearby fills the rooms.  distance, instance and triangle are REQUIRED (the room is where the keys live); the other
+ *      fields are optional.  count[n] is each point's FULL number of pairs; pops[n] the interior nodes visited (a statistic, not
+ *      part of the bit-exact contract).  In fixed rooms without count, the traversal prunes by the room's last key once the room
+ *      is full (k-nearest); the rooms are the same bits with and without count.
+ *      Both calls: inputs as for rt_closest_points; asynchronous on `stream` unless synchronize != 0; no host synchronisation,
+ *      allocation or copy to the host; no scene scratch; nothing launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL points with n > 0; rt_nearby_offsets: d_offsets or d_workspace NULL, or a workspace too
+ *      small, with n > 0; rt_list_nearby: NULL out, or distance, instance or triangle NULL, with n > 0; both or neither of
+ *      d_offsets and max_hits >= 1. ----------------------------------------------------------------------------------------- */
+typedef struct RtNearbyList {   /* fields indexed by room slot; distance, instance and triangle REQUIRED, the rest optional     */
+    float *distance;            /* [slots] sqrtf(d2); FLT_MAX = padding                                                  */
+    int32_t *instance;          /* [slots] -1 = padding                                                                  */
+    int32_t *triangle;          /* [slots] the uploaded numbering; -1 = padding                                          */
+    float *point;               /* [slots][3] world position of the triangle's closest point                             */
+    float *normal;              /* [slots][3] world face normal                                                          */
+    float *barycentric;         /* [slots][2] (b1, b2): the weights of v1 and v2                                         */
+    float *uv;                  /* [slots][2] texture uv                                                                 */
+    int32_t *count;             /* [n] the full number of pairs of each point                                            */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic)                                              */
+} RtNearbyList;
+size_t rt_nearby_offsets_workspace_bytes(int32_t n);
+int rt_nearby_offsets(RtScene *scene, const float *d_points, const float *d_max_distance, int32_t n, int64_t *d_offsets,
+                      void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+int rt_list_nearby(RtScene *scene, const float *d_points, const float *d_max_distance, int32_t n, const int64_t *d_offsets,
+                   int32_t max_hits, const RtNearbyList *out, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
