@@ -73,6 +73,14 @@ class RtNearbyList(C.Structure):            # include/rt_hip.h (device pointers;
     _fields_ = [(n, _vp) for n in ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "count", "pops")]
 
 
+class RtIntersectCounts(C.Structure):       # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in ("count", "any", "pops")]
+
+
+class RtIntersectList(C.Structure):         # include/rt_hip.h (device pointers; instance, triangle required)
+    _fields_ = [(n, _vp) for n in ("instance", "triangle", "normal", "segment", "count", "pops")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -88,7 +96,8 @@ RT_HIP_SYMBOLS = [
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
     "rt_closest_points", "rt_count_crossings", "rt_winding_numbers", "rt_signed_distance", "rt_crossing_offsets_workspace_bytes",
-    "rt_crossing_offsets", "rt_list_crossings", "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby"]
+    "rt_crossing_offsets", "rt_list_crossings", "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby",
+    "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -230,6 +239,11 @@ def _declare(h, s):
     h.rt_nearby_offsets_workspace_bytes.argtypes = [C.c_int32]
     h.rt_nearby_offsets.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_nearby.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtNearbyList), _vp, C.c_int]
+    h.rt_count_intersecting.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtIntersectCounts), _vp, C.c_int]
+    h.rt_intersecting_offsets_workspace_bytes.restype = C.c_size_t
+    h.rt_intersecting_offsets_workspace_bytes.argtypes = [C.c_int32]
+    h.rt_intersecting_offsets.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_list_intersecting.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtIntersectList), _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
     h.rt_timer_start.argtypes = [_vp, _vp]
@@ -638,6 +652,59 @@ class Scene:
         return _list_query(self, _NEARBY_LIST, [("points", points), ("max_distance", max_distance)],
                            None if csr else int(max_hits), slots, per_point, stream)
 
+    INTERSECT_COUNT_OUTPUTS = ("count", "any", "pops")     # the fields of RtIntersectCounts
+
+    def count_intersecting(self, triangles, skip_instance=None, outputs=("count",), stream=None):
+        """How many scene triangles each of the caller's triangles intersects (rt_count_intersecting; the rule, equal to a brute-force
+        loop over every instance and triangle, is rule 10 of include/rt_hip.h): dict of the wanted INTERSECT_COUNT_OUTPUTS of the
+        triangles' leading shape -- count (int32, the number of (instance, triangle) pairs), any (bool; wanted without count, the
+        traversal stops at the first pair: the cheap collision check), pops (int32, interior nodes visited).  triangles: float32
+        [..., 3, 3] world vertices, contiguous.  skip_instance: None or int32 of the leading shape, one instance per triangle whose pairs
+        are never reported (-1 = none).  torch tensors: asynchronous on `stream` (default the current stream); numpy arrays: copied to
+        the device and back, the call synchronises."""
+        bad = [o for o in outputs if o not in self.INTERSECT_COUNT_OUTPUTS]
+        if bad or not outputs:
+            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.INTERSECT_COUNT_OUTPUTS, tuple(outputs)))
+        outputs = tuple(outputs)
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            c = RtIntersectCounts(*[ptr.get(k) for k in Scene.INTERSECT_COUNT_OUTPUTS])
+            check(h.rt_count_intersecting(handle, ins[0], ins[1], n, C.byref(c), st, sync), "rt_count_intersecting")
+        res = _device_query(self, [("triangles", triangles), ("skip_instance", skip_instance)],
+                            {k: ((), np.uint8 if k == "any" else np.int32) for k in outputs}, call, stream, **_TRIANGLE_INPUTS)
+        if "any" in res:
+            a = res["any"]
+            res["any"] = a.view(np.bool_) if isinstance(a, np.ndarray) else a.view(__import__("torch").bool)
+        return res
+
+    INTERSECT_LIST_OUTPUTS = ("instance", "triangle", "normal", "segment")     # the slot fields of RtIntersectList
+
+    def list_intersecting(self, triangles, skip_instance=None, max_hits=None, outputs=("instance", "triangle"), stream=None):
+        """Every scene triangle each of the caller's triangles intersects, sorted by (instance, triangle) (rt_intersecting_offsets /
+        rt_list_intersecting, include/rt_hip.h rule 10).  Fields: instance / triangle (int32), normal ([3] float32, the world face
+        normal as closest_points gives it), segment ([2, 3] float32, world points of the first and the last counting segment test).
+        triangles / skip_instance as in count_intersecting.
+        max_hits=None (CSR): dict of `offsets` (int64 [n + 1], query j's pairs at offsets[j]:offsets[j+1]), the wanted fields over all
+        pairs ([total], [total, 3], [total, 2, 3]), `query_index` (int32 [total], the flat index of each pair's query) and `count`
+        (int32 of the leading shape, from the offsets); "pops" in outputs adds the interior nodes visited by the fill.  On torch this
+        makes exactly ONE host synchronisation (reading offsets[n] to size the outputs).
+        max_hits=K >= 1: the first K pairs of each query, fields [..., K] / [..., K, 3] / [..., K, 2, 3] padded with instance =
+        triangle = -1 and float 0; `count` (the full number, so count > K means truncated) and `pops` only when in outputs -- without
+        count the traversal ends after the instance of a full room's last key, with the same rooms.  On torch fully asynchronous on
+        `stream`.  numpy arrays: copied to the device and back, the call synchronises."""
+        slots = tuple(o for o in outputs if o not in ("count", "pops"))
+        bad = [o for o in slots if o not in self.INTERSECT_LIST_OUTPUTS]
+        if bad or not slots or len(set(outputs)) != len(tuple(outputs)):
+            raise ValueError("outputs must be a non-empty subset of %s, optionally with count and pops, got %r"
+                             % (self.INTERSECT_LIST_OUTPUTS, tuple(outputs)))
+        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not
+                                     1 <= int(max_hits) <= 2 ** 31 - 1):
+            raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
+        csr = max_hits is None
+        per_point = tuple(k for k in ("count", "pops") if k in outputs and not (csr and k == "count"))
+        return _list_query(self, _INTERSECT_LIST, [("triangles", triangles), ("skip_instance", skip_instance)],
+                           None if csr else int(max_hits), slots, per_point, stream)
+
     def info(self):
         b = C.c_size_t(0)
         d = C.c_int32(0)
@@ -1016,10 +1083,10 @@ def _point_query(scene, points, max_distance, outputs, stream):
     return _device_query(scene, [("points", points), ("max_distance", max_distance)], {k: shapes[k] for k in outputs}, call, stream)
 
 
-def _query_inputs(inputs):
+def _query_inputs(inputs, shape=(3,), ints=()):
     """The argument checks of _device_query and _list_query, before any device call -> (torch_in, leading shape, n, device).
-    inputs: (name, array) pairs, the first [..., 3], "directions" of the same shape, the others of the leading shape; None = not
-    given."""
+    inputs: (name, array) pairs, the first [..., *shape] (default [..., 3]), "directions" of the same shape, the others of the
+    leading shape; None = not given.  Every input is float32 except those named in `ints`, which are int32."""
     given = [(k, a) for k, a in inputs if a is not None]
     torch_in = type(given[0][1]).__module__.split(".")[0] == "torch"
     if any((type(a).__module__.split(".")[0] == "torch") != torch_in for _k, a in given):
@@ -1027,15 +1094,17 @@ def _query_inputs(inputs):
     if not torch_in and not all(isinstance(a, np.ndarray) for _k, a in given):
         raise ValueError("%s must be numpy arrays or torch tensors" % ", ".join(k for k, _a in given))
     for name, a in given:
-        if str(a.dtype) not in ("float32", "torch.float32"):
-            raise ValueError("%s must be float32, got %s" % (name, a.dtype))
+        want = "int32" if name in ints else "float32"
+        if str(a.dtype) not in (want, "torch." + want):
+            raise ValueError("%s must be %s, got %s" % (name, want, a.dtype))
         contiguous = a.is_contiguous() if torch_in else a.flags["C_CONTIGUOUS"]
         if not contiguous:
             raise ValueError("%s must be contiguous" % name)
     first, a0 = given[0]
-    if len(a0.shape) < 1 or a0.shape[-1] != 3:
-        raise ValueError("%s must have the shape [..., 3], got %s" % (first, tuple(a0.shape)))
-    lead = tuple(a0.shape[:-1])
+    nd = len(a0.shape) - len(shape)
+    if nd < 0 or tuple(a0.shape[nd:]) != tuple(shape):
+        raise ValueError("%s must have the shape [..., %s], got %s" % (first, ", ".join(str(x) for x in shape), tuple(a0.shape)))
+    lead = tuple(a0.shape[:nd])
     for name, a in inputs[1:]:
         if a is None:
             continue
@@ -1069,9 +1138,10 @@ class _ListKind:
     (always filled: the room keeps them), the struct (slot fields, then the per-point fields `tail`), the three C-ABI calls and the
     name of the per-slot query index of the CSR form"""
 
-    def __init__(self, names, fields, keys, struct, tail, ws, offsets, fill, index):
+    def __init__(self, names, fields, keys, struct, tail, ws, offsets, fill, index, inputs=None):
         self.names, self.fields, self.keys, self.struct, self.tail = names, fields, keys, struct, tail
         self.ws, self.offsets, self.fill, self.index = ws, offsets, fill, index
+        self.inputs = inputs or {}              # _query_inputs' shape / ints when they are not the defaults
 
 
 def _list_query(scene, kind, inputs, max_hits, outputs, per_point, stream):
@@ -1079,7 +1149,7 @@ def _list_query(scene, kind, inputs, max_hits, outputs, per_point, stream):
     array) pairs in the C-ABI's order.  The key fields are always filled (the room keeps the keys, so the kernel inserts rather than
     selects); the ones not wanted are dropped.  per_point: the fields of kind.tail the kernel fills ([...] int32 each, returned);
     in CSR form `count` is taken from the offsets when the kernel does not fill it."""
-    torch_in, lead, n, dev = _query_inputs(inputs)
+    torch_in, lead, n, dev = _query_inputs(inputs, **kind.inputs)
     h = libs()[0]
     handle = scene.device_handle
     fields = tuple(k for k in kind.names if k in outputs or k in kind.keys)
@@ -1168,20 +1238,26 @@ _CROSSING_LIST = _ListKind(Scene.CROSSING_LIST_OUTPUTS, _LIST_FIELDS, ("t", "ins
                            "rt_crossing_offsets_workspace_bytes", "rt_crossing_offsets", "rt_list_crossings", "ray")
 _NEARBY_LIST = _ListKind(Scene.NEARBY_LIST_OUTPUTS, _NEARBY_FIELDS, ("distance", "instance", "triangle"), RtNearbyList, ("count", "pops"),
                          "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby", "point_index")
+_TRIANGLE_INPUTS = dict(shape=(3, 3), ints=("skip_instance",))
+_INTERSECT_FIELDS = dict(instance=((), np.int32), triangle=((), np.int32), normal=((3,), np.float32), segment=((2, 3), np.float32))
+_INTERSECT_LIST = _ListKind(Scene.INTERSECT_LIST_OUTPUTS, _INTERSECT_FIELDS, ("instance", "triangle"), RtIntersectList, ("count", "pops"),
+                            "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting", "query_index",
+                            inputs=_TRIANGLE_INPUTS)
 
 
-def _device_query(scene, inputs, outs, call, stream):
-    """Scene.closest_points / count_crossings / winding_numbers / signed_distance: every argument is checked before any device
-    call.  inputs: (name, array) pairs, the first [..., 3], "directions" of the same shape, the others of the leading shape; None =
-    not given.  outs: name -> (trailing shape, dtype).  call(h, handle, input pointers, output pointers, n, stream, synchronize) makes the C-ABI call."""
-    torch_in, lead, n, dev = _query_inputs(inputs)
+def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=()):
+    """Scene.closest_points / count_crossings / winding_numbers / signed_distance / count_intersecting: every argument is checked
+    before any device call.  inputs: (name, array) pairs, the first [..., 3] (or [..., *shape]), "directions" of the same shape, the
+    others of the leading shape; None = not given; int32 where named in `ints`.  outs: name -> (trailing shape, dtype).  call(h,
+    handle, input pointers, output pointers, n, stream, synchronize) makes the C-ABI call."""
+    torch_in, lead, n, dev = _query_inputs(inputs, shape, ints)
     if torch_in:
         import torch
     h = libs()[0]
     handle = scene.device_handle
     shapes = {k: (lead + tr, dt) for k, (tr, dt) in outs.items()}
     if torch_in:
-        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}
         out = {k: torch.empty(shapes[k][0], dtype=tdt[shapes[k][1]], device=dev) for k in outs}
         ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
         st = ts.cuda_stream

@@ -19,6 +19,8 @@ struct RtPointHits;
 struct RtCrossings;
 struct RtCrossingList;
 struct RtNearbyList;
+struct RtIntersectCounts;
+struct RtIntersectList;
 
 class Scene {
 public:
@@ -80,6 +82,15 @@ public:
                        size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
     int list_nearby(const float* d_points, const float* d_max_distance, int32_t n, const int64_t* d_offsets, int32_t max_hits,
                     const RtNearbyList& out, void* stream = nullptr, bool synchronize = false);
+    // Triangle intersections on the device scene: rt_count_intersecting / rt_intersecting_offsets / rt_list_intersecting of
+    // include/rt_hip.h (rule 10, rooms), where the semantics are.  Triangles ([n][3][3] world), skip_instance (optional), offsets,
+    // workspace and outputs are DEVICE arrays.  Return the status.
+    int count_intersecting(const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const RtIntersectCounts& out,
+                           void* stream = nullptr, bool synchronize = false);
+    int intersecting_offsets(const float* d_triangles, const int32_t* d_skip_instance, int32_t n, int64_t* d_offsets, void* d_workspace,
+                             size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
+    int list_intersecting(const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const int64_t* d_offsets, int32_t max_hits,
+                          const RtIntersectList& out, void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

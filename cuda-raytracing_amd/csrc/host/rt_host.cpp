@@ -673,6 +673,32 @@ int Scene::list_nearby(const float* d_points, const float* d_max_distance, int32
     return last_error;
 }
 
+int Scene::count_intersecting(const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const RtIntersectCounts& out,
+                              void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_count_intersecting(d_scene, d_triangles, d_skip_instance, n, &out, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::intersecting_offsets(const float* d_triangles, const int32_t* d_skip_instance, int32_t n, int64_t* d_offsets,
+                                void* d_workspace, size_t workspace_bytes, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_intersecting_offsets(d_scene, d_triangles, d_skip_instance, n, d_offsets, d_workspace, workspace_bytes,
+                                                   stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::list_intersecting(const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const int64_t* d_offsets,
+                             int32_t max_hits, const RtIntersectList& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_list_intersecting(d_scene, d_triangles, d_skip_instance, n, d_offsets, max_hits, &out, stream,
+                                                synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

@@ -2795,11 +2795,10 @@ struct XqRay {
     bool zero;                  // d' == 0
 };
 
-__device__ __forceinline__ XqRay xq_ray(const DevInstance& in, V3 w, V3 d)
+// rule 3's set-up from a mesh-space o' and d': the shear axes and constants (the slab terms inv and omax are left unset)
+__device__ __forceinline__ void xq_shear(XqRay& r, V3 o, V3 dd)
 {
-    XqRay r;
-    r.o = apply_quat(in.q_pose, v3(w.x - in.pose_xyz[0], w.y - in.pose_xyz[1], w.z - in.pose_xyz[2]));
-    const V3 dd = apply_quat(in.q_pose, d);
+    r.o = o;
     const float ax = fabsf(dd.x), ay = fabsf(dd.y), az = fabsf(dd.z);
     int kz = 0;
     float m = ax;
@@ -2812,15 +2811,24 @@ __device__ __forceinline__ XqRay xq_ray(const DevInstance& in, V3 w, V3 d)
     r.kx = kx; r.ky = ky; r.kz = kz;
     r.sx = xq_sel(dd, kx) / dz; r.sy = xq_sel(dd, ky) / dz; r.sz = 1.0f / dz;
     r.ox = xq_sel(r.o, kx); r.oy = xq_sel(r.o, ky); r.oz = xq_sel(r.o, kz);
+}
+
+__device__ __forceinline__ XqRay xq_ray(const DevInstance& in, V3 w, V3 d)
+{
+    XqRay r;
+    const V3 o = apply_quat(in.q_pose, v3(w.x - in.pose_xyz[0], w.y - in.pose_xyz[1], w.z - in.pose_xyz[2]));
+    const V3 dd = apply_quat(in.q_pose, d);
+    xq_shear(r, o, dd);
     r.inv = v3(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z);
     r.omax = fmaxf(fmaxf(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z));
     return r;
 }
 
-// rule 3 of include/rt_hip.h on the triangle (A, A + AB, A + AC): 0 = not counted, else the sign of the crossing (+1 leaving)
-__device__ __forceinline__ int xq_triangle(const XqRay& r, V3 a, V3 ab, V3 ac, float tmax)
+// rule 3 of include/rt_hip.h on the triangle given by its vertices (a, b, c): 0 = not counted, else the sign of the crossing (+1
+// leaving); on a counted triangle also t, V, W and det (b1 = V / det, b2 = W / det)
+__device__ __forceinline__ int xq_vertices(const XqRay& r, V3 a, V3 b, V3 c, float tmax, float& t_out, float& v_out, float& w_out,
+                                           float& det_out)
 {
-    const V3 b = a + ab, c = a + ac;
     const float az = xq_sel(a, r.kz) - r.oz, bz = xq_sel(b, r.kz) - r.oz, cz = xq_sel(c, r.kz) - r.oz;
     const float ax = (xq_sel(a, r.kx) - r.ox) - r.sx * az, ay = (xq_sel(a, r.ky) - r.oy) - r.sy * az;
     const float bx = (xq_sel(b, r.kx) - r.ox) - r.sx * bz, by = (xq_sel(b, r.ky) - r.oy) - r.sy * bz;
@@ -2836,7 +2844,15 @@ __device__ __forceinline__ int xq_triangle(const XqRay& r, V3 a, V3 ab, V3 ac, f
     const float T = (u * (r.sz * az) + v * (r.sz * bz)) + w * (r.sz * cz);
     const float t = T / det;
     if (!(t > 0.0f && t <= tmax)) return 0;
+    t_out = t; v_out = v; w_out = w; det_out = det;
     return det < 0.0f ? 1 : -1;
+}
+
+// rule 3 on the triangle (A, A + AB, A + AC): 0 = not counted, else the sign of the crossing (+1 leaving)
+__device__ __forceinline__ int xq_triangle(const XqRay& r, V3 a, V3 ab, V3 ac, float tmax)
+{
+    float t, v, w, det;
+    return xq_vertices(r, a, a + ab, a + ac, tmax, t, v, w, det);
 }
 
 // Whether a counted triangle may lie in the mesh-space box lo..hi: the box is scaled (a negative scale swaps
@@ -2976,29 +2992,11 @@ struct CrossListParams {
     int32_t* count;
 };
 
-// xq_triangle with what the list needs of the test: the same fp32 sequence and fp64 fallback; on a counted triangle also t, V, W
-// and det (b1 = V / det, b2 = W / det)
+// xq_triangle with what the list needs of the test: on a counted triangle also t, V, W and det (b1 = V / det, b2 = W / det)
 __device__ __forceinline__ int xq_triangle_uvw(const XqRay& r, V3 a, V3 ab, V3 ac, float tmax, float& t_out, float& v_out, float& w_out,
                                                float& det_out)
 {
-    const V3 b = a + ab, c = a + ac;
-    const float az = xq_sel(a, r.kz) - r.oz, bz = xq_sel(b, r.kz) - r.oz, cz = xq_sel(c, r.kz) - r.oz;
-    const float ax = (xq_sel(a, r.kx) - r.ox) - r.sx * az, ay = (xq_sel(a, r.ky) - r.oy) - r.sy * az;
-    const float bx = (xq_sel(b, r.kx) - r.ox) - r.sx * bz, by = (xq_sel(b, r.ky) - r.oy) - r.sy * bz;
-    const float cx = (xq_sel(c, r.kx) - r.ox) - r.sx * cz, cy = (xq_sel(c, r.ky) - r.oy) - r.sy * cz;
-    float u = cx * by - cy * bx, v = ax * cy - ay * cx, w = bx * ay - by * ax;
-    if (u == 0.0f || v == 0.0f || w == 0.0f) {
-        const float3 e = xq_edges64(ax, ay, bx, by, cx, cy);
-        u = e.x; v = e.y; w = e.z;
-    }
-    const bool neg = u <= 0.0f && v <= 0.0f && w <= 0.0f, pos = u >= 0.0f && v >= 0.0f && w >= 0.0f;
-    const float det = (u + v) + w;
-    if (!(neg || pos) || det == 0.0f) return 0;
-    const float T = (u * (r.sz * az) + v * (r.sz * bz)) + w * (r.sz * cz);
-    const float t = T / det;
-    if (!(t > 0.0f && t <= tmax)) return 0;
-    t_out = t; v_out = v; w_out = w; det_out = det;
-    return det < 0.0f ? 1 : -1;
+    return xq_vertices(r, a, a + ab, a + ac, tmax, t_out, v_out, w_out, det_out);
 }
 
 // xq_trace's traversal, calling hit(k, slot, t, v, w, det, sign) at each counted triangle (instances in ascending order, triangles of
@@ -3444,6 +3442,252 @@ __global__ __launch_bounds__(kPointBlock, 8) void nearby_list_kernel(const Nearb
         if (p.uv) { p.uv[2 * q] = 0.0f; p.uv[2 * q + 1] = 0.0f; }
         if (p.point) { p.point[3 * q] = 0.0f; p.point[3 * q + 1] = 0.0f; p.point[3 * q + 2] = 0.0f; }
         if (p.normal) { p.normal[3 * q] = 0.0f; p.normal[3 * q + 1] = 0.0f; p.normal[3 * q + 2] = 0.0f; }
+    }
+    if (p.count) p.count[i] = total;
+    if (p.pops) p.pops[i] = pops;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------
+// Triangle intersections (rt_count_intersecting / rt_intersecting_offsets / rt_list_intersecting): every (instance, triangle) that a
+// caller's world triangle meets by rule 10 of include/rt_hip.h -- the box pre-test, then six segment tests of rule 3 -- equal to a
+// brute-force loop over every (instance, triangle) whatever the tree; the pruning argument is in DESIGN.md section 15.  One wave per
+// workgroup, one query triangle per lane, an unordered traversal on the general stack: every child box that overlaps the query's
+// box (widened as pq_gap widens it) is visited.
+// ---------------------------------------------------------------------------------------------------------
+struct TriParams {
+    const float4* records;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* tris;          // [n][3][3] world query triangles
+    const int32_t* skip;        // [n] or null: one instance per query whose pairs are never reported (-1 = none)
+    int32_t n;
+    const int64_t* offsets;     // the list kernel: [n + 1] (CSR rooms) or null: fixed rooms of max_hits
+    int32_t max_hits;
+    int32_t *instance, *triangle;   // the list kernel's keys, required; indexed by room slot
+    float *normal, *segment;    // optional, [slots][3] and [slots][2][3]
+    int32_t* count;             // optional, [n] (the offsets call: the workspace)
+    uint8_t* any;               // optional, [n] (the count kernel)
+    int32_t* pops;              // optional, [n]
+};
+constexpr int kTriBlock = 64;
+typedef StackT<kTriBlock> TriStack;
+
+// query vertex k of triangle P (world, [3][3]) in instance in's scaled mesh space: apply_lre(pose, P_k), rule 1's map
+__device__ __forceinline__ V3 ti_vertex(const float* P, const DevInstance& in, int k)
+{
+    return apply_quat(in.q_pose, v3(P[3 * k] - in.pose_xyz[0], P[3 * k + 1] - in.pose_xyz[1], P[3 * k + 2] - in.pose_xyz[2]));
+}
+__device__ __forceinline__ V3 ti_min3(V3 a, V3 b, V3 c) { return v3(fminf(fminf(a.x, b.x), c.x), fminf(fminf(a.y, b.y), c.y), fminf(fminf(a.z, b.z), c.z)); }
+__device__ __forceinline__ V3 ti_max3(V3 a, V3 b, V3 c) { return v3(fmaxf(fmaxf(a.x, b.x), c.x), fmaxf(fmaxf(a.y, b.y), c.y), fmaxf(fmaxf(a.z, b.z), c.z)); }
+
+// One axis of a child box against the query's box: the box scaled and widened exactly as pq_gap does it; kept unless a compare says
+// it lies wholly on one side, so a NaN anywhere keeps it
+__device__ __forceinline__ bool ti_axis(float lo, float hi, float s, float qlo, float qhi)
+{
+    const float x = lo * s, y = hi * s;
+    const float l = s < 0.0f ? y : x, h = s < 0.0f ? x : y;
+    const float m = fmaxf(fabsf(l), fabsf(h)) * 0x1p-16f + 0x1p-126f;
+    return !((l - m) > qhi) && !(qlo > (h + m));
+}
+__device__ __forceinline__ bool ti_box(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 qlo, V3 qhi)
+{
+    return ti_axis(lx, hx, s.x, qlo.x, qhi.x) && ti_axis(ly, hy, s.y, qlo.y, qhi.y) && ti_axis(lz, hz, s.z, qlo.z, qhi.z);
+}
+
+// Rule 10 step 4 for one pair whose boxes overlap: the query's edges Q0->Q1, Q1->Q2, Q2->Q0 against (A, B, C), then the scene
+// triangle's edges A->B, B->C, C->A against (Q0, Q1, Q2), each rule 3 with tmax = 1 on o' = X, d' = Y - X.  hit: whether one counts;
+// with `all` every test runs and p0 / p1 are the mesh-space points X + t*d' of the first and the last counting test; without it the
+// tests stop at the first that counts.  The query's vertices are mapped again here (the same sequence as the traversal's box), and
+// the whole test is out of line, so none of it occupies the traversal's registers.
+struct TiHit { int hit; V3 p0, p1; };
+__device__ __noinline__ TiHit ti_segments(const float* P, const DevInstance& in, V3 a, V3 b, V3 c, bool all)
+{
+    const V3 q0 = ti_vertex(P, in, 0), q1 = ti_vertex(P, in, 1), q2 = ti_vertex(P, in, 2);
+    TiHit h;
+    h.hit = 0; h.p0 = v3(0.0f, 0.0f, 0.0f); h.p1 = h.p0;
+#pragma unroll
+    for (int e = 0; e < 6; e++) {
+        const V3 x = e == 0 ? q0 : e == 1 ? q1 : e == 2 ? q2 : e == 3 ? a : e == 4 ? b : c;
+        const V3 y = e == 0 ? q1 : e == 1 ? q2 : e == 2 ? q0 : e == 3 ? b : e == 4 ? c : a;
+        const V3 d = y - x;
+        XqRay r;
+        xq_shear(r, x, d);
+        if (r.zero) continue;                                   // (a zero d' counts nothing)
+        float t = 0.0f, tv = 0.0f, tw = 0.0f, det = 0.0f;
+        const int sign = e < 3 ? xq_vertices(r, a, b, c, 1.0f, t, tv, tw, det) : xq_vertices(r, q0, q1, q2, 1.0f, t, tv, tw, det);
+        if (sign == 0) continue;
+        const V3 pt = v3(x.x + t * d.x, x.y + t * d.y, x.z + t * d.z);
+        if (!h.hit) h.p0 = pt;
+        h.hit = 1;
+        h.p1 = pt;
+        if (!all) break;
+    }
+    return h;
+}
+
+// Every pair of query i, instance by instance in ascending order (triangles of one instance in tree order), skipping skip[i].
+// go(k) is asked before instance k (false ends the traversal); pair(k, slot, hit) is called at each pair and returns whether to end
+// the traversal.  all: whether the pair needs the segment ends.  Returns the interior nodes visited.
+template <typename Go, typename Pair>
+__device__ __forceinline__ int32_t ti_trace(const TriParams& p, TriStack& stack, int32_t i, bool all, Go&& go, Pair&& pair)
+{
+    int32_t pops = 0;
+    const float* P = p.tris + (size_t)i * 9;
+    const int32_t skip = p.skip ? p.skip[i] : -1;
+    for (int32_t k = 0; k < p.num_instances; k++) {
+        if (k == skip) continue;
+        if (!go(k)) break;
+        const DevInstance& in = p.instances[k];
+        const V3 q0 = ti_vertex(P, in, 0), q1 = ti_vertex(P, in, 1), q2 = ti_vertex(P, in, 2);
+        const V3 qlo = ti_min3(q0, q1, q2), qhi = ti_max3(q0, q1, q2);   // rule 10 step 3's box of the query
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        bool done = false;
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: every child whose box overlaps, no order
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const bool pa = !prune || ti_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, qlo, qhi);
+                const bool pb = !prune || ti_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, qlo, qhi);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                if (pa && pb) stack.push(rb);
+                cur = pa ? ra : (pb ? rb : kNeedPop);
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    V3 a, ab, ac;
+                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
+                    const V3 b = a + ab, c = a + ac;
+                    const V3 tlo = ti_min3(a, b, c), thi = ti_max3(a, b, c);
+                    // step 3 first (NaN fails); the six segment tests only behind it
+                    if (tlo.x <= qhi.x && qlo.x <= thi.x && tlo.y <= qhi.y && qlo.y <= thi.y && tlo.z <= qhi.z && qlo.z <= thi.z) {
+                        const TiHit h = ti_segments(P, in, a, b, c, all);
+                        if (h.hit && pair(k, slot, h)) done = true;
+                    }
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel && !done);
+        if (done) break;
+    }
+    return pops;
+}
+
+// ANY = false: the number of pairs of each query (rt_count_intersecting, and rt_intersecting_offsets' first step into the workspace).
+// ANY = true (any wanted, count not): the traversal ends at the first pair, across instances too.
+template <bool ANY>
+__global__ __launch_bounds__(kTriBlock, 8) void intersect_count_kernel(const TriParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    int32_t total = 0;
+    const int32_t pops = ti_trace(p, stack, i, false, [&](int32_t) { return true; }, [&](int32_t, int32_t, const TiHit&) {
+        total++;
+        return ANY;
+    });
+    if (p.count) p.count[i] = total;
+    if (p.any) p.any[i] = total > 0 ? 1 : 0;
+    if (p.pops) p.pops[i] = pops;
+}
+
+// slot j (absolute) of a room <- the pair (instance k, record slot, triangle tid) with the segment ends h (mesh space)
+__device__ __forceinline__ void ti_store(const TriParams& p, size_t j, int32_t k, int32_t slot, int32_t tid, const TiHit& h)
+{
+    p.instance[j] = k;
+    p.triangle[j] = tid;
+    if (!(p.normal || p.segment)) return;
+    const DevInstance& in = p.instances[k];
+    if (p.normal) {
+        const V3 nn = pq_normal(p, in, slot);
+        p.normal[3 * j] = nn.x; p.normal[3 * j + 1] = nn.y; p.normal[3 * j + 2] = nn.z;
+    }
+    if (p.segment) {                                            // to world: apply_lre(inv_pose, .), closest_points' map
+        const V3 w0 = apply_quat(in.q_inv_pose, v3(h.p0.x - in.inv_pose_xyz[0], h.p0.y - in.inv_pose_xyz[1], h.p0.z - in.inv_pose_xyz[2]));
+        const V3 w1 = apply_quat(in.q_inv_pose, v3(h.p1.x - in.inv_pose_xyz[0], h.p1.y - in.inv_pose_xyz[1], h.p1.z - in.inv_pose_xyz[2]));
+        float* o = p.segment + 6 * j;
+        o[0] = w0.x; o[1] = w0.y; o[2] = w0.z; o[3] = w1.x; o[4] = w1.y; o[5] = w1.z;
+    }
+}
+
+// One traversal; each pair is inserted into the query's room, which stays sorted by (instance, triangle) -- lane-private, no atomics.
+// Pairs arrive instance by instance in ascending order, so only the order within an instance needs the insertion (tree order is not
+// triangle order).  Once the room is full a pair enters only below the last key.  In fixed rooms without count the traversal then
+// ends after the last key's instance: every later pair sorts after it.  Within that instance nothing can be skipped (triangle indices
+// are not spatial).  The rooms are the same bits with and without count.
+__global__ __launch_bounds__(kTriBlock, 8) void intersect_list_kernel(const TriParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const bool early = !p.offsets && !p.count;
+    int32_t total = 0, filled = 0;                              // (filled <= total: int32)
+    const int32_t pops = ti_trace(p, stack, i, p.segment != nullptr, [&](int32_t k) {
+        if (!early || filled < p.max_hits) return true;         // (fixed rooms: start i*K, room K)
+        return k <= p.instance[(size_t)i * (size_t)p.max_hits + (size_t)(p.max_hits - 1)];
+    }, [&](int32_t k, int32_t slot, const TiHit& h) {
+        total++;
+        size_t start;
+        uint64_t room;
+        xl_room(p, i, start, room);                             // (read again per pair: not held across the traversal)
+        if (room == 0) return false;
+        const int32_t tid = p.tri_id[slot];
+        uint64_t pos;
+        if ((uint64_t)filled < room) {
+            pos = (uint64_t)filled++;
+        } else {                                                // full: enter only below the last key
+            const size_t last = start + (size_t)(room - 1);
+            const int32_t li = p.instance[last];
+            if (k > li || (k == li && tid > p.triangle[last])) return false;      // (instances arrive in ascending order: k >= li)
+            pos = room - 1;
+        }
+        while (pos > 0) {                                       // shift the greater keys of this instance up by one slot
+            const size_t q = start + (size_t)(pos - 1);
+            const int32_t qi = p.instance[q];
+            if (qi < k || p.triangle[q] < tid) break;           // (qi <= k: an earlier instance, or this one below tid)
+            p.instance[q + 1] = qi;
+            p.triangle[q + 1] = p.triangle[q];
+            if (p.normal) { p.normal[3 * q + 3] = p.normal[3 * q]; p.normal[3 * q + 4] = p.normal[3 * q + 1]; p.normal[3 * q + 5] = p.normal[3 * q + 2]; }
+            if (p.segment) {
+                for (int c = 0; c < 6; c++) p.segment[6 * q + 6 + c] = p.segment[6 * q + c];
+            }
+            pos--;
+        }
+        ti_store(p, start + (size_t)pos, k, slot, tid, h);
+        return false;
+    });
+    size_t start;
+    uint64_t room;
+    xl_room(p, i, start, room);
+    for (uint64_t j = (uint64_t)filled; j < room; j++) {        // padding
+        const size_t q = start + (size_t)j;
+        p.instance[q] = -1;
+        p.triangle[q] = -1;
+        if (p.normal) { p.normal[3 * q] = 0.0f; p.normal[3 * q + 1] = 0.0f; p.normal[3 * q + 2] = 0.0f; }
+        if (p.segment) { for (int c = 0; c < 6; c++) p.segment[6 * q + c] = 0.0f; }
     }
     if (p.count) p.count[i] = total;
     if (p.pops) p.pops[i] = pops;
@@ -5234,6 +5478,96 @@ int rt_list_nearby(RtScene* s, const float* d_points, const float* d_max_distanc
         const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
         const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
         hipLaunchKernelGGL(nearby_list_kernel, dim3(groups), dim3(kPointBlock), lds, (hipStream_t)stream, p);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+extern "C++" {
+namespace {
+TriParams intersect_params(const RtScene* s, const float* d_triangles, const int32_t* d_skip_instance, int32_t n)
+{
+    TriParams p;
+    memset(&p, 0, sizeof p);
+    p.records = s->d_records; p.tri_id = s->d_tri_id; p.leaf_count = s->d_leaf_count;
+    p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
+    p.num_instances = (int32_t)s->instances.size();
+    p.stack_depth = s->max_stack;
+    p.tris = d_triangles; p.skip = d_skip_instance; p.n = n;
+    return p;
+}
+void launch_intersect_count(const TriParams& p, bool any_only, hipStream_t st)
+{
+    const unsigned groups = (unsigned)(((int64_t)p.n + kTriBlock - 1) / kTriBlock);
+    const size_t lds = (size_t)lds_rows(p.stack_depth) * kTriBlock * sizeof(int);
+    if (any_only)
+        hipLaunchKernelGGL(intersect_count_kernel<true>, dim3(groups), dim3(kTriBlock), lds, st, p);
+    else
+        hipLaunchKernelGGL(intersect_count_kernel<false>, dim3(groups), dim3(kTriBlock), lds, st, p);
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_count_intersecting(RtScene* s, const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const RtIntersectCounts* out,
+                          void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_triangles || !out))) return RT_E_INVALID;
+    if (n > 0 && !(out->count || out->any || out->pops)) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    {
+        RT_SCENE_CALL(s);
+        TriParams p = intersect_params(s, d_triangles, d_skip_instance, n);
+        p.count = out->count; p.any = out->any; p.pops = out->pops;
+        launch_intersect_count(p, p.any && !p.count, (hipStream_t)stream);     // (any without count: stop at the first pair)
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+size_t rt_intersecting_offsets_workspace_bytes(int32_t n)
+{
+    return n > 0 ? crossing_offsets_bytes(n, nullptr, nullptr) : 0;
+}
+
+int rt_intersecting_offsets(RtScene* s, const float* d_triangles, const int32_t* d_skip_instance, int32_t n, int64_t* d_offsets,
+                            void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_triangles || !d_offsets || !d_workspace))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
+    int64_t blocks[8];
+    int levels = 0;
+    if (workspace_bytes < crossing_offsets_bytes(n, blocks, &levels)) return RT_E_INVALID;
+    {
+        RT_SCENE_CALL(s);
+        const hipStream_t st = (hipStream_t)stream;
+        TriParams p = intersect_params(s, d_triangles, d_skip_instance, n);
+        p.count = (int32_t*)d_workspace;
+        launch_intersect_count(p, false, st);
+        scan_offsets(d_workspace, n, d_offsets, blocks, levels, st);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_list_intersecting(RtScene* s, const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const int64_t* d_offsets,
+                         int32_t max_hits, const RtIntersectList* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_triangles || !out))) return RT_E_INVALID;
+    if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
+    if (n > 0 && !(out->instance && out->triangle)) return RT_E_INVALID;     // the room holds the keys
+    if (n == 0) return RT_OK;
+    {
+        RT_SCENE_CALL(s);
+        TriParams p = intersect_params(s, d_triangles, d_skip_instance, n);
+        p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
+        p.instance = out->instance; p.triangle = out->triangle; p.normal = out->normal; p.segment = out->segment;
+        p.count = out->count; p.pops = out->pops;
+        const unsigned groups = (unsigned)(((int64_t)n + kTriBlock - 1) / kTriBlock);
+        const size_t lds = (size_t)lds_rows(p.stack_depth) * kTriBlock * sizeof(int);
+        hipLaunchKernelGGL(intersect_list_kernel, dim3(groups), dim3(kTriBlock), lds, (hipStream_t)stream, p);
         RT_HIP(hipGetLastError());
     }
     RT_WAIT_IF(synchronize, stream);

@@ -596,6 +596,70 @@ int rt_nearby_offsets(RtScene *scene, const float *d_points, const float *d_max_
 int rt_list_nearby(RtScene *scene, const float *d_points, const float *d_max_distance, int32_t n, const int64_t *d_offsets,
                    int32_t max_hits, const RtNearbyList *out, void *stream, int synchronize);
 
+/* ---- triangle intersections: every (instance, triangle) of the scene that a caller's world triangle meets --
+ *      collision and interference checks.  The pairs equal a brute-force loop over every (instance, triangle), whatever the tree.
+ *      10. For query triangle j with world vertices P0, P1, P2 (fp32) and instance i:
+ *          1. Query vertices: Qk = apply_lre(pose_i, Pk), rule 1's map into scaled mesh space.  The query triangle is (Q0, Q1, Q2).
+ *          2. Scene triangle: A = v0*s, B = A + AB, C = A + AC, the fp32 sums of rule 2 (rt_closest_points' A, AB, AC).
+ *          3. Box pre-test: per axis lo = fminf(fminf(x0, x1), x2) and hi = fmaxf(fmaxf(x0, x1), x2) over each triangle's three
+ *             vertices; the pair passes when loT <= hiQ && loQ <= hiT on all three axes (NaN fails).
+ *          4. Six segment tests in a fixed order: the query's edges Q0->Q1, Q1->Q2, Q2->Q0 against the triangle (A, B, C), then the
+ *             scene triangle's edges A->B, B->C, C->A against (Q0, Q1, Q2).  Segment X->Y has o' = X and d' = Y - X (fp32 per
+ *             component).  Each test is rule 3 with tmax = 1 on the triangle given by its three vertices (no b = a + ab is
+ *             recomputed): the shear, U, V, W, the fp64 fallback with +-2^-149, det != 0 and 0 < t <= 1.  A zero d' counts nothing;
+ *             both faces count.
+ *          5. (i, triangle) is a PAIR of query j when step 3 passes and at least one of the six tests counts.
+ *          6. Per pair: instance and triangle (the uploaded numbering of rt_render_ids / rt_trace_rays / rt_closest_points); normal =
+ *             the world face normal exactly as rt_closest_points gives it; segment = [2][3] world points of the first and the last
+ *             counting test in step 4's order, each X + t*d' per component in fp32, mapped to world by apply_lre(inv_pose_i, .)
+ *             (closest_points' map).  The two ends are equal when only one test counts.
+ *          7. ORDER: a query's pairs sorted by (instance, triangle) ascending.  ROOMS, padding and "nothing is ever written outside a
+ *             room" are rule 8's; padding is instance = triangle = -1, normal and segment 0.
+ *          8. skip_instance (optional int32 [n]): per query one instance whose pairs are never reported (-1 = none).  Instance k's own
+ *             world triangles with skip_instance = k ask "what does instance k touch?".
+ *      COPLANAR triangles: every segment test then rests on rounding in the sheared coordinates, so coplanar overlap is not reliably
+ *      reported.  Closed meshes that touch face to face typically still report a contact, through side faces whose edges end on the
+ *      shared plane.
+ *      SHARED vertices and edges: the tests are closed, so triangles that share a vertex or an edge normally report a pair.  This is
+ *      why the query is not (yet) a self-intersection test.
+ *      NON-FINITE input: query triangles with a non-finite coordinate do not fault, do not change other queries' results and never
+ *      write outside their room; their own results are unspecified.
+ *      rt_count_intersecting: count [n] (the number of pairs), any [n] (1 when there is one), pops [n] (interior nodes visited, a
+ *      statistic); all optional, at least one given.  With any and without count the traversal ends at the first pair, across
+ *      instances too (the cheap collision check).
+ *      rt_intersecting_offsets writes offsets[0] = 0 and offsets[i+1] = offsets[i] + count_i (int64): the count traversal into the
+ *      workspace, then rt_crossing_offsets' exclusive scan on the device.  Its workspace is DEVICE memory of at least
+ *      rt_intersecting_offsets_workspace_bytes(n) bytes (0 for n <= 0).  With n == 0 nothing is launched and d_offsets is not written.
+ *      rt_list_intersecting fills the rooms: CSR (d_offsets) or fixed (d_offsets NULL, max_hits = K >= 1), as in rule 8.  instance and
+ *      triangle are REQUIRED (the room is where the keys live), the rest optional; count[n] is each query's FULL count.  In fixed
+ *      rooms without count, once a room is full the traversal ends after the instance of the room's last key; the rooms are the same
+ *      bits with and without count.
+ *      All calls: d_triangles is a DEVICE array [n][3][3] of world vertices; asynchronous on `stream` unless synchronize != 0; no host
+ *      synchronisation, allocation or scene scratch (calls may overlap each other and renders); nothing launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL triangles with n > 0; rt_count_intersecting: NULL out or no output with n > 0;
+ *      rt_intersecting_offsets: d_offsets or d_workspace NULL, or a workspace too small, with n > 0; rt_list_intersecting: NULL out,
+ *      or instance or triangle NULL, with n > 0; both or neither of d_offsets and max_hits >= 1. ------------------------------- */
+typedef struct RtIntersectCounts {  /* every pointer optional, at least one given                                              */
+    int32_t *count;             /* [n] the number of pairs                                                                 */
+    uint8_t *any;               /* [n] 1 when the query has a pair                                                         */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic, not part of the exact contract)                */
+} RtIntersectCounts;
+typedef struct RtIntersectList {    /* fields indexed by room slot; instance and triangle REQUIRED, the rest optional          */
+    int32_t *instance;          /* [slots] -1 = padding                                                                    */
+    int32_t *triangle;          /* [slots] the uploaded numbering; -1 = padding                                            */
+    float *normal;              /* [slots][3] world face normal                                                            */
+    float *segment;             /* [slots][2][3] world points of the first and the last counting segment test             */
+    int32_t *count;             /* [n] the full number of pairs of each query                                              */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic)                                                */
+} RtIntersectList;
+int rt_count_intersecting(RtScene *scene, const float *d_triangles, const int32_t *d_skip_instance, int32_t n,
+                          const RtIntersectCounts *out, void *stream, int synchronize);
+size_t rt_intersecting_offsets_workspace_bytes(int32_t n);
+int rt_intersecting_offsets(RtScene *scene, const float *d_triangles, const int32_t *d_skip_instance, int32_t n, int64_t *d_offsets,
+                            void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+int rt_list_intersecting(RtScene *scene, const float *d_triangles, const int32_t *d_skip_instance, int32_t n, const int64_t *d_offsets,
+                         int32_t max_hits, const RtIntersectList *out, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
