@@ -124,7 +124,7 @@ def build(force=False, verbose=False):
 
 def _build_locked(force, verbose):
     if force or _hip_out_of_date():
-        # RT_HIPCC_EXTRA: extra compiler flags for A/B experiments on the kernels (e.g. -DRT_PRED_STACK=1); never set in a normal build.
+        # RT_HIPCC_EXTRA: extra compiler flags for A/B experiments on the kernels (tools/build_variant.sh: e.g. -O2, or a -D of a patch under test); never set in a normal build.
         # The hash of what is being compiled goes into the binary (rt_build_info): the roofline guard of bench.py and libs()
         # check the library that runs, not the sources next to it.
         if not os.path.exists(HIPCC):

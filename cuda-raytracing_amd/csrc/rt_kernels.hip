@@ -25,53 +25,10 @@
 
 using namespace rt;
 
-// build-time switches of the traversal loop (A/B experiments only: RT_HIPCC_EXTRA=-DRT_OCTANTS=0 ...; the defaults are what ships)
-#ifndef RT_OCTANTS
-#define RT_OCTANTS 1            // octant-specialised loops, see trace_instance
-#endif
-#ifndef RT_WAIT_AT_FETCH
-#define RT_WAIT_AT_FETCH 0      // 1: the vector fetch waits for its four loads where it issues them (measured +0.5 %), see trace_loop
-#endif
-#ifndef RT_SENTINEL
-#define RT_SENTINEL 1           // the traversal stack starts with a sentinel entry: "stack empty" is a value popped, see trace_loop
-#endif
-#ifndef RT_STACK_WAVE_CHECK
-#define RT_STACK_WAVE_CHECK 0   // 1: push / pop ask once per wave whether any lane is beyond the LDS part of the stack (measured +0.8 %), see StackT
-#endif
-#ifndef RT_LANE_MORTON
-#define RT_LANE_MORTON 0        // 1: lanes of a wave cover their 8x8 pixels in Z-order (a quad of lanes = 2x2 pixels; measured +-0.3 %), see pixel_of
-#endif
-#ifndef RT_LEAF_FLAT
-#define RT_LEAF_FLAT 1          // leaf step without the empty-leaf region; the wave's "any accept" asked inside the leaf region
-#endif
-#ifndef RT_EX_RECOMPUTE
-#define RT_EX_RECOMPUTE 0       // 1: render_ex_kernel derives base colour, normal and cosine of a shaded hit again after its shadow cast instead of keeping
-                                // them across it (measured +1.1 % on c3: profiles/r05_experiments/ex_spill_variants.md)
-#endif
-#ifndef RT_EX_PEEL
-#define RT_EX_PEEL 1            // render_ex_kernel: the primary ray's depth written out before the bounce loop (measured -0.7 % on c3, same log)
-#endif
-#ifndef RT_OPTIMISTIC_STACK
-#define RT_OPTIMISTIC_STACK 1   // deep trees: the timed kernels run the LDS-only stack and a lane whose stack would outgrow it starts again on the
-                                // general stack afterwards (render_pixel), instead of every push and pop asking "which memory"
-#endif
-// Measured and off (round 6, profiles/r06_experiments/ex_secondary_asm.md): the bounce kernel's secondary rays through the hand-written loop
-// (bit 0: shadow rays, bit 1: bounce rays; trace_instance's SEC) and the kernel compiled for fewer waves per SIMD (8: 64 registers,
-// 7: 72, 6: 80).  The loop saves instructions (-4.5 % vector, -16 % scalar on c3 with bit 1) and 5 % of the frame at EQUAL occupancy,
-// but at eight waves its 53 registers push the path state into scratch (writes x 2.5, fetches x 10: c3 +5 %), and every wave given up
-// for registers costs more than the loop returns (c3: 8 waves 19.4 ms, 7: 19.8, 6: 20.9; 6 waves with the loop: 19.8).
-#ifndef RT_EX_BOUNCE_WAVES
-#define RT_EX_BOUNCE_WAVES 8
-#endif
-#ifndef RT_EX_SECONDARY_ASM
-#define RT_EX_SECONDARY_ASM 0
-#endif
-#ifndef RT_EX_PRIMARY_ASM
-#define RT_EX_PRIMARY_ASM 1     // the bounce kernel's camera ray through the hand-written loop and the view records
-#endif
-#ifndef RT_NEED_POP_VALUE
-#define RT_NEED_POP_VALUE 1     // "this lane must pop" is a value of `cur` (kNeedPop), not a flag merged across the loop's branches
-#endif
+// The traversal code below holds ONE form of everything: the forms that were measured against it and lost (the round-5 text of the
+// hand-written loop, a wave-level stack check, Z-order lanes, flag forms of the sentinel loop, the bounce kernel's secondary rays through
+// the hand-written loop, ...) live in history; their logs under profiles/r0*_experiments/ name the commits that hold them.  An A/B
+// experiment is a variant library built with RT_HIPCC_EXTRA (tools/build_variant.sh), not a switch kept here.
 
 // =====================================================================================
 //                                      device code
@@ -175,13 +132,13 @@ constexpr int kLdsStack = 16;
 // Two entries no tree contains: leaf references whose slot field is beyond every slot a scene can hold (rt_scene_upload and the
 // rebuild keep slot_base + n + 1 <= kSlotMask, so the largest first-slot of a leaf is kSlotMask - 2).  Chosen among the
 // hardware's inline integer constants (-16 .. 64): compares and selects against them need no register.
-// kSentinel: with RT_SENTINEL the first entry of every traversal; popping it ends the loop.
+// kSentinel: the first entry of every traversal; popping it ends the loop.
 // kNeedPop: what interior_apply / the leaf step leave in `cur` when the lane has to pop.
 constexpr int32_t kSentinel = -2;               // = leaf flag | count 31 | slot kSlotMask - 1
 constexpr int32_t kNeedPop = -1;                // = leaf flag | count 31 | slot kSlotMask
 static_assert((kSentinel & kSlotMask) == kSlotMask - 1 && (kNeedPop & kSlotMask) == kSlotMask, "beyond the slot space");
 // rows of a workgroup's LDS stack block ([row][thread] ints): the postponed nodes kept in LDS, plus the sentinel's row
-__host__ __device__ inline int lds_rows(int stack_depth) { return (stack_depth < kLdsStack ? stack_depth : kLdsStack) + RT_SENTINEL; }
+__host__ __device__ inline int lds_rows(int stack_depth) { return (stack_depth < kLdsStack ? stack_depth : kLdsStack) + 1; }
 typedef __attribute__((address_space(3))) int lds_int;      // typed LDS pointer: keeps stack traffic on ds_read/ds_write
 // SPILL = false: the tree is shallow enough for the LDS part alone (a tree of L levels never holds more than L - 1 postponed
 // nodes: the entries of a stack sit at strictly increasing levels below the root) -- no private array, and neither push
@@ -201,16 +158,11 @@ struct StackT {
     int* spill;                 // this lane's private overflow, kMaxStack - kLdsStack entries
     int lds_depth;              // entries kept in LDS: lds_rows(stack_depth)
     int sp;
-    // (RT_STACK_WAVE_CHECK: whether ANY lane of the wave is beyond the LDS part is asked once per wave -- a scalar branch; the
-    // per-lane "which memory" regions then only run when one is.  Deep entries are rare (the c2 tree has 28 levels and no
-    // ray of its three cameras holds more than 16 postponed nodes), but the ballot costs what the regions cost: measured
-    // +0.8 % on c2, off.)
+    // (Asking once per wave whether ANY lane is beyond the LDS part costs what the per-lane "which memory" regions cost: measured
+    // +0.8 % on c2, profiles/r04_experiments/sentinel_loop_ab.log.)
     __device__ __forceinline__ void push(int32_t v)
     {
-        if constexpr (SPILL && RT_STACK_WAVE_CHECK) {
-            if (__builtin_amdgcn_ballot_w64(sp >= lds_depth) == 0ull) lds[sp * STRIDE] = v;
-            else if (sp < lds_depth) lds[sp * STRIDE] = v; else spill[sp - lds_depth] = v;
-        } else if constexpr (SPILL) { if (sp < lds_depth) lds[sp * STRIDE] = v; else spill[sp - lds_depth] = v; }
+        if constexpr (SPILL) { if (sp < lds_depth) lds[sp * STRIDE] = v; else spill[sp - lds_depth] = v; }
         else lds[sp * STRIDE] = v;
         sp++;
     }
@@ -218,7 +170,6 @@ struct StackT {
     {
         --sp;
         if constexpr (!SPILL) return lds[sp * STRIDE];
-        if constexpr (RT_STACK_WAVE_CHECK) { if (__builtin_amdgcn_ballot_w64(sp >= lds_depth) == 0ull) return lds[sp * STRIDE]; }
         // always an LDS read (index clamped) and, rarely, a private read on top: a select between the two
         // address spaces would turn into one slow flat_load
         int32_t v = lds[(sp < lds_depth ? sp : lds_depth - 1) * STRIDE];
@@ -386,20 +337,18 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
                                            V3 org, STK& stack, Hit& hit, Counters<DEBUG>& cnt, int* iters, int* pops, uint32_t vdelta = 0,
                                            float tmax = FLT_MAX)
 {
-    static_assert(!VIEW || (!DEBUG && !PROF && !EX && RT_SENTINEL && RT_LEAF_FLAT), "view records: the timed primary kernels only");
+    static_assert(!VIEW || (!DEBUG && !PROF && !EX), "view records: the timed primary kernels only");
     stack.sp = 0;
-#if RT_SENTINEL
     // The stack starts with a sentinel (raycast.cu:58 starts it with the root, which here stays in a register): "pop from an
     // empty stack" (raycast.cu:60) is then an ordinary pop that returns the sentinel, and the loop ends on the VALUE popped --
     // one compare for all lanes at the bottom of the loop instead of an `if (sp == 0) break` nested in the pop branch, which
     // cost ten scalar instructions of exec-mask bookkeeping per iteration.
     stack.push(kSentinel);
-#endif
     int32_t cur = in.root_ref;                                  // raycast.cu:58 (kept in a register)
     bool have = true;
     // "this lane must pop" as a value of `cur` instead of the flag `have`: -1.5 % on the primary kernel, +0.8 % on the bounce
     // casts of the extension kernel (EX: they keep the flag) -- profiles/r04_experiments/sentinel_loop_ab.log
-    constexpr bool kNeedPopValue = RT_SENTINEL && RT_NEED_POP_VALUE && !EX;
+    constexpr bool kNeedPopValue = !EX;
     int rem = -1;                                               // triangles left in the leaf being walked, -1 = not in a leaf
     unsigned long long c_pop = 0, c_mem = 0, c_int = 0, c_leaf = 0, n_it = 0, n_int = 0, n_leaf = 0, t0 = 0, t1 = 0, t2 = 0, t3 = 0;
     unsigned long long n_g1 = 0, n_g2 = 0, n_g34 = 0;
@@ -480,13 +429,9 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
         } else {
             const float4* rec = p.records + (size_t)(cur & kSlotMask) * 4;     // node or triangle: one array, one index space
             r0 = rec[0]; r1 = rec[1]; r2 = rec[2]; r3 = rec[3];
-#if RT_WAIT_AT_FETCH
-            // All four loads are waited for HERE (the empty asm uses a word of each): otherwise every later use of r0..r3 -- in
-            // code that the wave-uniform path shares -- gets its own s_waitcnt vmcnt(n), ten no-ops per iteration on the
-            // path that issued no vector load at all.  Measured: ten fewer instructions per iteration and 0.5 % MORE time (the
-            // subtractions of box_differences no longer overlap the later loads): off, kept as a switch for the record.
-            asm volatile("" : "+v"(r0.x), "+v"(r1.x), "+v"(r2.x), "+v"(r3.x));
-#endif
+            // (Every later use of r0..r3 gets its own s_waitcnt vmcnt(n), also on the path that issued no vector load.  Waiting for all
+            // four loads HERE saves ten instructions per iteration and costs 0.5 % MORE time: the subtractions of box_differences no
+            // longer overlap the later loads -- profiles/r04_experiments/sentinel_loop_ab.log.)
             if (interior) {
                 const float w[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
                 box_differences(w, r.ro, r0, r1, r2);
@@ -519,7 +464,7 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
             const int coded = (cur >> kSlotBits) & 31;
             rem = first ? coded : rem;
             if (first & (coded == 31)) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles: rare)
-            if constexpr (DEBUG || !RT_LEAF_FLAT) {             // (the instrumented kernel counts triangle tests: none for an empty leaf)
+            if constexpr (DEBUG) {                              // (the instrumented kernel counts triangle tests: none for an empty leaf)
                 if (rem > 0) accept = triangle_test<DEBUG, EX>(p, in, exact_uv, identity_inv, r, org, slot, hit.min, cnt, r0, r1, r2, r3, c);
             } else {
                 // An empty leaf (degenerate splits only) holds no triangle to test: its "test" runs on whatever record sits at
@@ -527,13 +472,12 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
                 // in every leaf iteration of every other scene.
                 accept = triangle_test<DEBUG, EX>(p, in, exact_uv, identity_inv, r, org, slot, hit.min, cnt, r0, r1, r2, r3, c) & (rem > 0);
             }
-            if constexpr (RT_LEAF_FLAT) any_accept = __builtin_amdgcn_ballot_w64(accept);   // (asked here, where `accept` is a compare result, not a merged flag)
+            any_accept = __builtin_amdgcn_ballot_w64(accept);   // (asked here, where `accept` is a compare result, not a merged flag)
             rem--;
             have = rem > 0;
             cur = have ? cur + 1 : (kNeedPopValue ? kNeedPop : cur);    // next slot of the same leaf (the slot field never overflows)
             rem = have ? rem : -1;
         }
-        if constexpr (!RT_LEAF_FLAT) any_accept = __builtin_amdgcn_ballot_w64(accept);
         if (any_accept != 0ull) {                               // (wave-level: most iterations accept nothing)
             hit.min = accept ? c.dist : hit.min;
             hit.slot = accept ? slot : hit.slot;
@@ -547,25 +491,17 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
                 const bool done = accept & (c.dist < tmax);
                 if constexpr (kNeedPopValue) cur = done ? kSentinel : cur;
                 else {
-                    // (the flag forms of the A/B switches RT_SENTINEL=0 / RT_NEED_POP_VALUE=0: the lane leaves its leaf and finds
-                    // nothing left but the sentinel -- or nothing at all -- when it pops next)
+                    // (EX keeps "must pop" as the flag: the lane leaves its leaf and finds nothing left but the sentinel when it pops next)
                     have = done ? false : have;
                     rem = done ? -1 : rem;
-                    stack.sp = done ? RT_SENTINEL : stack.sp;
+                    stack.sp = done ? 1 : stack.sp;
                 }
             }
         }
         if constexpr (PROF) { __builtin_amdgcn_s_waitcnt(0); t0 = __builtin_amdgcn_s_memtime(); }
-#if RT_SENTINEL
         // (kNeedPopValue: `have` is not read -- as a flag it is a lane mask that every branch of the loop has to merge into,
         // eight scalar instructions per iteration; as a value of `cur` it costs one select)
         if (kNeedPopValue ? cur == kNeedPop : !have) cur = stack.pop();     // raycast.cu:60-61 (the sentinel when nothing is left)
-#else
-        if (!have) {
-            if (stack.sp == 0) break;
-            cur = stack.pop();                                  // raycast.cu:61
-        }
-#endif
         // One latch for both ways round (popped / kept going): a convergent no-op that the optimiser may not clone.
         // Without it the two back edges are split into nested loops ("iterate while nobody pops" inside "pop"),
         // i.e. lanes that need a pop wait for every lane that does not: +50 % time on views with sky.
@@ -574,7 +510,7 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
             __builtin_amdgcn_s_waitcnt(0);
             c_mem += t2 - t1; c_int += t3 - t2; c_leaf += t0 - t3; c_pop += __builtin_amdgcn_s_memtime() - t0;
         }
-    } while (!RT_SENTINEL || cur != kSentinel);
+    } while (cur != kSentinel);
     if constexpr (PROF) {
         if (p.trace) {                                          // the longest-lived lane's view of the wave
             unsigned long long v[10] = {c_pop, c_mem, c_int, c_leaf, n_it, n_int, n_leaf, n_g1, n_g2, n_g34};
@@ -590,7 +526,7 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The traversal loop of the timed primary kernels, written in gfx950 assembly (RT_ASM_LOOP; the C++ loop above stays the
+// The traversal loop of the timed primary kernels, written in gfx950 assembly (the C++ loop above stays the
 // reference form, the instrumented kernels' loop and the loop of every case this one does not take).
 //
 // Why: on this kernel every instruction costs the same, whatever unit executes it -- measured over four rounds of variants
@@ -609,75 +545,15 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
 // scalars, s[46:47] the exec mask the loop was entered with; the ray, the hit and the stack state are operands.
 // Hazards (gfx940 family): a VALU-written SGPR / VCC needs two wait states before a VALU reads it (none before a SALU read),
 // four before v_div_fmas reads VCC; a transcendental result one before a non-transcendental VALU uses it.
-#ifndef RT_ASM_LOOP
-#define RT_ASM_LOOP 1
-#endif
-#ifndef RT_ASM_GUARD
-#define RT_ASM_GUARD 0
-#endif
-// RT_ASM_V2 (round 6, second session; 0 = the loop as round 5 wrote it, kept for A/B): the same decisions from fewer vector
-// instructions -- masks that only the per-lane path reads are made there (and one of them by the scalar unit), "which child passes"
-// is taken from the slab distances themselves instead of from FLT_MAX-patched copies of them, "the nearer child is next" is folded
-// into one select, and the stack's top is kept as an LDS ADDRESS (push and pop add a constant to it instead of shifting an index).
-// No floating-point operation changes or moves; profiles/r06_experiments/asm_loop_v2.md.
-#ifndef RT_ASM_V2
-#define RT_ASM_V2 1
-#endif
-
-// RT_ASM_BACKFACE: when no lane of the wave holds a triangle that faces its ray (denom < 0, raycast.cu:107-109) the rest of
-// the triangle test -- the division, the point on the plane, the barycentrics -- is skipped for the whole wave.
-#ifndef RT_ASM_BACKFACE
-#define RT_ASM_BACKFACE 1
-#endif
-#if RT_ASM_BACKFACE
-#define RT_ASM_BACKFACE_EXIT \
-    "s_and_b64 s[40:41], s[40:41], s[42:43]\n\t" \
-    "s_cbranch_scc0 .Lrt_next_triangle%=\n\t"
-#define RT_ASM_BACKFACE_AND ""
-#else
-#define RT_ASM_BACKFACE_EXIT ""
-#define RT_ASM_BACKFACE_AND "s_and_b64 s[40:41], s[40:41], s[42:43]\n\t"
-#endif
+// Round 6 rewrote the loop of round 5: the same decisions from fewer vector instructions -- masks that only the per-lane path reads are
+// made there (and one of them by the scalar unit), "which child passes" is taken from the slab distances themselves instead of from
+// FLT_MAX-patched copies of them, "the nearer child is next" is folded into one select, and the stack's top is kept as an LDS ADDRESS
+// (push and pop add a constant to it instead of shifting an index).  No floating-point operation changed or moved; the round-5 text
+// and the A/B against it: profiles/r06_experiments/asm_loop_v2.md.
 
 // one interior node: v0..v11 hold box - origin, v12 / v13 the two child entries; exec = the lanes at this node.
 // N* / F* = the registers holding the near / far plane of the axis for this octant (slab_oct's operand choice).
-#if !RT_ASM_V2
-#define RT_ASM_INTERIOR(AXN, AXF, AYN, AYF, AZN, AZF, BXN, BXF, BYN, BYF, BZN, BZF) \
-    "v_mul_f32 v16, " AXN ", %[dix]\n\t"  "v_mul_f32 v17, " AYN ", %[diy]\n\t"  "v_mul_f32 v18, " AZN ", %[diz]\n\t" \
-    "v_mul_f32 v19, " AXF ", %[dix]\n\t"  "v_mul_f32 v20, " AYF ", %[diy]\n\t"  "v_mul_f32 v21, " AZF ", %[diz]\n\t" \
-    "v_max3_f32 v16, v16, v17, v18\n\t"                 /* near of a */ \
-    "v_min3_f32 v19, v19, v20, v21\n\t"                 /* far of a */ \
-    "v_mul_f32 v22, " BXN ", %[dix]\n\t"  "v_mul_f32 v23, " BYN ", %[diy]\n\t"  "v_mul_f32 v24, " BZN ", %[diz]\n\t" \
-    "v_mul_f32 v25, " BXF ", %[dix]\n\t"  "v_mul_f32 v26, " BYF ", %[diy]\n\t"  "v_mul_f32 v27, " BZF ", %[diz]\n\t" \
-    "v_max3_f32 v22, v22, v23, v24\n\t"                 /* near of b */ \
-    "v_min3_f32 v25, v25, v26, v27\n\t"                 /* far of b */ \
-    "v_cmp_ge_f32_e32 vcc, v19, v16\n\t" \
-    "v_cmp_lt_f32_e64 s[38:39], 0, v19\n\t" \
-    "v_cmp_ge_f32_e64 s[40:41], v25, v22\n\t" \
-    "v_cmp_lt_f32_e64 s[42:43], 0, v25\n\t" \
-    "v_mov_b32_e32 v17, 0x7f7fffff\n\t" \
-    "s_and_b64 vcc, vcc, s[38:39]\n\t" \
-    "s_and_b64 s[40:41], s[40:41], s[42:43]\n\t" \
-    "v_cndmask_b32_e32 v16, v17, v16, vcc\n\t"          /* da = hit ? near : FLT_MAX */ \
-    "v_cndmask_b32_e64 v22, v17, v22, s[40:41]\n\t"     /* db */ \
-    "v_cmp_lt_f32_e64 s[38:39], v16, %[hmin]\n\t"       /* pa */ \
-    "v_cmp_lt_f32_e64 s[40:41], v22, %[hmin]\n\t"       /* pb */ \
-    "v_cmp_lt_f32_e64 s[42:43], v16, v22\n\t"           /* a is the nearer */ \
-    "s_and_b64 s[44:45], s[38:39], s[40:41]\n\t"        /* both pass: one is pushed */ \
-    "s_or_b64 vcc, s[38:39], s[40:41]\n\t"              /* any passes */ \
-    "v_cndmask_b32_e64 v18, v13, v12, s[38:39]\n\t"     /* next = pa ? a : b */ \
-    "s_and_saveexec_b64 s[38:39], s[44:45]\n\t" \
-    "v_lshl_add_u32 v20, %[sp], %[shift], %[col]\n\t" \
-    "v_cmp_gt_i32_e64 s[44:45], %[depth], %[sp]\n\t"    /* the push fits (else it lands in the spare row and the lane stops, see StackT) */ \
-    "v_cndmask_b32_e64 v18, v13, v12, s[42:43]\n\t"     /* the nearer child is next */ \
-    "ds_write_b32 v20, %[tos]\n\t"                     /* the stack's top lives in a register: the one below it goes to LDS ... */ \
-    "v_add_u32_e32 %[sp], 1, %[sp]\n\t" \
-    "v_cndmask_b32_e64 %[tos], v12, v13, s[42:43]\n\t"  /* ... and the farther child becomes the top */ \
-    "v_cndmask_b32_e64 v18, -2, v18, s[44:45]\n\t" \
-    "s_or_b64 exec, exec, s[38:39]\n\t" \
-    "v_cndmask_b32_e32 %[cur], -1, v18, vcc\n\t"        /* nothing passes: this lane pops */
-#else
-// (v2) pa = hit(a) and near(a) < hit.min, pb likewise: the reference's `dist < hit.min` on a distance that is FLT_MAX for a miss
+// pa = hit(a) and near(a) < hit.min, pb likewise: the reference's `dist < hit.min` on a distance that is FLT_MAX for a miss
 // (BVHTree.hpp:40-54, raycast.cu:72-79) -- FLT_MAX < hit.min is false for every hit.min, so the mask is the same without the select;
 // "a is the nearer" is only read where both pass, i.e. where both distances are the slab's own.  s[38:39] = pa, s[40:41] = pb,
 // s[68:69] = near(a) < near(b), s[42:43] = the lanes that go on with a, vcc = the lanes that go on at all.
@@ -714,7 +590,6 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
     "v_cndmask_b32_e64 v18, -2, v18, s[44:45]\n\t" \
     "s_or_b64 exec, exec, s[38:39]\n\t" \
     "v_cndmask_b32_e32 %[cur], -1, v18, vcc\n\t"        /* nothing passes: this lane pops */
-#endif
 
 // The pieces that differ between the plain loop and the VIEW loop (RtScene::ViewPool: interior records whose box words already are
 // box - origin, `vdelta` bytes behind the records themselves):
@@ -766,22 +641,14 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
 #define RT_ASM_ANYHIT_LEAVE "v_cndmask_b32_e64 %[cur], %[cur], -2, s[66:67]\n\t"
 #define RT_ASM_LOC "v_mov_b32_e32 %[px], v18\n\tv_mov_b32_e32 %[py], v19\n\tv_mov_b32_e32 %[pz], v20\n\t"
 
-// RT_ASM_LAYOUT (round 6): fewer TAKEN branches on the common paths -- a taken branch restarts the wave's instruction fetch.  The
-// count lookup of a leaf above 30 triangles moves out of line (the branch over it was taken at almost every triangle), and the
-// wave-uniform interior step ends in its own copy of the pop / latch block instead of a branch to the shared one.
-#ifndef RT_ASM_LAYOUT
-#define RT_ASM_LAYOUT RT_ASM_V2
-#endif
-#define RT_ASM_LONG_LEAF_BODY \
-    "s_and_saveexec_b64 s[40:41], s[38:39]\n\t" \
-    "v_and_b32_e32 v17, 0x3ffffff, %[cur]\n\t" \
-    "v_lshlrev_b32_e32 v17, 2, v17\n\t" \
-    "global_load_dword %[rem], v17, %[lc]\n\t" \
-    "s_waitcnt vmcnt(0)\n\t" \
-    "s_or_b64 exec, exec, s[40:41]\n\t"
-#if RT_ASM_LAYOUT
-#define RT_ASM_LONG_LEAF_INLINE "s_cbranch_scc1 .Lrt_long%=\n\t"
-#define RT_ASM_LONG_LEAF_OUT_OF_LINE ".Lrt_long%=:\n\t" RT_ASM_LONG_LEAF_BODY "s_branch .Lrt_short%=\n\t"
+// Few TAKEN branches on the common paths -- a taken branch restarts the wave's instruction fetch.  The count lookup of a leaf above
+// 30 triangles sits out of line (.Lrt_long: the branch over it was taken at almost every triangle), and the wave-uniform interior step
+// ends in its own copy of the pop / latch block instead of a branch to the shared one (profiles/r06_experiments/asm_loop_v2.md).
+#define RT_ASM_POP \
+    "v_subrev_u32_e32 %[sa], %[stride], %[sa]\n\t" \
+    "s_waitcnt lgkmcnt(0)\n\t"                         /* (the top's reload of an earlier pop: long done) */ \
+    "v_mov_b32_e32 %[cur], %[tos]\n\t"                 /* the popped entry is in a register: the lane goes on at once ... */ \
+    "ds_read_b32 %[tos], %[sa]\n\t"                    /* ... and the new top arrives while it works on it */
 #define RT_ASM_UNI_TAIL \
     "v_cmp_eq_u32_e32 vcc, -1, %[cur]\n\t" \
     "s_and_saveexec_b64 s[36:37], vcc\n\t" \
@@ -793,45 +660,15 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
     "s_and_b64 exec, exec, vcc\n\t" \
     "s_cbranch_execnz .Lrt_top%=\n\t" \
     "s_branch .Lrt_exit%=\n\t"
-#else
-#define RT_ASM_LONG_LEAF_INLINE "s_cbranch_scc0 .Lrt_short%=\n\t" RT_ASM_LONG_LEAF_BODY
-#define RT_ASM_LONG_LEAF_OUT_OF_LINE ""
-#define RT_ASM_UNI_TAIL "s_branch .Lrt_pop%=\n\t"
-#endif
-#if RT_ASM_V2
-#define RT_ASM_POP \
-    "v_subrev_u32_e32 %[sa], %[stride], %[sa]\n\t" \
-    "s_waitcnt lgkmcnt(0)\n\t"                         /* (the top's reload of an earlier pop: long done) */ \
-    "v_mov_b32_e32 %[cur], %[tos]\n\t"                 /* the popped entry is in a register: the lane goes on at once ... */ \
-    "ds_read_b32 %[tos], %[sa]\n\t"                    /* ... and the new top arrives while it works on it */
-#else
-#define RT_ASM_POP \
-    "v_add_u32_e32 %[sp], -1, %[sp]\n\t" \
-    "s_waitcnt lgkmcnt(0)\n\t"                         /* (the top's reload of an earlier pop: long done) */ \
-    "v_lshl_add_u32 v16, %[sp], %[shift], %[col]\n\t" \
-    "v_mov_b32_e32 %[cur], %[tos]\n\t"                 /* the popped entry is in a register: the lane goes on at once ... */ \
-    "ds_read_b32 %[tos], v16\n\t"                      /* ... and the new top arrives while it works on it */
-#endif
-// s[64:65] = the lanes at an interior node, s[34:35] = the lanes at a triangle: read by the per-lane path only.  v2 makes them there
-// (the second one is exec without the first: an entry of a live lane is a node or a triangle); the two wait states a vector read of
-// s30 needs after v_readfirstlane are an s_nop then (v1: the two compares).  VEC_ADDR_VIEW reads s[64:65] two instructions later.
-#if RT_ASM_V2
-#define RT_ASM_MASKS_AT_TOP "s_nop 1\n\t"
-#define RT_ASM_MASKS_AT_VECTOR \
-    "v_cmp_lt_i32_e64 s[64:65], -1, %[cur]\n\t" \
-    "s_andn2_b64 s[34:35], exec, s[64:65]\n\t"
-#else
-#define RT_ASM_MASKS_AT_TOP \
-    "v_cmp_lt_i32_e64 s[64:65], -1, %[cur]\n\t"         /* lanes at an interior node */ \
-    "v_cmp_gt_i32_e64 s[34:35], 0, %[cur]\n\t"          /* lanes at a triangle */
-#define RT_ASM_MASKS_AT_VECTOR ""
-#endif
+// s[64:65] = the lanes at an interior node, s[34:35] = the lanes at a triangle: read by the per-lane path only, and made there (the
+// second one is exec without the first: an entry of a live lane is a node or a triangle).  VEC_ADDR_VIEW reads s[64:65] two
+// instructions later.
 #define RT_ASM_LOOP_TEXT(COUNT_TEXT, POPS_INT, POPS_LEAF, LOC_TEXT, LEAF_TAIL, UNI_OFFSET, UNI_INTERIOR, VEC_ADDR, VEC_SUBS, AXN, AXF, AYN, AYF, AZN, AZF, BXN, BXF, BYN, BYF, BZN, BZF) \
     "s_mov_b64 s[46:47], exec\n\t" \
     ".Lrt_top%=:\n\t" \
     COUNT_TEXT \
     "v_readfirstlane_b32 s30, %[cur]\n\t" \
-    RT_ASM_MASKS_AT_TOP \
+    "s_nop 1\n\t"                                       /* (a vector read of s30 after v_readfirstlane: two wait states) */ \
     "v_cmp_ne_u32_e32 vcc, s30, %[cur]\n\t" \
     "s_cbranch_vccnz .Lrt_vector%=\n\t" \
     /* ---- every lane holds the same entry: the record comes through the scalar cache */ \
@@ -854,7 +691,8 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
     "s_branch .Lrt_leaf%=\n\t" \
     /* ---- lanes hold different entries: one 64-byte record per lane, node or triangle, from one array */ \
     ".Lrt_vector%=:\n\t" \
-    RT_ASM_MASKS_AT_VECTOR \
+    "v_cmp_lt_i32_e64 s[64:65], -1, %[cur]\n\t" \
+    "s_andn2_b64 s[34:35], exec, s[64:65]\n\t" \
     VEC_ADDR \
     "global_load_dwordx4 v[0:3], v16, %[rec]\n\t" \
     "global_load_dwordx4 v[4:7], v16, %[rec] offset:16\n\t" \
@@ -879,7 +717,7 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
     "v_cndmask_b32_e32 %[rem], %[rem], v16, vcc\n\t" \
     POPS_LEAF \
     "s_and_b64 s[38:39], s[38:39], vcc\n\t"             /* a leaf of more than 30 triangles: its count is in leaf_count */ \
-    RT_ASM_LONG_LEAF_INLINE \
+    "s_cbranch_scc1 .Lrt_long%=\n\t" \
     ".Lrt_short%=:\n\t" \
     /* TrianglePrimitive::ray_intersect: denom = rd . n, tt = ((v0 - ro) . n) / denom */ \
     "v_mul_f32_e32 v16, %[rdx], v3\n\t" \
@@ -899,7 +737,10 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
     "v_rcp_f32_e32 v19, v18\n\t" \
     "v_cmp_nlt_f32_e64 s[40:41], |v16|, %[eps]\n\t"     /* !(|denom| < 1e-6) */ \
     "v_cmp_gt_f32_e64 s[42:43], 0, v16\n\t"             /* denom < 0: the only candidates that can be accepted */ \
-    RT_ASM_BACKFACE_EXIT \
+    /* no lane of the wave holds a triangle that faces its ray: the rest of the test -- the division, the point on the plane, the \
+       barycentrics -- is skipped for the whole wave */ \
+    "s_and_b64 s[40:41], s[40:41], s[42:43]\n\t" \
+    "s_cbranch_scc0 .Lrt_next_triangle%=\n\t" \
     "v_fma_f32 v20, -v18, v19, 1.0\n\t" \
     "v_fmac_f32_e32 v19, v20, v19\n\t" \
     "v_div_scale_f32 v20, vcc, v17, v16, v17\n\t" \
@@ -909,7 +750,6 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
     "v_fma_f32 v18, -v18, v21, v20\n\t" \
     "v_div_fmas_f32 v18, v18, v19, v21\n\t" \
     "v_div_fixup_f32 v17, v18, v16, v17\n\t"            /* tt */ \
-    RT_ASM_BACKFACE_AND \
     "v_mul_f32_e32 v18, %[rdx], v17\n\t" \
     "v_mul_f32_e32 v19, %[rdy], v17\n\t" \
     "v_mul_f32_e32 v20, %[rdz], v17\n\t" \
@@ -1091,25 +931,21 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
     "v_mul_f32_e32 v7, s50, v4\n\t" \
     "v_add_f32_e32 v23, v23, v7\n\t" \
     "s_branch .Lrt_have_loc%=\n\t" \
-    RT_ASM_LONG_LEAF_OUT_OF_LINE \
+    /* ---- out of line: the count of a leaf of more than 30 triangles */ \
+    ".Lrt_long%=:\n\t" \
+    "s_and_saveexec_b64 s[40:41], s[38:39]\n\t" \
+    "v_and_b32_e32 v17, 0x3ffffff, %[cur]\n\t" \
+    "v_lshlrev_b32_e32 v17, 2, v17\n\t" \
+    "global_load_dword %[rem], v17, %[lc]\n\t" \
+    "s_waitcnt vmcnt(0)\n\t" \
+    "s_or_b64 exec, exec, s[40:41]\n\t" \
+    "s_branch .Lrt_short%=\n\t" \
     ".Lrt_end%=:\n\t"
-
-// (experiments: -DRT_ASM_PAD_KIND=1|2|3 adds eight scalar / vector / no-op instructions to every iteration, to price an instruction of each kind)
-#define RT_ASM_X8(t) t t t t t t t t
-#if RT_ASM_PAD_KIND == 1
-#define RT_ASM_PAD RT_ASM_X8("s_mov_b32 s31, s30\n\t")
-#elif RT_ASM_PAD_KIND == 2
-#define RT_ASM_PAD RT_ASM_X8("v_mov_b32 v27, v26\n\t")
-#elif RT_ASM_PAD_KIND == 3
-#define RT_ASM_PAD RT_ASM_X8("s_nop 0\n\t")
-#else
-#define RT_ASM_PAD ""
-#endif
 
 // (the byte offsets .Lrt_general reads the instance record at)
 static_assert(offsetof(DevInstance, q_inv_pose) == 0x20 && offsetof(DevInstance, scale) == 0x58 && sizeof(DevInstance) % 16 == 0, "DevInstance layout");
 
-// ORGV: the ray's world origin differs per lane (secondary rays of the extension kernel): vector operands, and never a VIEW
+// ORGV: the ray's world origin differs per lane (the ray queries' rays): vector operands, and never a VIEW
 template <int OCT, bool COUNT, int ROW_SHIFT, bool VIEW, bool POPS, bool LOC, bool ORGV = false, bool ANYHIT = false>  // ROW_SHIFT = log2 of the bytes between two entries of a lane's LDS stack column
 __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_index, const MeshRay& r, V3 org, lds_int* column, int lds_depth,
                                                int32_t& cur, int32_t& sp, Hit& hit, int& wave_iters, uint32_t vdelta, int& pops, V3& point,
@@ -1120,7 +956,6 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
     static_assert(!LOC || POPS, "the hit point is kept for the extension kernel, which counts pops");
     static_assert(!(ORGV && VIEW) && !(ANYHIT && (LOC || !POPS || !ORGV)), "secondary rays: no view; a shadow ray keeps no location");
     int32_t rem = -1;
-#if RT_ASM_V2
     // the stack pointer as the LDS address of the next free row of the lane's column, and the address of the first row that is not there
     // -- as a SCALAR: a column starts less than one row pitch behind its wave's first column (4 bytes per lane), so `row < depth` is
     // `address < first column of the wave + depth * pitch` for every lane
@@ -1130,10 +965,6 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
                           (lds_depth << ROW_SHIFT);
 #define RT_ASM_STACK_OUT [sa] "+v"(sa)
 #define RT_ASM_STACK_IN [lim] "s"(limit), [stride] "n"(1 << ROW_SHIFT)
-#else
-#define RT_ASM_STACK_OUT [sp] "+v"(sp)
-#define RT_ASM_STACK_IN [col] "v"(column), [depth] "s"(lds_depth), [shift] "n"(ROW_SHIFT)
-#endif
     int32_t tos = kSentinel;                                    // the stack's top entry (row 0 of the LDS column holds a second sentinel, so
                                                                 // that the last pop's reload reads a row that exists and leaves sp == 0)
     const float eps = __int_as_float(0x358637be);
@@ -1155,13 +986,8 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
                    "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", \
                    "s30", "s31", "s64", "s65", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", \
                    "s66", "s67", "s68", "s69", "vcc", "scc", "memory")
-#if RT_ASM_GUARD    // (bring-up only: a loop that does not end leaves after a million iterations instead of hanging the GPU)
-#define RT_ASM_COUNT "s_add_u32 %[iters], %[iters], 1\n\ts_cmp_gt_u32 %[iters], 0x100000\n\ts_cbranch_scc1 .Lrt_exit%=\n\t"
-#define RT_ASM_NOCOUNT RT_ASM_COUNT
-#else
-#define RT_ASM_COUNT "s_add_u32 %[iters], %[iters], 1\n\t" RT_ASM_PAD
-#define RT_ASM_NOCOUNT RT_ASM_PAD
-#endif
+#define RT_ASM_COUNT "s_add_u32 %[iters], %[iters], 1\n\t"
+#define RT_ASM_NOCOUNT ""
 #define RT_ASM_ARGS(...) __VA_ARGS__
     // VN = the registers of the record's planes as the per-lane fetch leaves them (x: v0 / v3 for box a, v6 / v9 for box b; y: v1 / v4,
     // v7 / v10; z: v2 / v5, v8 / v11 -- min, max), SN = the scalar registers a wave-uniform fetch leaves them in (s48 ..): per axis
@@ -1185,7 +1011,7 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
     RT_ASM_CASE(5, RT_ASM_ARGS("v3", "v0", "v1", "v4", "v5", "v2", "v9", "v6", "v7", "v10", "v11", "v8"), RT_ASM_ARGS("s51", "s48", "s49", "s52", "s53", "s50", "s57", "s54", "s55", "s58", "s59", "s56")) \
     RT_ASM_CASE(6, RT_ASM_ARGS("v0", "v3", "v4", "v1", "v5", "v2", "v6", "v9", "v10", "v7", "v11", "v8"), RT_ASM_ARGS("s48", "s51", "s52", "s49", "s53", "s50", "s54", "s57", "s58", "s55", "s59", "s56")) \
     RT_ASM_CASE(7, RT_ASM_ARGS("v3", "v0", "v4", "v1", "v5", "v2", "v9", "v6", "v10", "v7", "v11", "v8"), RT_ASM_ARGS("s51", "s48", "s52", "s49", "s53", "s50", "s57", "s54", "s58", "s55", "s59", "s56"))
-    // (the same eight loops with the ray's world origin in vector registers, and the any-hit form: secondary rays and ray queries)
+    // (the same eight loops with the ray's world origin in vector registers, and the any-hit form: the ray queries)
     if constexpr (ORGV) {
 #define RT_ASM_ORG_C "v"
 #define RT_ASM_CASE_ANYHIT(VN, SN) else if constexpr (ANYHIT) { RT_ASM_VARIANT(RT_ASM_NOCOUNT, RT_ASM_POPS_INTERIOR, RT_ASM_POPS_LEAF RT_ASM_ANYHIT_CLEAR, RT_ASM_ANYHIT_MARK, RT_ASM_ANYHIT_LEAVE, RT_ASM_OUT_ANYHIT, RT_ASM_ARGS(VN), RT_ASM_ARGS(SN)); }
@@ -1213,12 +1039,10 @@ __device__ __forceinline__ void trace_loop_asm(const RenderParams& p, int inst_i
 #undef RT_ASM_OUT_ANYHIT
 #undef RT_ASM_STACK_OUT
 #undef RT_ASM_STACK_IN
-#if RT_ASM_V2
     sp = (int32_t)(sa - column) >> (ROW_SHIFT - 2);
-#endif
 }
 
-// Octant-specialised loops (RT_OCTANTS=0 at compile time keeps only the generic one).  The rays of a wave -- an 8x8-pixel
+// Octant-specialised loops.  The rays of a wave -- an 8x8-pixel
 // tile, or the samples of a few pixels -- almost always share the sign octant of their mesh-space direction: one ballot per
 // instance decides whether the wave runs the loop instantiated for that octant (slab_oct: the min / max pairs of the slab test
 // become operand choices) or the generic loop.  A wave qualifies when every active lane has a finite origin and finite,
@@ -1247,7 +1071,7 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
     const MeshRay r = to_mesh_space(in, org, dir);
     const uint32_t vdelta = VIEW ? view_off + (uint32_t)p.view_inst_off[inst_index] : 0u;
     int oct = -1;
-    if constexpr (RT_OCTANTS && !PROF && OCTANTS) {
+    if constexpr (!PROF && OCTANTS) {
         const float inf = __int_as_float(0x7f800000);
         const bool usable = fabsf(r.dinv.x) < inf && fabsf(r.dinv.y) < inf && fabsf(r.dinv.z) < inf &&
                             r.dinv.x != 0.0f && r.dinv.y != 0.0f && r.dinv.z != 0.0f &&
@@ -1256,13 +1080,13 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
         const int first = __builtin_amdgcn_readfirstlane(mine);
         if ((p.mesh_flags[in.mesh_index] & 1) == 0 && __ballot(!usable || mine != first) == 0ull) oct = first;
     }
-    // SEC (round 6: a secondary ray of the extension kernel -- origin per lane, a shadow ray done at its first hit -- on the optimistic
-    // stack): the hand-written loop or nothing.  A wave it does not cover (mixed sign octants, an exact-uv mesh) leaves with sp != 0,
+    // SEC (round 6: a ray with an origin of its own per lane -- the ray queries' rays; an any-hit ray is done at its first hit -- on the
+    // optimistic stack): the hand-written loop or nothing.  A wave it does not cover (mixed sign octants, an exact-uv mesh) leaves with sp != 0,
     // which is what an outgrown stack looks like: cast_ray_ex then casts the ray again on the general stack and the compiler's loop, so
     // a cast site holds the eight hand-written loops and ONE compiled loop.
-    static_assert(!SEC || (RT_ASM_LOOP && RT_SENTINEL && RT_OCTANTS && OCTANTS && POPS && !VIEW && !UNIFORM_ORG && !STK::kSpill && !DEBUG && !PROF && !COUNT), "SEC");
+    static_assert(!SEC || (OCTANTS && POPS && !VIEW && !UNIFORM_ORG && !STK::kSpill && !DEBUG && !PROF && !COUNT), "SEC");
     if constexpr (SEC) { if (!(oct >= 0 && in.exact_uv == 0)) { stack.sp = 1; return; } }
-    if constexpr (RT_ASM_LOOP && RT_SENTINEL && RT_OCTANTS && OCTANTS && !DEBUG && !PROF && (UNIFORM_ORG || SEC) && (!EX || POPS) && !(POPS && COUNT) && (!ANYHIT || SEC) && !STK::kSpill) {
+    if constexpr (OCTANTS && !DEBUG && !PROF && (UNIFORM_ORG || SEC) && (!EX || POPS) && !(POPS && COUNT) && (!ANYHIT || SEC) && !STK::kSpill) {
         // the hand-written loop (trace_loop_asm) for what it covers; everything else takes the C++ loops below
         if (SEC || (oct >= 0 && in.exact_uv == 0)) {
             if constexpr (STATS) { loop_stat(p, RT_LOOP_ASM); if (in.unit_inv == 0) loop_stat(p, RT_LOOP_ASM_POSED); }
@@ -1369,15 +1193,8 @@ __device__ __forceinline__ uint32_t shade(const RenderParams& p, const Hit& hit)
 __device__ __forceinline__ void pixel_of(const RenderParams& p, const FrameParams& f, int tid, int x0, int y0, int& x, int& ly, int& y)
 {
     const int wave = tid >> 6, lane = tid & 63;
-#if RT_LANE_MORTON
-    // Z-order inside the wave's 8x8 block: four consecutive lanes are a 2x2 block of pixels, sixteen a 4x4 block (the idea: the
-    // vector memory path coalesces the lanes of a quad that read the same line, and rays of a 2x2 block hold the same entry
-    // more often than four rays in a row).  Measured: no difference on any camera (profiles/r04_experiments/sentinel_loop_ab.log);
-    // off.  (Which lane renders which pixel changes nothing a pixel computes.)
-    const int lx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), lyy = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
-#else
+    // (rows of eight lanes; Z-order inside the 8x8 block made no difference on any camera: profiles/r04_experiments/sentinel_loop_ab.log)
     const int lx = lane & 7, lyy = lane >> 3;
-#endif
     x = x0 + (wave & 1) * 8 + lx;
     ly = y0 + (wave >> 1) * 8 + lyy;
     y = ly;                                                     // stripes: local row -> frame row (the identity for one rank)
@@ -1386,7 +1203,7 @@ __device__ __forceinline__ void pixel_of(const RenderParams& p, const FrameParam
 
 // whether render_kernel<DEBUG, PROF, ., SPILL> runs the optimistic stack (StackT), and the rows of its LDS block
 template <bool DEBUG, bool PROF, bool SPILL>
-__host__ __device__ constexpr bool optimistic_stack() { return RT_OPTIMISTIC_STACK && RT_SENTINEL && SPILL && !DEBUG && !PROF; }
+__host__ __device__ constexpr bool optimistic_stack() { return SPILL && !DEBUG && !PROF; }
 template <bool DEBUG, bool PROF, bool SPILL>
 __host__ __device__ inline int lds_block_rows(int stack_depth) { return lds_rows(stack_depth) + (optimistic_stack<DEBUG, PROF, SPILL>() ? 1 : 0); }
 
@@ -1537,7 +1354,7 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
 // (profiles/r05_experiments/ex_one_wave_workgroups.log).
 // VIEW (the samples-only kernel's primary rays: they share the frame's origin): the cast reads view records, see trace_loop.
 // PRIMARY: the ray starts at the camera in every lane (trace_instance's UNIFORM_ORG).
-// SEC: a secondary ray through the hand-written loop (trace_instance); with OCTANTS and OPTIMISTIC.
+// SEC: a ray with an origin of its own per lane through the hand-written loop (trace_instance: the ray queries); with OCTANTS and OPTIMISTIC.
 // tmax (ANYHIT): the light distance of raycast.cu:129-133 -- a lane is done at its first accepted hit below it, and the instance loops
 // skip the instances after that hit (FLT_MAX for the extension's shadow rays, per ray for rt_occluded).
 // Whether the cast has returned: a hit was accepted below tmax.  (hit.min starts at FLT_MAX, which is below a tmax of +inf without any
@@ -1555,7 +1372,7 @@ __device__ __forceinline__ Hit cast_ray_ex(const RenderParams& p, V3 org, V3 dir
     hit.min = FLT_MAX; hit.slot = -1; hit.instance = -1; hit.u = 0.0f; hit.v = 0.0f;
     hit.loc = v3(0.0f, 0.0f, 0.0f);
     Counters<false> none;
-    if constexpr (OPTIMISTIC && RT_OPTIMISTIC_STACK && RT_SENTINEL && STK::kSpill) {
+    if constexpr (OPTIMISTIC && STK::kSpill) {
         // the optimistic stack (StackT, render_pixel): the cast on the LDS part alone, and again from its start on the general stack
         // for the lanes whose stack outgrew it (their pop count starts again too)
         StackT<STK::kStride, false, true> fast;
@@ -1649,6 +1466,11 @@ __device__ __forceinline__ Xorwow ex_stream(const RenderParams& p, int x, int y,
 // workgroup used to be.
 constexpr int kExBlock = 64;
 typedef StackT<kExBlock> ExStack;
+// The bounce kernel is compiled for eight waves per SIMD (64 registers) and its shadow and bounce rays take the compiler's loop.  Through
+// the hand-written loop (trace_instance's SEC, which the ray queries ship) they need 53 registers at the cast site: at eight waves that
+// pushes the path state into scratch (c3 +5 %), and every wave given up for registers costs more than the loop returns
+// (profiles/r06_experiments/ex_secondary_asm.md).
+constexpr int kExBounceWaves = 8;
 // PHASE (round 6; bounces / lighting, PX mapping): 0 = the whole path in one kernel, as above -- the default.  1 + 2 (RT_EX_SPLIT=1, opt-in)
 // = the same path in TWO launches with the same grid: phase 1 casts the camera ray -- the hand-written loop, the frame's view records,
 // no path state to carry, like the samples-only kernel -- and stores what survives the cast per lane, (slot, instance, u, v) and
@@ -1661,7 +1483,7 @@ typedef StackT<kExBlock> ExStack;
 // operation on their results are the same, so the frame is the same bit for bit (tests: both forms against each other and the oracle).
 // The launch is cut into chunks of workgroups when the records of all of it would not fit the scratch budget (wg_base).
 template <bool SIMPLE, bool PX = false, bool VIEW = false, int PHASE = 0>
-__global__ __launch_bounds__(kExBlock, (SIMPLE ? 8 : RT_EX_BOUNCE_WAVES)) void render_ex_kernel(const RenderParams p)
+__global__ __launch_bounds__(kExBlock, (SIMPLE ? 8 : kExBounceWaves)) void render_ex_kernel(const RenderParams p)
 {
     static_assert(PHASE == 0 || (PX && !SIMPLE), "the two-launch form is the bounce kernel's, in the pixel-wave mapping");
     static_assert(PHASE != 2 || !VIEW, "phase 2 casts no camera ray");
@@ -1728,37 +1550,20 @@ __global__ __launch_bounds__(kExBlock, (SIMPLE ? 8 : RT_EX_BOUNCE_WAVES)) void r
     auto after_cast = [&](Hit hit, const int depth) __attribute__((always_inline)) -> bool {
         if (hit.min == FLT_MAX) { sample = sample + weight * v3(1.0f, 0.8f, 0.6f); return false; }
         float illum = 1.0f;
-#if RT_EX_RECOMPUTE
-        // What is shaded is a function of the accepted hit -- (slot, instance, u, v) -- and the scene: base colour, normal and
-        // cosine are NOT carried across the shadow cast (seven registers of a kernel that spills), they are derived again from
-        // those four words after it: the same operations on the same inputs, so the same bits.  (The empty asm makes the slot
-        // opaque: the optimiser would otherwise recognise the second derivation and keep the first results alive.)
-        if (p.lighting) {                                   // raycast.cu:249-287 with the commented lines active
-            const float cos_illum = dot(hit_normal(p, hit), sun);
-            illum = (float)(0.4 * (double)cos_illum);
-            if (cos_illum > 0) {
-                // (only hit-or-miss survives a shadow cast: no hit location to keep.  Octant loops at either cast of this
-                // kernel: within +-0.6 %, profiles/r04_experiments/octants_in_extension_kernels.log)
-                const Hit sh = cast_ray_ex<false, false, true, ExStack>(p, hit.loc + sun * (float)1e-4, sun, stack, pops);
-                asm volatile("" : "+v"(hit.slot));
-                if (sh.min == FLT_MAX) illum = (float)(1.0 * (double)dot(hit_normal(p, hit), sun));
-            }
-        }
-        const V3 base = base_colour(p, hit);
-        const V3 n = hit_normal(p, hit);
-#else
+        // (base colour, normal and cosine are kept across the shadow cast: deriving them again after it from (slot, instance, u, v) gives
+        // the same bits with fewer spilled registers and is 1.1 % slower on c3, profiles/r05_experiments/ex_spill_variants.md)
         const V3 base = base_colour(p, hit);
         const V3 n = hit_normal(p, hit);
         if (p.lighting) {                                   // raycast.cu:249-287 with the commented lines active
             const float cos_illum = dot(n, sun);
             illum = (float)(0.4 * (double)cos_illum);
             if (dot(n, sun) > 0) {
-                const Hit sh = cast_ray_ex<false, (RT_EX_SECONDARY_ASM & 1) != 0, true, ExStack, (RT_EX_SECONDARY_ASM & 1) != 0, false, false, (RT_EX_SECONDARY_ASM & 1) != 0>(
-                    p, hit.loc + sun * (float)1e-4, sun, stack, pops);
+                // (only hit-or-miss survives a shadow cast: no hit location to keep.  Octant loops at either cast of this
+                // kernel: within +-0.6 %, profiles/r04_experiments/octants_in_extension_kernels.log)
+                const Hit sh = cast_ray_ex<false, false, true, ExStack>(p, hit.loc + sun * (float)1e-4, sun, stack, pops);
                 if (sh.min == FLT_MAX) illum = (float)(1.0 * (double)cos_illum);
             }
         }
-#endif
         illum = fminf(1.0f, illum);                         // raycast.cu:289-290
         illum = fmaxf(0.4f, illum);
         const V3 local = v3(illum * base.x, illum * base.y, illum * base.z);
@@ -1783,9 +1588,8 @@ __global__ __launch_bounds__(kExBlock, (SIMPLE ? 8 : RT_EX_BOUNCE_WAVES)) void r
         return true;
     };
     auto step = [&](auto primary, const int depth) __attribute__((always_inline)) -> bool {
-        constexpr bool kPrimary = RT_EX_PRIMARY_ASM && VIEW && decltype(primary)::value;
-        constexpr bool kSec = (RT_EX_SECONDARY_ASM & 2) != 0 && !decltype(primary)::value;       // (a bounce ray)
-        Hit hit = cast_ray_ex<true, kPrimary || kSec, false, ExStack, kPrimary || kSec, kPrimary, kPrimary, kSec>(p, org, dir, stack, pops);
+        constexpr bool kPrimary = VIEW && decltype(primary)::value;
+        Hit hit = cast_ray_ex<true, kPrimary, false, ExStack, kPrimary, kPrimary, kPrimary>(p, org, dir, stack, pops);
         return after_cast(hit, depth);
     };
     if constexpr (PHASE == 2) {
@@ -1800,13 +1604,10 @@ __global__ __launch_bounds__(kExBlock, (SIMPLE ? 8 : RT_EX_BOUNCE_WAVES)) void r
         if (after_cast(hit, 0))
             for (int depth = 1; depth <= p.bounces; depth++) if (!step(std::false_type{}, depth)) break;
     } else {
-#if RT_EX_PEEL
     // the primary ray's depth written out: weight = 1 and sample = 0 are constants across its cast, not registers to keep
+    // (-0.7 % on c3, profiles/r05_experiments/ex_spill_variants.md)
     if (step(std::true_type{}, 0))
         for (int depth = 1; depth <= p.bounces; depth++) if (!step(std::false_type{}, depth)) break;
-#else
-    for (int depth = 0; depth <= p.bounces; depth++) if (!step(std::false_type{}, depth)) break;
-#endif
     }
     }
     }
@@ -4887,7 +4688,7 @@ static int launch_ex(RtScene* s, RenderParams& p, const RtRenderOptions* opts, i
         // (four LDS rows per lane hold a wave's samples for the in-wave sum, whatever the depth of the stack)
         const size_t lds = (size_t)std::max(lds_rows(p.stack_depth) + 1, 4) * kExBlock * sizeof(int);       // (+ the optimistic stack's spare row)
         // the samples-only kernel's rays all start at the camera: one view of the tree serves every sample of the frame
-        const int view_slot = (simple || RT_EX_PRIMARY_ASM) ? view_prepare(s, p, stream, p.spp) : -1;
+        const int view_slot = view_prepare(s, p, stream, p.spp);
         struct ViewDone {
             RtScene* s; int slot; hipStream_t stream;
             ~ViewDone() { view_done(s, slot, stream); }
@@ -5151,6 +4952,50 @@ int rt_unstripe(const uint8_t* d_gathered, size_t local_pitch, size_t rank_strid
     return rt_unstripe_batch(d_gathered, local_pitch, rank_stride, 0, d_img, pitch, 0, 1, width, height, stripe_rows, num_ranks, stream);
 }
 
+// ---- queries: what their entry points share --------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// the launch shape of a query kernel: one thread per query in workgroups of `block`, and the bytes of a workgroup's LDS stack block
+// (spare_rows: the optimistic stack's row, see StackT)
+struct QueryShape {
+    dim3 groups;
+    size_t lds;
+};
+QueryShape query_shape(int32_t n, int block, int stack_depth, int spare_rows = 0)
+{
+    return {dim3((unsigned)(((int64_t)n + block - 1) / block)), (size_t)(lds_rows(stack_depth) + spare_rows) * block * sizeof(int)};
+}
+
+// a query's params struct, zeroed, with the fields every one of them reads the scene through
+template <class P>
+P scene_params(const RtScene* s)
+{
+    P p;
+    memset(&p, 0, sizeof p);
+    p.records = s->d_records; p.leaf_count = s->d_leaf_count; p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
+    p.num_instances = (int32_t)s->instances.size();
+    p.stack_depth = s->max_stack;
+    return p;
+}
+
+// The part of a query call that touches the scene, after the argument checks and the n == 0 return (which take no lock): `launch`
+// enqueues on `stream` under the scene's call lock and returns RT_OK or the call's error; the lock is left BEFORE the stream is
+// waited for, so a synchronous call does not keep other threads' launches out while its own work runs.
+template <class F>
+int scene_launch(RtScene* s, void* stream, int synchronize, F&& launch)
+{
+    {
+        RT_SCENE_CALL(s);
+        const int rc = launch((hipStream_t)stream);
+        if (rc != RT_OK) return rc;
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
 // ---- ray queries ------------------------------------------------------------------------------------------------------------
 namespace {
 constexpr size_t kQueryBinsBytes = 256;                          // the workspace's counters (16 ints), then the permutation
@@ -5160,14 +5005,11 @@ int launch_query(RtScene* s, QueryParams& q, bool anyhit, void* d_workspace, siz
     if (!s || q.n < 0 || (q.n > 0 && (!q.org || !q.dir))) return RT_E_INVALID;
     if (d_workspace && workspace_bytes < rt_trace_workspace_bytes(q.n)) return RT_E_INVALID;
     if (q.n == 0) return RT_OK;                                  // nothing launched
-    const hipStream_t st = (hipStream_t)stream;
-    {
-        RT_SCENE_CALL(s);
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
         RenderParams p;
         memset(&p, 0, sizeof p);
         fill_scene(p, s);
         p.num_frames = 1;
-        const unsigned groups = (unsigned)(((int64_t)q.n + kQueryBlock - 1) / kQueryBlock);
         if (d_workspace) {
             q.bins = (int32_t*)d_workspace;
             int32_t* order = (int32_t*)((char*)d_workspace + kQueryBinsBytes);
@@ -5177,13 +5019,11 @@ int launch_query(RtScene* s, QueryParams& q, bool anyhit, void* d_workspace, siz
             hipLaunchKernelGGL(bin_scatter_kernel, dim3(chunks), dim3(kBinBlock), 0, st, q, order);
             q.order = order;
         }
-        const size_t lds = (size_t)(lds_rows(p.stack_depth) + 1) * kQueryBlock * sizeof(int);     // (+ the optimistic stack's spare row)
-        if (anyhit) hipLaunchKernelGGL(query_kernel<true>, dim3(groups), dim3(kQueryBlock), lds, st, p, q);
-        else hipLaunchKernelGGL(query_kernel<false>, dim3(groups), dim3(kQueryBlock), lds, st, p, q);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        const QueryShape k = query_shape(q.n, kQueryBlock, p.stack_depth, 1);     // (+ the optimistic stack's spare row)
+        if (anyhit) hipLaunchKernelGGL(query_kernel<true>, k.groups, dim3(kQueryBlock), k.lds, st, p, q);
+        else hipLaunchKernelGGL(query_kernel<false>, k.groups, dim3(kQueryBlock), k.lds, st, p, q);
+        return RT_OK;
+    });
 }
 }  // namespace
 
@@ -5214,6 +5054,7 @@ int rt_occluded(RtScene* s, const float* d_origins, const float* d_directions, c
     return launch_query(s, q, true, d_workspace, workspace_bytes, stream, synchronize);
 }
 
+// ---- point queries ----------------------------------------------------------------------------------------------------------
 int rt_closest_points(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, const RtPointHits* out, void* stream,
                       int synchronize)
 {
@@ -5221,44 +5062,26 @@ int rt_closest_points(RtScene* s, const float* d_points, const float* d_max_dist
     if (n > 0 && !(out->distance || out->instance || out->triangle || out->point || out->normal || out->barycentric || out->uv || out->pops))
         return RT_E_INVALID;
     if (n == 0) return RT_OK;                                    // nothing launched
-    const hipStream_t st = (hipStream_t)stream;
-    {
-        RT_SCENE_CALL(s);
-        PointParams p;
-        memset(&p, 0, sizeof p);
-        p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
-        p.leaf_count = s->d_leaf_count; p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
-        p.num_instances = (int32_t)s->instances.size();
-        p.stack_depth = s->max_stack;
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        PointParams p = scene_params<PointParams>(s);
+        p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
         p.pts = d_points; p.max_distance = d_max_distance; p.n = n;
         p.distance = out->distance; p.instance = out->instance; p.triangle = out->triangle;
         p.point = out->point; p.normal = out->normal; p.barycentric = out->barycentric; p.uv = out->uv; p.pops = out->pops;
-        const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
-        const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
-        hipLaunchKernelGGL(closest_point_kernel, dim3(groups), dim3(kPointBlock), lds, st, p);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        const QueryShape k = query_shape(n, kPointBlock, p.stack_depth);
+        hipLaunchKernelGGL(closest_point_kernel, k.groups, dim3(kPointBlock), k.lds, st, p);
+        return RT_OK;
+    });
 }
 
+// ---- crossings --------------------------------------------------------------------------------------------------------------
 extern "C++" {
 namespace {
-CrossParams crossing_params(const RtScene* s)
-{
-    CrossParams p;
-    memset(&p, 0, sizeof p);
-    p.records = s->d_records; p.leaf_count = s->d_leaf_count; p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
-    p.num_instances = (int32_t)s->instances.size();
-    p.stack_depth = s->max_stack;
-    return p;
-}
 template <bool POINT>
 void launch_crossings(const CrossParams& p, hipStream_t st)
 {
-    const unsigned groups = (unsigned)(((int64_t)p.n + kCrossBlock - 1) / kCrossBlock);
-    const size_t lds = (size_t)lds_rows(p.stack_depth) * kCrossBlock * sizeof(int);
-    hipLaunchKernelGGL(crossing_kernel<POINT>, dim3(groups), dim3(kCrossBlock), lds, st, p);
+    const QueryShape k = query_shape(p.n, kCrossBlock, p.stack_depth);
+    hipLaunchKernelGGL(crossing_kernel<POINT>, k.groups, dim3(kCrossBlock), k.lds, st, p);
 }
 }  // namespace
 }  // extern "C++"
@@ -5269,31 +5092,25 @@ int rt_count_crossings(RtScene* s, const float* d_origins, const float* d_direct
     if (!s || n < 0 || (n > 0 && (!d_origins || !d_directions || !out))) return RT_E_INVALID;
     if (n > 0 && !(out->count || out->winding || out->pops)) return RT_E_INVALID;
     if (n == 0) return RT_OK;                                    // nothing launched
-    {
-        RT_SCENE_CALL(s);
-        CrossParams p = crossing_params(s);
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        CrossParams p = scene_params<CrossParams>(s);
         p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n;
         p.count = out->count; p.winding = out->winding; p.pops = out->pops;
-        launch_crossings<false>(p, (hipStream_t)stream);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        launch_crossings<false>(p, st);
+        return RT_OK;
+    });
 }
 
 int rt_winding_numbers(RtScene* s, const float* d_points, int32_t n, int32_t* d_winding, void* stream, int synchronize)
 {
     if (!s || n < 0 || (n > 0 && (!d_points || !d_winding))) return RT_E_INVALID;
     if (n == 0) return RT_OK;
-    {
-        RT_SCENE_CALL(s);
-        CrossParams p = crossing_params(s);
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        CrossParams p = scene_params<CrossParams>(s);
         p.org = d_points; p.n = n; p.winding = d_winding;
-        launch_crossings<true>(p, (hipStream_t)stream);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        launch_crossings<true>(p, st);
+        return RT_OK;
+    });
 }
 
 int rt_signed_distance(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, float* d_sdf, int32_t* d_winding,
@@ -5301,28 +5118,27 @@ int rt_signed_distance(RtScene* s, const float* d_points, const float* d_max_dis
 {
     if (!s || n < 0 || (n > 0 && (!d_points || !d_sdf))) return RT_E_INVALID;
     if (n == 0) return RT_OK;
-    {
-        RT_SCENE_CALL(s);
+    // (both launches under one hold of the scene's lock: no other thread's update comes between the distance and its sign)
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
         RtPointHits hits;
         memset(&hits, 0, sizeof hits);
         hits.distance = d_sdf;                                   // the distance first, then negated in place where inside
         const int rc = rt_closest_points(s, d_points, d_max_distance, n, &hits, stream, 0);
         if (rc != RT_OK) return rc;
-        CrossParams p = crossing_params(s);
+        CrossParams p = scene_params<CrossParams>(s);
         p.org = d_points; p.n = n; p.winding = d_winding; p.sdf = d_sdf;
-        launch_crossings<true>(p, (hipStream_t)stream);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        launch_crossings<true>(p, st);
+        return RT_OK;
+    });
 }
 
+// ---- list queries: CSR offsets from a family's counts ----------------------------------------------------------------------
 extern "C++" {
 namespace {
-// rt_crossing_offsets' workspace: the counts (int32 [n]), then the block totals of each level of the scan over n + 1 elements
+// The *_offsets workspace: the counts (int32 [n]), then the block totals of each level of the scan over n + 1 elements
 constexpr size_t kScanAlign = 256;
 size_t scan_align(size_t b) { return (b + kScanAlign - 1) / kScanAlign * kScanAlign; }
-size_t crossing_offsets_bytes(int64_t n, int64_t* level_blocks, int* levels)
+size_t offsets_bytes(int64_t n, int64_t* level_blocks, int* levels)
 {
     size_t bytes = scan_align((size_t)n * sizeof(int32_t));
     int64_t m = n + 1;
@@ -5338,8 +5154,9 @@ size_t crossing_offsets_bytes(int64_t n, int64_t* level_blocks, int* levels)
     if (levels) *levels = l;
     return bytes;
 }
+size_t offsets_workspace_bytes(int32_t n) { return n > 0 ? offsets_bytes(n, nullptr, nullptr) : 0; }
 // the exclusive int64 scan of the counts at the workspace's start (int32 [n]) into d_offsets[0..n], the block totals of each level in
-// the rest of the workspace (crossing_offsets_bytes' layout): level 0 scans the counts, level l > 0 level l - 1's block totals in
+// the rest of the workspace (offsets_bytes' layout): level 0 scans the counts, level l > 0 level l - 1's block totals in
 // place, then each block of level l - 1 adds its scanned total on the way down
 void scan_offsets(void* d_workspace, int32_t n, int64_t* d_offsets, const int64_t* blocks, int levels, hipStream_t st)
 {
@@ -5356,33 +5173,36 @@ void scan_offsets(void* d_workspace, int32_t n, int64_t* d_offsets, const int64_
         hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)blocks[l - 1]), dim3(kScanThreads), 0, st, l >= 2 ? sums[l - 2] : d_offsets,
                            l >= 2 ? blocks[l - 2] : (int64_t)n + 1, sums[l - 1]);
 }
+// The *_offsets call of a list query, once its own pointers are checked and n > 0: `launch_counts(counts, stream)` runs the family's
+// count kernel into the workspace's start, the scan turns the counts into d_offsets[0..n].
+template <class F>
+int query_offsets(RtScene* s, int32_t n, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream, int synchronize,
+                  F&& launch_counts)
+{
+    int64_t blocks[8];
+    int levels = 0;
+    if (workspace_bytes < offsets_bytes(n, blocks, &levels)) return RT_E_INVALID;
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        launch_counts((int32_t*)d_workspace, st);
+        scan_offsets(d_workspace, n, d_offsets, blocks, levels, st);
+        return RT_OK;
+    });
+}
 }  // namespace
 }  // extern "C++"
 
-size_t rt_crossing_offsets_workspace_bytes(int32_t n)
-{
-    return n > 0 ? crossing_offsets_bytes(n, nullptr, nullptr) : 0;
-}
+size_t rt_crossing_offsets_workspace_bytes(int32_t n) { return offsets_workspace_bytes(n); }
 
 int rt_crossing_offsets(RtScene* s, const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, int64_t* d_offsets,
                         void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
 {
     if (!s || n < 0 || (n > 0 && (!d_origins || !d_directions || !d_offsets || !d_workspace))) return RT_E_INVALID;
     if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
-    int64_t blocks[8];
-    int levels = 0;
-    if (workspace_bytes < crossing_offsets_bytes(n, blocks, &levels)) return RT_E_INVALID;
-    {
-        RT_SCENE_CALL(s);
-        const hipStream_t st = (hipStream_t)stream;
-        CrossParams p = crossing_params(s);
-        p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n; p.count = (int32_t*)d_workspace;
+    return query_offsets(s, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize, [&](int32_t* counts, hipStream_t st) {
+        CrossParams p = scene_params<CrossParams>(s);
+        p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n; p.count = counts;
         launch_crossings<false>(p, st);
-        scan_offsets(d_workspace, n, d_offsets, blocks, levels, st);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+    });
 }
 
 int rt_list_crossings(RtScene* s, const float* d_origins, const float* d_directions, const float* d_tmax, int32_t n, const int64_t* d_offsets,
@@ -5393,72 +5213,48 @@ int rt_list_crossings(RtScene* s, const float* d_origins, const float* d_directi
     if (n > 0 && !(out->t || out->instance || out->triangle || out->sign || out->barycentric || out->uv || out->point || out->count))
         return RT_E_INVALID;
     if (n == 0) return RT_OK;
-    {
-        RT_SCENE_CALL(s);
-        CrossListParams p;
-        memset(&p, 0, sizeof p);
-        p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id; p.leaf_count = s->d_leaf_count;
-        p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
-        p.num_instances = (int32_t)s->instances.size();
-        p.stack_depth = s->max_stack;
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        CrossListParams p = scene_params<CrossListParams>(s);
+        p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
         p.org = d_origins; p.dir = d_directions; p.tmax = d_tmax; p.n = n;
         p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
         p.t = out->t; p.instance = out->instance; p.triangle = out->triangle; p.sign = out->sign;
         p.barycentric = out->barycentric; p.uv = out->uv; p.point = out->point; p.count = out->count;
-        const unsigned groups = (unsigned)(((int64_t)n + kCrossBlock - 1) / kCrossBlock);
-        const size_t lds = (size_t)lds_rows(p.stack_depth) * kCrossBlock * sizeof(int);
+        const QueryShape k = query_shape(n, kCrossBlock, p.stack_depth);
         if (p.t && p.instance && p.triangle)                    // the room holds the keys: insertion
-            hipLaunchKernelGGL(crossing_list_kernel<false>, dim3(groups), dim3(kCrossBlock), lds, (hipStream_t)stream, p);
+            hipLaunchKernelGGL(crossing_list_kernel<false>, k.groups, dim3(kCrossBlock), k.lds, st, p);
         else
-            hipLaunchKernelGGL(crossing_list_kernel<true>, dim3(groups), dim3(kCrossBlock), lds, (hipStream_t)stream, p);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+            hipLaunchKernelGGL(crossing_list_kernel<true>, k.groups, dim3(kCrossBlock), k.lds, st, p);
+        return RT_OK;
+    });
 }
 
+// ---- nearby triangles -------------------------------------------------------------------------------------------------------
 extern "C++" {
 namespace {
 NearbyParams nearby_params(const RtScene* s, const float* d_points, const float* d_max_distance, int32_t n)
 {
-    NearbyParams p;
-    memset(&p, 0, sizeof p);
-    p.records = s->d_records; p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id; p.leaf_count = s->d_leaf_count;
-    p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
-    p.num_instances = (int32_t)s->instances.size();
-    p.stack_depth = s->max_stack;
+    NearbyParams p = scene_params<NearbyParams>(s);
+    p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
     p.pts = d_points; p.max_distance = d_max_distance; p.n = n;
     return p;
 }
 }  // namespace
 }  // extern "C++"
 
-size_t rt_nearby_offsets_workspace_bytes(int32_t n)
-{
-    return n > 0 ? crossing_offsets_bytes(n, nullptr, nullptr) : 0;
-}
+size_t rt_nearby_offsets_workspace_bytes(int32_t n) { return offsets_workspace_bytes(n); }
 
 int rt_nearby_offsets(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, int64_t* d_offsets, void* d_workspace,
                       size_t workspace_bytes, void* stream, int synchronize)
 {
     if (!s || n < 0 || (n > 0 && (!d_points || !d_offsets || !d_workspace))) return RT_E_INVALID;
     if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
-    int64_t blocks[8];
-    int levels = 0;
-    if (workspace_bytes < crossing_offsets_bytes(n, blocks, &levels)) return RT_E_INVALID;
-    {
-        RT_SCENE_CALL(s);
-        const hipStream_t st = (hipStream_t)stream;
+    return query_offsets(s, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize, [&](int32_t* counts, hipStream_t st) {
         NearbyParams p = nearby_params(s, d_points, d_max_distance, n);
-        p.count = (int32_t*)d_workspace;
-        const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
-        const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
-        hipLaunchKernelGGL(nearby_count_kernel, dim3(groups), dim3(kPointBlock), lds, st, p);
-        scan_offsets(d_workspace, n, d_offsets, blocks, levels, st);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        p.count = counts;
+        const QueryShape k = query_shape(n, kPointBlock, p.stack_depth);
+        hipLaunchKernelGGL(nearby_count_kernel, k.groups, dim3(kPointBlock), k.lds, st, p);
+    });
 }
 
 int rt_list_nearby(RtScene* s, const float* d_points, const float* d_max_distance, int32_t n, const int64_t* d_offsets, int32_t max_hits,
@@ -5468,43 +5264,35 @@ int rt_list_nearby(RtScene* s, const float* d_points, const float* d_max_distanc
     if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
     if (n > 0 && !(out->distance && out->instance && out->triangle)) return RT_E_INVALID;     // the room holds the keys
     if (n == 0) return RT_OK;
-    {
-        RT_SCENE_CALL(s);
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
         NearbyParams p = nearby_params(s, d_points, d_max_distance, n);
         p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
         p.distance = out->distance; p.instance = out->instance; p.triangle = out->triangle;
         p.point = out->point; p.normal = out->normal; p.barycentric = out->barycentric; p.uv = out->uv;
         p.count = out->count; p.pops = out->pops;
-        const unsigned groups = (unsigned)(((int64_t)n + kPointBlock - 1) / kPointBlock);
-        const size_t lds = (size_t)lds_rows(p.stack_depth) * kPointBlock * sizeof(int);
-        hipLaunchKernelGGL(nearby_list_kernel, dim3(groups), dim3(kPointBlock), lds, (hipStream_t)stream, p);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        const QueryShape k = query_shape(n, kPointBlock, p.stack_depth);
+        hipLaunchKernelGGL(nearby_list_kernel, k.groups, dim3(kPointBlock), k.lds, st, p);
+        return RT_OK;
+    });
 }
 
+// ---- intersecting triangles -------------------------------------------------------------------------------------------------
 extern "C++" {
 namespace {
 TriParams intersect_params(const RtScene* s, const float* d_triangles, const int32_t* d_skip_instance, int32_t n)
 {
-    TriParams p;
-    memset(&p, 0, sizeof p);
-    p.records = s->d_records; p.tri_id = s->d_tri_id; p.leaf_count = s->d_leaf_count;
-    p.mesh_flags = s->d_mesh_flags; p.instances = s->d_instances;
-    p.num_instances = (int32_t)s->instances.size();
-    p.stack_depth = s->max_stack;
+    TriParams p = scene_params<TriParams>(s);
+    p.tri_id = s->d_tri_id;
     p.tris = d_triangles; p.skip = d_skip_instance; p.n = n;
     return p;
 }
 void launch_intersect_count(const TriParams& p, bool any_only, hipStream_t st)
 {
-    const unsigned groups = (unsigned)(((int64_t)p.n + kTriBlock - 1) / kTriBlock);
-    const size_t lds = (size_t)lds_rows(p.stack_depth) * kTriBlock * sizeof(int);
+    const QueryShape k = query_shape(p.n, kTriBlock, p.stack_depth);
     if (any_only)
-        hipLaunchKernelGGL(intersect_count_kernel<true>, dim3(groups), dim3(kTriBlock), lds, st, p);
+        hipLaunchKernelGGL(intersect_count_kernel<true>, k.groups, dim3(kTriBlock), k.lds, st, p);
     else
-        hipLaunchKernelGGL(intersect_count_kernel<false>, dim3(groups), dim3(kTriBlock), lds, st, p);
+        hipLaunchKernelGGL(intersect_count_kernel<false>, k.groups, dim3(kTriBlock), k.lds, st, p);
 }
 }  // namespace
 }  // extern "C++"
@@ -5515,41 +5303,26 @@ int rt_count_intersecting(RtScene* s, const float* d_triangles, const int32_t* d
     if (!s || n < 0 || (n > 0 && (!d_triangles || !out))) return RT_E_INVALID;
     if (n > 0 && !(out->count || out->any || out->pops)) return RT_E_INVALID;
     if (n == 0) return RT_OK;                                    // nothing launched
-    {
-        RT_SCENE_CALL(s);
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
         TriParams p = intersect_params(s, d_triangles, d_skip_instance, n);
         p.count = out->count; p.any = out->any; p.pops = out->pops;
-        launch_intersect_count(p, p.any && !p.count, (hipStream_t)stream);     // (any without count: stop at the first pair)
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        launch_intersect_count(p, p.any && !p.count, st);       // (any without count: stop at the first pair)
+        return RT_OK;
+    });
 }
 
-size_t rt_intersecting_offsets_workspace_bytes(int32_t n)
-{
-    return n > 0 ? crossing_offsets_bytes(n, nullptr, nullptr) : 0;
-}
+size_t rt_intersecting_offsets_workspace_bytes(int32_t n) { return offsets_workspace_bytes(n); }
 
 int rt_intersecting_offsets(RtScene* s, const float* d_triangles, const int32_t* d_skip_instance, int32_t n, int64_t* d_offsets,
                             void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
 {
     if (!s || n < 0 || (n > 0 && (!d_triangles || !d_offsets || !d_workspace))) return RT_E_INVALID;
     if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
-    int64_t blocks[8];
-    int levels = 0;
-    if (workspace_bytes < crossing_offsets_bytes(n, blocks, &levels)) return RT_E_INVALID;
-    {
-        RT_SCENE_CALL(s);
-        const hipStream_t st = (hipStream_t)stream;
+    return query_offsets(s, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize, [&](int32_t* counts, hipStream_t st) {
         TriParams p = intersect_params(s, d_triangles, d_skip_instance, n);
-        p.count = (int32_t*)d_workspace;
+        p.count = counts;
         launch_intersect_count(p, false, st);
-        scan_offsets(d_workspace, n, d_offsets, blocks, levels, st);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+    });
 }
 
 int rt_list_intersecting(RtScene* s, const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const int64_t* d_offsets,
@@ -5559,19 +5332,15 @@ int rt_list_intersecting(RtScene* s, const float* d_triangles, const int32_t* d_
     if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
     if (n > 0 && !(out->instance && out->triangle)) return RT_E_INVALID;     // the room holds the keys
     if (n == 0) return RT_OK;
-    {
-        RT_SCENE_CALL(s);
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
         TriParams p = intersect_params(s, d_triangles, d_skip_instance, n);
         p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
         p.instance = out->instance; p.triangle = out->triangle; p.normal = out->normal; p.segment = out->segment;
         p.count = out->count; p.pops = out->pops;
-        const unsigned groups = (unsigned)(((int64_t)n + kTriBlock - 1) / kTriBlock);
-        const size_t lds = (size_t)lds_rows(p.stack_depth) * kTriBlock * sizeof(int);
-        hipLaunchKernelGGL(intersect_list_kernel, dim3(groups), dim3(kTriBlock), lds, (hipStream_t)stream, p);
-        RT_HIP(hipGetLastError());
-    }
-    RT_WAIT_IF(synchronize, stream);
-    return RT_OK;
+        const QueryShape k = query_shape(n, kTriBlock, p.stack_depth);
+        hipLaunchKernelGGL(intersect_list_kernel, k.groups, dim3(kTriBlock), k.lds, st, p);
+        return RT_OK;
+    });
 }
 
 int rt_camera_rays(const RtCameraParams* cam, float* d_origins, float* d_directions, void* stream, int synchronize)
