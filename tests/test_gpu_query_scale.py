@@ -1,0 +1,436 @@
+"""What the query families share, at the sizes where it can go wrong (the arithmetic of each family is test_gpu_crossing_list.py's,
+test_gpu_nearby.py's and test_gpu_tri_intersect.py's business): the CSR scan behind the three *_offsets calls at its block edges and on
+its three-level path, totals and room positions past 2^31 and 2^32, and every query kernel with a partly filled last workgroup on the
+deep scene.  The C-ABI is called directly on torch buffers: the Python wrappers would allocate `total` rows.
+
+Every offsets check compares with np.concatenate([[0], np.cumsum(counts)]) of the CPU shims' counts (crossing_oracle, nearby_oracle,
+tri_intersect_oracle), never with the library's own counts.  Every buffer a kernel may write is allocated at its full size; the large
+cases read back small windows only."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import crossing_list_oracle as xl
+import crossing_oracle as xo
+import nearby_oracle as nb
+import point_oracle
+import query_points as qp
+import ray_oracle
+import scene_defs as sd
+import tri_intersect_oracle as ti
+from test_crossing_host import _cube
+from test_gpu_crossings import _eq, _product
+from test_gpu_tri_intersect import families as tri_families
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+SCAN_BLOCK = 1024                                               # elements per block of the scan over n + 1 offsets (kScanBlock)
+GUARD = 0x5A
+GUARD64 = int.from_bytes(bytes([GUARD]) * 8, "little")
+FAMILIES = ("crossing", "nearby", "intersecting")
+
+
+def _cumsum(counts):
+    return np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+
+
+def _block_totals(counts):
+    """the totals of the scan's level-0 blocks: n + 1 elements (the last one 0) in blocks of SCAN_BLOCK"""
+    c = np.append(counts.astype(np.int64), 0)
+    c = np.concatenate([c, np.zeros((-len(c)) % SCAN_BLOCK, np.int64)])
+    return c.reshape(-1, SCAN_BLOCK).sum(axis=1)
+
+
+def _ws_bytes(h, family, n):
+    return int(getattr(h, "rt_%s_offsets_workspace_bytes" % family)(n))
+
+
+def _call_offsets(h, family, handle, q, n, off, ws, ws_bytes):
+    """rt_<family>_offsets on device pointers, synchronous on the NULL stream; q: the family's two query arrays (the second may be
+    None)"""
+    a, b = q[0].data_ptr(), None if q[1] is None else q[1].data_ptr()
+    if family == "crossing":
+        return h.rt_crossing_offsets(handle, a, b, None, n, off, ws, ws_bytes, None, 1)
+    if family == "nearby":
+        return h.rt_nearby_offsets(handle, a, b, n, off, ws, ws_bytes, None, 1)
+    return h.rt_intersecting_offsets(handle, a, b, n, off, ws, ws_bytes, None, 1)
+
+
+def _up(arrays):
+    import torch
+    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+class _Offsets:
+    """Guarded buffers for one n: offsets int64 [n + 1] with 8 guard words behind, the workspace with 256 guard bytes behind"""
+
+    def __init__(self, h, family, n):
+        import torch
+        self.h, self.family, self.n = h, family, n
+        self.ws_bytes = _ws_bytes(h, family, n)
+        self.off = torch.full((n + 1 + 8,), GUARD64, dtype=torch.int64, device="cuda")
+        self.ws = torch.full((self.ws_bytes + 256,), GUARD, dtype=torch.uint8, device="cuda")
+
+    def run(self, handle, q, where):
+        """one call -> the offsets [n + 1]; the guards behind the offsets and behind the workspace are checked"""
+        import torch
+        torch.cuda.synchronize()
+        rc = _call_offsets(self.h, self.family, handle, q, self.n, self.off.data_ptr(), self.ws.data_ptr(), self.ws_bytes)
+        assert rc == 0, (where, rc)
+        got = self.off.cpu().numpy()
+        assert (got[self.n + 1:] == GUARD64).all(), "%s: the words behind offsets[n] were written: %s" % (where, got[self.n + 1:])
+        tail = self.ws[self.ws_bytes:].cpu().numpy()
+        assert (tail == GUARD).all(), "%s: %d bytes behind the workspace were written" % (where, int((tail != GUARD).sum()))
+        return got[:self.n + 1]
+
+
+def _same_offsets(got, ref, where):
+    bad = np.flatnonzero(got != ref)
+    assert bad.size == 0, "%s: %d of %d offsets differ, first at %d (block %d): got %s want %s" % (
+        where, bad.size, len(ref), bad[0], bad[0] // SCAN_BLOCK, got[bad[:3]], ref[bad[:3]])
+
+
+# ---- scenes, uploaded once per module ----------------------------------------------------------------------------------------
+class _Pair:
+    def __init__(self, rt, orc, desc):
+        self.desc = desc
+        self.so = desc.build_oracle(orc)
+        self.sp = _product(rt, desc)
+        self.handle = self.sp.device_handle
+
+    def close(self):
+        self.sp.close()
+        self.so.close()
+
+
+@pytest.fixture(scope="module")
+def multi(rt, orc, scenes, blob5k):
+    p = _Pair(rt, orc, sd.multi_instance_scene(scenes, blob5k))
+    yield p
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def cube(rt, orc):
+    p = _Pair(rt, orc, sd.SceneDesc([((1.0, 1.0, 1.0), None)], [("tris", _cube(orc))], [(0, 0, (0.0,) * 6, (1.0, 1.0, 1.0))]))
+    yield p
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def deep(rt, orc):
+    p = _Pair(rt, orc, sd.deep_stack_scene(28))
+    yield p
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def stack(rt, orc):
+    """test_gpu_crossing_list.test_thousand_crossings_sorted's 1200 parallel quads (2400 triangles, in shuffled order), as two
+    coincident instances: a ray along z crosses one triangle of every quad of both, about 2400 crossings"""
+    o_ = orc.oracle()
+    rng = np.random.default_rng(3)
+    zs = rng.permutation(1200).astype(F32) * F32(0.01)
+    tris = []
+    for z in zs:
+        for f in ((0, 1, 2), (0, 2, 3)):
+            v = np.array([(0, 0, z), (1, 0, z), (1, 1, z), (0, 1, z)], F32)[list(f)]
+            tris.append(np.asarray(o_.tri_from_vertices(v.ravel()), F32))
+    inst = (0, 0, (0.0,) * 6, (1.0, 1.0, 1.0))
+    p = _Pair(rt, orc, sd.SceneDesc([((1.0, 1.0, 1.0), None)], [("tris", np.stack(tris))], [inst, inst]))
+    yield p
+    p.close()
+
+
+# ---- B1: the scan's block edges ------------------------------------------------------------------------------------------------
+POOL = 2049
+
+
+@pytest.fixture(scope="module")
+def pools(orc, multi):
+    """Per family: POOL queries on the multi-instance scene (hits and misses mixed) with the shim's counts, computed once, and the
+    indices of the queries with a count above 0"""
+    rng = np.random.default_rng(41)
+    o = rng.uniform(-1.5, 1.5, (POOL, 3)).astype(F32)
+    d = rng.normal(size=(POOL, 3)).astype(F32)
+    pts = rng.uniform(-1.5, 1.5, (POOL, 3)).astype(F32)
+    md = rng.uniform(0.02, 0.3, POOL).astype(F32)
+    tris = np.concatenate([f[1] for f in tri_families(rng, orc.oracle(), multi.desc, n=400)])
+    tris = np.ascontiguousarray(tris[rng.permutation(len(tris))[:POOL]], F32)
+    assert len(tris) == POOL
+    out = {"crossing": ((o, d), xo.count_crossings(multi.so, o, d)["count"]),
+           "nearby": ((pts, md), nb.count_nearby(multi.so, pts, md)),
+           "intersecting": ((tris, None), ti.count_intersecting(multi.so, tris))}
+    for family, (_q, c) in out.items():
+        assert (c > 0).sum() >= 16 and (c == 0).sum() >= 16, (family, int((c > 0).sum()))
+    return out
+
+
+def _prefix(pool, n):
+    """The first n queries of a pool with the last min(n, 3) replaced by queries whose count is above 0 -> (queries, counts).  The
+    last counted element of the scan, and with it the last block that holds counts, is then never empty."""
+    q, c = pool
+    idx = np.arange(n)
+    hits = np.flatnonzero(c > 0)
+    k = min(n, 3)
+    idx[n - k:] = hits[-k:]
+    return tuple(None if a is None else np.ascontiguousarray(a[idx]) for a in q), c[idx]
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049])
+@pytest.mark.parametrize("family", FAMILIES)
+def test_offsets_at_scan_block_edges(rt, multi, pools, family, n):
+    """d_offsets[0..n] is the cumulative sum of the shim's counts with n + 1 below, at and above one and two scan blocks (and the
+    query kernels' workgroup of 64); nothing behind offsets[n] or behind the workspace is written; a second call with the queries
+    in reverse order into the SAME buffers, not cleared, gives that order's cumulative sum (no dependence on prior contents)."""
+    h = rt.libs()[0]
+    q, counts = _prefix(pools[family], n)
+    ref = _cumsum(counts)
+    last = (n - 1) // SCAN_BLOCK * SCAN_BLOCK                  # the last scan block that holds a count
+    assert counts[-1] > 0 and counts[last:].sum() > 0 and ref[-1] > ref[last]
+    buf = _Offsets(h, family, n)
+    got = buf.run(multi.handle, _up(q), "%s n=%d" % (family, n))
+    _same_offsets(got, ref, "%s n=%d" % (family, n))
+    rq = tuple(None if a is None else a[::-1].copy() for a in q)
+    got = buf.run(multi.handle, _up(rq), "%s n=%d again" % (family, n))
+    _same_offsets(got, _cumsum(counts[::-1]), "%s n=%d, buffers reused" % (family, n))
+
+
+# ---- B2: the three-level scan --------------------------------------------------------------------------------------------------
+DISTINCT = 4096
+
+
+@pytest.fixture(scope="module")
+def cube_queries(cube):
+    """DISTINCT distinct queries per family around the unit cube, hits and misses mixed without a period, and the shim's counts"""
+    rng = np.random.default_rng(43)
+    u = rng.normal(size=(DISTINCT, 3))
+    o = (0.5 + 3.0 * u / np.linalg.norm(u, axis=1, keepdims=True)).astype(F32)
+    aim = rng.uniform(-0.6, 1.6, (DISTINCT, 3))
+    d = (aim - o).astype(F32)
+    pts = rng.uniform(-0.5, 1.5, (DISTINCT, 3)).astype(F32)
+    md = rng.uniform(0.05, 0.5, DISTINCT).astype(F32)
+    cen = rng.uniform(-0.3, 1.3, (DISTINCT, 1, 3))
+    tris = np.ascontiguousarray(cen + rng.normal(size=(DISTINCT, 3, 3)) * 0.15, F32)
+    return {"crossing": ((o, d), xo.count_crossings(cube.so, o, d)["count"]),
+            "nearby": ((pts, md), nb.count_nearby(cube.so, pts, md)),
+            "intersecting": ((tris, None), ti.count_intersecting(cube.so, tris))}
+
+
+def _tiled(pool, n):
+    q, c = pool
+    return tuple(None if a is None else np.resize(a, (n,) + a.shape[1:]) for a in q), np.resize(c, n)
+
+
+def _three_levels(rt, cube, cube_queries, family, n):
+    h = rt.libs()[0]
+    q, counts = _tiled(cube_queries[family], n)
+    c0 = cube_queries[family][1]
+    assert n + 1 > SCAN_BLOCK ** 2                              # three levels: more than 1024 level-0 blocks
+    assert (c0 > 0).sum() > DISTINCT // 8 and (c0 == 0).sum() > DISTINCT // 8, family
+    assert not any(np.array_equal(c0[:SCAN_BLOCK], c0[k * SCAN_BLOCK:(k + 1) * SCAN_BLOCK]) for k in (1, 2, 3)), "period 1024"
+    totals = _block_totals(counts)
+    assert len(np.unique(totals[:-1])) >= 2 and len(totals) > SCAN_BLOCK, (family, np.unique(totals))
+    ref = _cumsum(counts)
+    got = _Offsets(h, family, n).run(cube.handle, _up(q), "%s n=%d" % (family, n))
+    _same_offsets(got, ref, "%s n=%d" % (family, n))
+
+
+@pytest.mark.parametrize("n", [2 ** 20 - 1, 2 ** 20, 2 ** 20 + 1, 2 ** 20 + 1025])
+def test_three_level_scan_crossing(rt, cube, cube_queries, n):
+    """rt_crossing_offsets just below the three-level threshold (n + 1 = 2^20: the widest two-level scan), at 1025 level-0 blocks,
+    at 1025 blocks plus one element and at 1026 blocks plus an element: the whole offsets array equals the cumulative sum of the
+    shim's counts of 4096 distinct rays, tiled.  The level-0 block totals differ from block to block, so totals added to the wrong
+    block, or into the wrong level's array, change offsets."""
+    if n + 1 > SCAN_BLOCK ** 2:
+        _three_levels(rt, cube, cube_queries, "crossing", n)
+        return
+    h = rt.libs()[0]
+    q, counts = _tiled(cube_queries["crossing"], n)
+    assert len(_block_totals(counts)) == SCAN_BLOCK
+    got = _Offsets(h, "crossing", n).run(cube.handle, _up(q), "crossing n=%d" % n)
+    _same_offsets(got, _cumsum(counts), "crossing n=%d" % n)
+
+
+@pytest.mark.parametrize("family", ["nearby", "intersecting"])
+def test_three_level_scan_other_families(rt, cube, cube_queries, family):
+    """The same at n = 2^20 + 1 through rt_nearby_offsets and rt_intersecting_offsets: one scan, but each family's own count launch"""
+    _three_levels(rt, cube, cube_queries, family, 2 ** 20 + 1)
+
+
+# ---- B3: totals beyond 2^31 and 2^32 -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,lo,hi", [(2 ** 20 + 1, 2 ** 31, 2 ** 32), (1850000, 2 ** 32, 2 ** 33)])
+def test_totals_beyond_32_bits(rt, stack, n, lo, hi):
+    """rt_crossing_offsets on the quad stack, 64 distinct rays of about 2400 crossings each, tiled: with n = 2^20 + 1 the total lies
+    between 2^31 and 2^32 (a signed 32-bit intermediate anywhere in the scan shows), with n = 1.85 M above 2^32 (an unsigned one
+    shows).  All offsets are compared.  The stack is instanced twice because one instance gives 1200 crossings per ray, and the
+    total at n = 2^20 + 1 would stay below 2^31.  The count kernel does the work of `total` crossings, 2.5 and 4.4 G here; on an
+    MI355X each case takes 0.06 s, upload and read-back of the offsets included, so both stay in the suite as they are."""
+    h = rt.libs()[0]
+    rng = np.random.default_rng(3)
+    o = np.concatenate([rng.uniform(0.2, 0.8, (64, 2)), np.full((64, 1), -1.0)], axis=1).astype(F32)
+    d = np.concatenate([rng.uniform(-0.01, 0.01, (64, 2)), np.ones((64, 1))], axis=1).astype(F32)
+    c64 = xo.count_crossings(stack.so, o, d)["count"]
+    assert (c64 >= 2400).all() and (c64 <= 2 * 2400).all(), c64
+    counts = np.resize(c64, n)
+    ref = _cumsum(counts)
+    assert lo < ref[-1] < hi, (int(ref[-1]), lo, hi)
+    got = _Offsets(h, "crossing", n).run(stack.handle, _up((np.resize(o, (n, 3)), np.resize(d, (n, 3)))), "quad stack n=%d" % n)
+    _same_offsets(got, ref, "quad stack n=%d (total %d)" % (n, ref[-1]))
+
+
+# ---- B4: room positions beyond 2^31 and 2^32 in the list kernel -----------------------------------------------------------------
+def _need_memory(nbytes):
+    import torch
+    free, total = torch.cuda.mem_get_info()
+    if free < 2 * nbytes:
+        pytest.skip("needs %d bytes of device memory twice over, %d of %d free" % (nbytes, free, total))
+
+
+def _list_sign_only(rt, handle, q, n, offsets_ptr, max_hits, sign_ptr):
+    """rt_list_crossings with the sign field alone (no key field: the selection path), synchronous on the NULL stream"""
+    import torch
+    lst = rt.RtCrossingList(sign=sign_ptr)
+    torch.cuda.synchronize()
+    return rt.libs()[0].rt_list_crossings(handle, q[0].data_ptr(), q[1].data_ptr(), None, n, offsets_ptr, max_hits, C.byref(lst), None, 1)
+
+
+@pytest.mark.parametrize("base", [2 ** 31 + 5, 2 ** 32 + 5])
+def test_csr_rooms_beyond_32_bits(rt, cube, cube_queries, base):
+    """400 rays on the cube with hand-made offsets base + cumsum(room), rooms below, at and above each count: the int8 sign rooms land
+    at byte `base` and beyond of a buffer that large and equal the shim's; the guard bytes 64 either side of them and in the first
+    4096 bytes of the buffer (where a start cut to 32 bits would land) are untouched.  Only those windows are ever written by the
+    test or read back."""
+    import torch
+    rng = np.random.default_rng(47)
+    (o, d), c = cube_queries["crossing"]
+    o, d, c = o[:400], d[:400], c[:400].astype(np.int64)
+    room = np.maximum(c + rng.integers(-1, 3, 400), 0)
+    assert (room < c).any() and (room > c).any() and (room == 0).any() and (c > 0).sum() > 50
+    rooms = int(room.sum())
+    assert rooms + 5 + 64 <= 4096                               # (offsets mod 2^32 fall inside the head window)
+    offsets = (base + _cumsum(room)).astype(np.int64)
+    nbytes = base + rooms + 64
+    _need_memory(nbytes)
+    lo, hi = base - 64, base + rooms + 64
+    ref = xl.rooms(cube.so, o, d, offsets=offsets - lo, slots=hi - lo, fill=dict(sign=GUARD))
+    buf = None
+    try:
+        buf = torch.empty(nbytes, dtype=torch.int8, device="cuda")
+        buf[lo:hi].fill_(GUARD)
+        buf[:4096].fill_(GUARD)
+        q = _up((o, d))
+        doff = torch.from_numpy(offsets).cuda()
+        assert _list_sign_only(rt, cube.handle, q, 400, doff.data_ptr(), 0, buf.data_ptr()) == 0
+        window, head = buf[lo:hi].cpu().numpy(), buf[:4096].cpu().numpy()
+        assert (head == GUARD).all(), "%d of the buffer's first 4096 bytes were written" % int((head != GUARD).sum())
+        _eq(window, ref["sign"], "sign rooms at byte %d" % base)
+        assert set(np.unique(window[64:64 + rooms])) == {-1, 0, 1}
+    finally:
+        del buf
+        torch.cuda.empty_cache()
+
+
+def test_fixed_rooms_beyond_31_bits(rt, cube):
+    """max_hits = 2049 and n = 2^20 + 64: the int8 sign rooms of the last 64 rays, the only ones that hit the cube, start beyond byte
+    2^31 and equal the shim's fixed rooms; the rooms of a sample of the other rays (the first, the last, and those around byte 2^31)
+    are all padding."""
+    import torch
+    K, n = 2049, 2 ** 20 + 64
+    rng = np.random.default_rng(53)
+    o = np.full((n, 3), 50.0, F32)                              # far off, pointing away: no crossing
+    d = np.tile(np.array([[1.0, 0.5, 0.25]], F32), (n, 1))
+    o[-64:] = np.concatenate([np.full((64, 1), -1.0), rng.uniform(0.1, 0.9, (64, 2))], axis=1).astype(F32)
+    d[-64:] = np.concatenate([np.ones((64, 1)), rng.uniform(-0.05, 0.05, (64, 2))], axis=1).astype(F32)
+    ref = xl.rooms(cube.so, o[-64:], d[-64:], max_hits=K)
+    assert (ref["count"] == 2).all() and (n - 64) * K > 2 ** 31
+    assert (xo.count_crossings(cube.so, o[:64], d[:64])["count"] == 0).all()
+    nbytes = n * K
+    _need_memory(nbytes)
+    buf = None
+    try:
+        buf = torch.empty(nbytes, dtype=torch.int8, device="cuda")
+        sample = sorted({0, 1, 63, 64, 2 ** 19, 2 ** 31 // K - 1, 2 ** 31 // K, 2 ** 31 // K + 1, n - 66, n - 65})
+        for i in sample:
+            buf[i * K:(i + 1) * K].fill_(GUARD)
+        buf[(n - 64) * K:].fill_(GUARD)
+        assert _list_sign_only(rt, cube.handle, _up((o, d)), n, None, K, buf.data_ptr()) == 0
+        last = buf[(n - 64) * K:].cpu().numpy()
+        _eq(last, ref["sign"], "the last 64 rooms")
+        assert (np.abs(last.reshape(64, K)[:, :2]) == 1).all()
+        for i in sample:
+            room = buf[i * K:(i + 1) * K].cpu().numpy()
+            assert (room == 0).all(), "room %d (a ray without crossings): %d bytes are not padding" % (i, int((room != 0).sum()))
+    finally:
+        del buf
+        torch.cuda.empty_cache()
+
+
+# ---- B5: a partly filled last workgroup on the deep scene -------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def deep_queries(orc, scenes, deep):
+    """Pools of rays, points (with finite radii) and triangles on the 28-level chain, each with a measure of how deep its traversal
+    goes: the test oracle's node pops of the ray itself, or of the ray from the camera through the point / the triangle's centroid
+    (the brute-force shims of the point and triangle families have no traversal to count)"""
+    rng = np.random.default_rng(59)
+    cam = np.array([0.0, -1.0, 0.0], F32)
+    co, cd = ray_oracle.camera_rays(96, 64, scenes.scaled_K(96), scenes.D_REF, (0.0, -1.0, 0.0, 0.0, 0.0, 0.0))
+    co, cd = np.ascontiguousarray(co.reshape(-1, 3)), np.ascontiguousarray(cd.reshape(-1, 3))
+    pick = rng.choice(len(co), 1500, replace=False)
+    ro, rd = np.ascontiguousarray(co[pick]), np.ascontiguousarray(cd[pick])
+    pts = qp.flatten(qp.families(rng, orc.oracle(), deep.desc, deep.so, (co, cd), n=150))
+    tris = np.ascontiguousarray(np.concatenate([f[1] for f in tri_families(rng, orc.oracle(), deep.desc, n=120)]), F32)
+    dist = point_oracle.closest_points(deep.so, pts)["distance"]
+    md = (np.where(dist < np.finfo(F32).max, dist, F32(1.0)) * rng.uniform(1.0, 3.0, len(pts))).astype(F32)
+
+    def toward(p):
+        p = np.ascontiguousarray(p, F32)
+        return ray_oracle.cast_rays(deep.so, np.tile(cam, (len(p), 1)), np.ascontiguousarray(p - cam, F32))["pops"]
+    out = dict(rays=((ro, rd), ray_oracle.cast_rays(deep.so, ro, rd)["pops"]), points=((pts, md), toward(pts)),
+               tris=((tris,), toward(tris.mean(axis=1))))
+    assert out["rays"][1].max() > 16, out["rays"][1].max()      # deeper than the stack's LDS rows
+    return out
+
+
+def _hardest_last(pool, n, rng):
+    """n queries of a pool: the n // 2 deepest and random others, ordered by depth, so the deepest sit in the last workgroup"""
+    arrays, pops = pool
+    order = np.argsort(pops, kind="stable")
+    hard = order[len(order) - n // 2:] if n > 1 else order[-1:]
+    rest = rng.choice(order[:len(order) - len(hard)], n - len(hard), replace=False)
+    idx = np.concatenate([rest, hard])
+    idx = idx[np.argsort(pops[idx], kind="stable")]
+    assert pops[idx[-1]] == pops.max()
+    return tuple(np.ascontiguousarray(a[idx]) for a in arrays)
+
+
+@pytest.mark.parametrize("n", [1, 63, 65, 129])
+def test_partial_workgroup_on_the_deep_scene(deep, deep_queries, n):
+    """One call of each family with n one, one below and one above the workgroup of 64, and two groups plus one, on the scene whose
+    traversal stack outgrows its LDS rows; the deepest queries come last, in the partly filled group.  Every result equals the shim's
+    bit for bit."""
+    sp, so = deep.sp, deep.so
+    rng = np.random.default_rng(61 + n)
+    o, d = _hardest_last(deep_queries["rays"], n, rng)
+    pts, md = _hardest_last(deep_queries["points"], n, rng)
+    tris, = _hardest_last(deep_queries["tris"], n, rng)
+    assert sp.info()["max_stack"] > 16
+    exact = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv")
+    got, ref = sp.closest_points(pts, outputs=exact + ("pops",)), point_oracle.closest_points(so, pts)
+    for k in exact:
+        _eq(got[k], ref[k], "closest_points n=%d %s" % (n, k))
+    got, ref = sp.count_crossings(o, d, outputs=("count", "winding", "pops")), xo.count_crossings(so, o, d)
+    for k in ("count", "winding"):
+        _eq(got[k], ref[k], "count_crossings n=%d %s" % (n, k))
+    _eq(sp.winding_numbers(pts), xo.winding_numbers(so, pts), "winding_numbers n=%d" % n)
+    _eq(sp.signed_distance(pts, md), xo.signed_distance(so, pts, md), "signed_distance n=%d" % n)
+    got, ref = sp.list_crossings(o, d), xl.list_crossings(so, o, d)
+    for k in ("t", "instance", "triangle", "sign", "barycentric", "uv", "point", "offsets", "ray", "count"):
+        _eq(got[k], ref[k], "list_crossings n=%d %s" % (n, k))
+    got, ref = sp.list_nearby(pts, md, outputs=exact), nb.list_nearby(so, pts, md)
+    for k in exact + ("offsets", "point_index", "count"):
+        _eq(got[k], ref[k], "list_nearby n=%d %s" % (n, k))
+    got, ref = sp.count_intersecting(tris, outputs=("count", "any", "pops")), ti.count_intersecting(so, tris)
+    _eq(got["count"], ref, "count_intersecting n=%d count" % n)
+    assert np.array_equal(got["any"], ref > 0), "count_intersecting n=%d any" % n
