@@ -10,6 +10,7 @@ The directory name is not a Python identifier; import it with
 ``importlib.import_module("cuda-raytracing_amd")``.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -53,32 +54,43 @@ class RtInstanceDesc(C.Structure):
                 ("rotation", C.c_float * 3), ("inv_rotation", C.c_float * 3), ("scale", C.c_float * 3), ("inv_scale", C.c_float * 3)]
 
 
+# The fields of the query result structs of include/rt_hip.h, in struct order: the structs below and Scene.*_OUTPUTS are made of these
+# tuples (a list struct is its slot fields, then its per-query tail), and _FIELDS has each name's trailing shape and dtype.
+_RAY_OUTPUTS = ("t", "instance", "triangle", "location", "normal", "uv", "pops")
+_POINT_OUTPUTS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "pops")
+_CROSSING_OUTPUTS = ("count", "winding", "pops")
+_CROSSING_LIST_OUTPUTS = ("t", "instance", "triangle", "sign", "barycentric", "uv", "point")
+_NEARBY_LIST_OUTPUTS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv")
+_INTERSECT_COUNT_OUTPUTS = ("count", "any", "pops")
+_INTERSECT_LIST_OUTPUTS = ("instance", "triangle", "normal", "segment")
+
+
 class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers, any may be NULL)
-    _fields_ = [(n, _vp) for n in ("t", "instance", "triangle", "location", "normal", "uv", "pops")]
+    _fields_ = [(n, _vp) for n in _RAY_OUTPUTS]
 
 
 class RtPointHits(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL)
-    _fields_ = [(n, _vp) for n in ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "pops")]
+    _fields_ = [(n, _vp) for n in _POINT_OUTPUTS]
 
 
 class RtCrossings(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL)
-    _fields_ = [(n, _vp) for n in ("count", "winding", "pops")]
+    _fields_ = [(n, _vp) for n in _CROSSING_OUTPUTS]
 
 
 class RtCrossingList(C.Structure):          # include/rt_hip.h (device pointers, any may be NULL, at least one given)
-    _fields_ = [(n, _vp) for n in ("t", "instance", "triangle", "sign", "barycentric", "uv", "point", "count")]
+    _fields_ = [(n, _vp) for n in _CROSSING_LIST_OUTPUTS + ("count",)]
 
 
 class RtNearbyList(C.Structure):            # include/rt_hip.h (device pointers; distance, instance, triangle required)
-    _fields_ = [(n, _vp) for n in ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "count", "pops")]
+    _fields_ = [(n, _vp) for n in _NEARBY_LIST_OUTPUTS + ("count", "pops")]
 
 
 class RtIntersectCounts(C.Structure):       # include/rt_hip.h (device pointers, any may be NULL, at least one given)
-    _fields_ = [(n, _vp) for n in ("count", "any", "pops")]
+    _fields_ = [(n, _vp) for n in _INTERSECT_COUNT_OUTPUTS]
 
 
 class RtIntersectList(C.Structure):         # include/rt_hip.h (device pointers; instance, triangle required)
-    _fields_ = [(n, _vp) for n in ("instance", "triangle", "normal", "segment", "count", "pops")]
+    _fields_ = [(n, _vp) for n in _INTERSECT_LIST_OUTPUTS + ("count", "pops")]
 
 
 class RtSceneDesc(C.Structure):
@@ -212,6 +224,7 @@ def _declare(h, s):
                                              C.c_int32, C.c_int32, C.c_int32, _vp]
     _sz = C.POINTER(C.c_size_t)
     h.rt_comm_last_error.restype = C.c_char_p
+    h.rt_comm_last_error_any.restype = C.c_char_p
     h.rt_comm_available.argtypes = [_i]
     h.rt_comm_unique_id.argtypes = [_vp]
     h.rt_comm_init_rank.argtypes = [_vp, C.c_int32, C.c_int32, C.POINTER(_vp)]
@@ -326,6 +339,13 @@ def _fa(a):
 
 def _fp(a):
     return a.ctypes.data_as(_f)
+
+
+def _pose_batch(poses, d_ptrs):
+    """The arguments of a batched launch: (n, poses as float32 [n, 6], the n device pointers as a ctypes void* array)"""
+    n = len(poses)
+    P = _fa(np.asarray(poses, np.float32).reshape(n, 6))
+    return n, P, (_vp * n)(*[int(x) if not isinstance(x, _vp) else x.value for x in d_ptrs])
 
 
 def check(rc, what="rt call"):
@@ -509,12 +529,11 @@ class Scene:
     def loop_stats(self, camera, poses, d_imgs, pitch, stream=None):
         """rt_scene_loop_stats: renders the batch (poses[i] -> d_imgs[i]) through the instrumented copy of the production kernel and says
         which traversal loop the waves ran: dict of the RT_LOOP_* counts plus asm_loop_frac = casts on the hand-written loop / all casts."""
-        n = len(poses)
+        n, P, ptrs = _pose_batch(poses, d_imgs)
         cams = (RtCameraParams * n)()
-        for i, pose in enumerate(poses):
-            camera.set_pose(pose)
+        for i in range(n):
+            camera.set_pose(P[i])
             libs()[1].rth_camera_params(camera.h, C.addressof(cams[i]))
-        ptrs = (_vp * n)(*[int(x) if not isinstance(x, _vp) else x.value for x in d_imgs])
         out = (C.c_uint64 * 8)()
         check(libs()[0].rt_scene_loop_stats(self.device_handle, cams, ptrs, pitch, n, stream, out), "rt_scene_loop_stats")
         d = {k: int(out[i]) for i, k in enumerate(self.LOOP_STATS)}
@@ -522,7 +541,7 @@ class Scene:
         d["asm_loop_frac"] = round(d["asm"] / casts, 5) if casts else None
         return d
 
-    RAY_OUTPUTS = ("t", "instance", "triangle", "location", "normal", "uv", "pops")     # the fields of RtRayHits
+    RAY_OUTPUTS = _RAY_OUTPUTS                                          # the fields of RtRayHits
 
     def trace_rays(self, origins, directions, outputs=("t", "instance", "triangle"), stream=None, binning=None):
         """The reference's cast_ray (raycast.cu:21-142) on the caller's rays, closest hit, bit for bit (rt_trace_rays): dict of the
@@ -531,20 +550,28 @@ class Scene:
         accepted hit, :115-122), uv [..., 2] float32 (TrianglePrimitive::point_inside), pops [...] int32 (node pops, :61).
         origins, directions: float32 [..., 3], contiguous, same shape.  torch tensors on the scene's (current) device: outputs
         are torch tensors allocated there and the call is enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t; default
-        torch.cuda.current_stream()) without a synchronise.  numpy arrays: copied to the device and back, the call synchronises.  binning: sort the rays by direction
+        torch.cuda.current_stream()) without a synchronise.  Every tensor a query makes (outputs, offsets, workspace) is allocated
+        with `stream` as the current stream, so the caching allocator hands its memory out again only in `stream`'s order, after the
+        kernel that writes it.  numpy arrays: copied to the device and back, the call synchronises.  binning: sort the rays by direction
         octant on the device first (same results; None = TRACE_BINNING, see DESIGN.md "Ray queries")."""
-        bad = [o for o in outputs if o not in self.RAY_OUTPUTS]
-        if bad or not outputs:
-            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.RAY_OUTPUTS, tuple(outputs)))
-        return _ray_query(self, origins, directions, None, tuple(outputs), stream, binning)
+        outputs = _check_outputs(outputs, self.RAY_OUTPUTS)
+
+        def call(h, handle, ins, ptr, n, st, sync, ws, ws_bytes):
+            hits = RtRayHits(*[ptr.get(k) for k in _RAY_OUTPUTS])
+            check(h.rt_trace_rays(handle, ins[0], ins[1], n, C.byref(hits), ws, ws_bytes, st, sync), "rt_trace_rays")
+        return _device_query(self, [("origins", origins), ("directions", directions)], outputs, call, stream,
+                             scratch=_trace_workspace(binning))
 
     def occluded(self, origins, directions, tmax=None, stream=None, binning=None):
         """Occlusion (rt_occluded): cast_ray(ray, lighting_pass = true, light_distance = tmax) with the early return of
         raycast.cu:129-133 -- uint8 [...], 1 where the cast accepts a hit closer than tmax (None: FLT_MAX for every ray; a
         float32 array of the rays' leading shape otherwise).  Arguments and paths as in trace_rays."""
-        return _ray_query(self, origins, directions, tmax, ("occluded",), stream, binning)["occluded"]
+        def call(h, handle, ins, ptr, n, st, sync, ws, ws_bytes):
+            check(h.rt_occluded(handle, ins[0], ins[1], ins[2], n, ptr["occluded"], ws, ws_bytes, st, sync), "rt_occluded")
+        return _device_query(self, [("origins", origins), ("directions", directions), ("tmax", tmax)], ("occluded",), call, stream,
+                             scratch=_trace_workspace(binning))["occluded"]
 
-    POINT_OUTPUTS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv", "pops")    # the fields of RtPointHits
+    POINT_OUTPUTS = _POINT_OUTPUTS                                      # the fields of RtPointHits
 
     def closest_points(self, points, max_distance=None, outputs=("distance", "instance", "triangle"), stream=None):
         """The nearest point of the scene's triangles to each of the caller's points (rt_closest_points; the rule, bit for bit a
@@ -553,15 +580,17 @@ class Scene:
         (world position of the closest point, world face normal), barycentric [..., 2] float32 (weights of v1 and v2), uv [..., 2]
         float32, pops [...] int32 (interior nodes visited).  points: float32 [..., 3], contiguous.  max_distance: None (+inf) or
         float32 of the points' leading shape; a triangle farther than it is no candidate (inclusive), NaN or negative = a miss.
-        torch tensors on the scene's (current) device: outputs are allocated there and the call is enqueued on `stream` (a
-        torch.cuda.Stream or a raw hipStream_t; default torch.cuda.current_stream()) without a synchronise.  numpy arrays: copied
-        to the device and back, the call synchronises."""
-        bad = [o for o in outputs if o not in self.POINT_OUTPUTS]
-        if bad or not outputs:
-            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.POINT_OUTPUTS, tuple(outputs)))
-        return _point_query(self, points, max_distance, tuple(outputs), stream)
+        torch tensors on the scene's (current) device: outputs are allocated there, with `stream` as the current stream as in
+        trace_rays, and the call is enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t; default
+        torch.cuda.current_stream()) without a synchronise.  numpy arrays: copied to the device and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.POINT_OUTPUTS)
 
-    CROSSING_OUTPUTS = ("count", "winding", "pops")     # the fields of RtCrossings
+        def call(h, handle, ins, ptr, n, st, sync):
+            hits = RtPointHits(*[ptr.get(k) for k in _POINT_OUTPUTS])
+            check(h.rt_closest_points(handle, ins[0], ins[1], n, C.byref(hits), st, sync), "rt_closest_points")
+        return _device_query(self, [("points", points), ("max_distance", max_distance)], outputs, call, stream)
+
+    CROSSING_OUTPUTS = _CROSSING_OUTPUTS                                # the fields of RtCrossings
 
     def count_crossings(self, origins, directions, tmax=None, outputs=("count", "winding"), stream=None):
         """Crossings of the scene's triangles along each of the caller's rays (rt_count_crossings; the rule, equal to a brute-force
@@ -571,16 +600,12 @@ class Scene:
         float32 [..., 3], contiguous.  tmax: None (+inf) or float32 of the rays' leading shape, a ray parameter (with directions
         b - a and tmax 1, count is the crossings of the segment ab).  torch tensors: asynchronous on `stream` (default the current
         stream); numpy arrays: copied to the device and back, the call synchronises."""
-        bad = [o for o in outputs if o not in self.CROSSING_OUTPUTS]
-        if bad or not outputs:
-            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.CROSSING_OUTPUTS, tuple(outputs)))
-        outputs = tuple(outputs)
+        outputs = _check_outputs(outputs, self.CROSSING_OUTPUTS)
 
         def call(h, handle, ins, ptr, n, st, sync):
-            c = RtCrossings(*[ptr.get(k) for k in Scene.CROSSING_OUTPUTS])
+            c = RtCrossings(*[ptr.get(k) for k in _CROSSING_OUTPUTS])
             check(h.rt_count_crossings(handle, ins[0], ins[1], ins[2], n, C.byref(c), st, sync), "rt_count_crossings")
-        return _device_query(self, [("origins", origins), ("directions", directions), ("tmax", tmax)],
-                               {k: ((), np.int32) for k in outputs}, call, stream)
+        return _device_query(self, [("origins", origins), ("directions", directions), ("tmax", tmax)], outputs, call, stream)
 
     def winding_numbers(self, points, stream=None):
         """The winding number of each of the caller's points (rt_winding_numbers): int32 of the points' leading shape, the median of
@@ -588,7 +613,7 @@ class Scene:
         in count_crossings."""
         def call(h, handle, ins, ptr, n, st, sync):
             check(h.rt_winding_numbers(handle, ins[0], n, ptr["winding"], st, sync), "rt_winding_numbers")
-        return _device_query(self, [("points", points)], {"winding": ((), np.int32)}, call, stream)["winding"]
+        return _device_query(self, [("points", points)], ("winding",), call, stream)["winding"]
 
     def signed_distance(self, points, max_distance=None, stream=None):
         """Signed distance of each of the caller's points (rt_signed_distance): float32 of the points' leading shape, closest_points'
@@ -596,10 +621,9 @@ class Scene:
         float32 [..., 3]; max_distance: None (+inf) or float32 of the points' leading shape.  Paths as in count_crossings."""
         def call(h, handle, ins, ptr, n, st, sync):
             check(h.rt_signed_distance(handle, ins[0], ins[1], n, ptr["sdf"], None, st, sync), "rt_signed_distance")
-        return _device_query(self, [("points", points), ("max_distance", max_distance)], {"sdf": ((), np.float32)}, call,
-                               stream)["sdf"]
+        return _device_query(self, [("points", points), ("max_distance", max_distance)], ("sdf",), call, stream)["sdf"]
 
-    CROSSING_LIST_OUTPUTS = ("t", "instance", "triangle", "sign", "barycentric", "uv", "point")     # the fields of RtCrossingList
+    CROSSING_LIST_OUTPUTS = _CROSSING_LIST_OUTPUTS                      # the slot fields of RtCrossingList
 
     def list_crossings(self, origins, directions, tmax=None, max_hits=None, outputs=CROSSING_LIST_OUTPUTS, stream=None):
         """Every triangle each of the caller's rays crosses, sorted by (t, instance, triangle) (rt_crossing_offsets /
@@ -612,16 +636,11 @@ class Scene:
         max_hits=K >= 1: the first K hits of each ray, fields [..., K] / [..., K, 2|3] padded with t = inf, instance = triangle = -1,
         sign 0 and float 0, plus `count` (the full count, so count > K means truncated); on torch fully asynchronous on `stream`.
         numpy arrays: copied to the device and back, the call synchronises."""
-        bad = [o for o in outputs if o not in self.CROSSING_LIST_OUTPUTS]
-        if bad or not outputs:
-            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.CROSSING_LIST_OUTPUTS, tuple(outputs)))
-        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not
-                                     1 <= int(max_hits) <= 2 ** 31 - 1):
-            raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
+        outputs = _check_outputs(outputs, self.CROSSING_LIST_OUTPUTS)
         return _list_query(self, _CROSSING_LIST, [("origins", origins), ("directions", directions), ("tmax", tmax)],
-                           None if max_hits is None else int(max_hits), tuple(outputs), ("count",), stream)
+                           _check_max_hits(max_hits), outputs, stream, per_query=("count",))
 
-    NEARBY_LIST_OUTPUTS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv")     # the slot fields of RtNearbyList
+    NEARBY_LIST_OUTPUTS = _NEARBY_LIST_OUTPUTS                          # the slot fields of RtNearbyList
 
     def list_nearby(self, points, max_distance=None, max_hits=None, outputs=("distance", "instance", "triangle"), stream=None):
         """Every triangle within max_distance of each of the caller's points, sorted by (d2, instance, triangle) -- slot 0 is
@@ -637,22 +656,13 @@ class Scene:
         without count the traversal prunes by the K-th distance (k-nearest), with the same rooms.  On torch fully asynchronous on
         `stream`.  max_distance and max_hits must not both be None (every triangle for every point).
         numpy arrays: copied to the device and back, the call synchronises."""
-        slots = tuple(o for o in outputs if o not in ("count", "pops"))
-        bad = [o for o in slots if o not in self.NEARBY_LIST_OUTPUTS]
-        if bad or not slots or len(set(outputs)) != len(tuple(outputs)):
-            raise ValueError("outputs must be a non-empty subset of %s, optionally with count and pops, got %r"
-                             % (self.NEARBY_LIST_OUTPUTS, tuple(outputs)))
-        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not
-                                     1 <= int(max_hits) <= 2 ** 31 - 1):
-            raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
+        outputs = _check_outputs(outputs, self.NEARBY_LIST_OUTPUTS, extras=("count", "pops"))
+        max_hits = _check_max_hits(max_hits)
         if max_distance is None and max_hits is None:
             raise ValueError("max_distance and max_hits are both None: that lists every triangle for every point")
-        csr = max_hits is None
-        per_point = tuple(k for k in ("count", "pops") if k in outputs and not (csr and k == "count"))
-        return _list_query(self, _NEARBY_LIST, [("points", points), ("max_distance", max_distance)],
-                           None if csr else int(max_hits), slots, per_point, stream)
+        return _list_query(self, _NEARBY_LIST, [("points", points), ("max_distance", max_distance)], max_hits, outputs, stream)
 
-    INTERSECT_COUNT_OUTPUTS = ("count", "any", "pops")     # the fields of RtIntersectCounts
+    INTERSECT_COUNT_OUTPUTS = _INTERSECT_COUNT_OUTPUTS                  # the fields of RtIntersectCounts
 
     def count_intersecting(self, triangles, skip_instance=None, outputs=("count",), stream=None):
         """How many scene triangles each of the caller's triangles intersects (rt_count_intersecting; the rule, equal to a brute-force
@@ -662,22 +672,15 @@ class Scene:
         [..., 3, 3] world vertices, contiguous.  skip_instance: None or int32 of the leading shape, one instance per triangle whose pairs
         are never reported (-1 = none).  torch tensors: asynchronous on `stream` (default the current stream); numpy arrays: copied to
         the device and back, the call synchronises."""
-        bad = [o for o in outputs if o not in self.INTERSECT_COUNT_OUTPUTS]
-        if bad or not outputs:
-            raise ValueError("outputs must be a non-empty subset of %s, got %r" % (self.INTERSECT_COUNT_OUTPUTS, tuple(outputs)))
-        outputs = tuple(outputs)
+        outputs = _check_outputs(outputs, self.INTERSECT_COUNT_OUTPUTS)
 
         def call(h, handle, ins, ptr, n, st, sync):
-            c = RtIntersectCounts(*[ptr.get(k) for k in Scene.INTERSECT_COUNT_OUTPUTS])
+            c = RtIntersectCounts(*[ptr.get(k) for k in _INTERSECT_COUNT_OUTPUTS])
             check(h.rt_count_intersecting(handle, ins[0], ins[1], n, C.byref(c), st, sync), "rt_count_intersecting")
-        res = _device_query(self, [("triangles", triangles), ("skip_instance", skip_instance)],
-                            {k: ((), np.uint8 if k == "any" else np.int32) for k in outputs}, call, stream, **_TRIANGLE_INPUTS)
-        if "any" in res:
-            a = res["any"]
-            res["any"] = a.view(np.bool_) if isinstance(a, np.ndarray) else a.view(__import__("torch").bool)
-        return res
+        return _device_query(self, [("triangles", triangles), ("skip_instance", skip_instance)], outputs, call, stream,
+                             **_TRIANGLE_INPUTS)
 
-    INTERSECT_LIST_OUTPUTS = ("instance", "triangle", "normal", "segment")     # the slot fields of RtIntersectList
+    INTERSECT_LIST_OUTPUTS = _INTERSECT_LIST_OUTPUTS                    # the slot fields of RtIntersectList
 
     def list_intersecting(self, triangles, skip_instance=None, max_hits=None, outputs=("instance", "triangle"), stream=None):
         """Every scene triangle each of the caller's triangles intersects, sorted by (instance, triangle) (rt_intersecting_offsets /
@@ -692,18 +695,9 @@ class Scene:
         triangle = -1 and float 0; `count` (the full number, so count > K means truncated) and `pops` only when in outputs -- without
         count the traversal ends after the instance of a full room's last key, with the same rooms.  On torch fully asynchronous on
         `stream`.  numpy arrays: copied to the device and back, the call synchronises."""
-        slots = tuple(o for o in outputs if o not in ("count", "pops"))
-        bad = [o for o in slots if o not in self.INTERSECT_LIST_OUTPUTS]
-        if bad or not slots or len(set(outputs)) != len(tuple(outputs)):
-            raise ValueError("outputs must be a non-empty subset of %s, optionally with count and pops, got %r"
-                             % (self.INTERSECT_LIST_OUTPUTS, tuple(outputs)))
-        if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not
-                                     1 <= int(max_hits) <= 2 ** 31 - 1):
-            raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
-        csr = max_hits is None
-        per_point = tuple(k for k in ("count", "pops") if k in outputs and not (csr and k == "count"))
+        outputs = _check_outputs(outputs, self.INTERSECT_LIST_OUTPUTS, extras=("count", "pops"))
         return _list_query(self, _INTERSECT_LIST, [("triangles", triangles), ("skip_instance", skip_instance)],
-                           None if csr else int(max_hits), slots, per_point, stream)
+                           _check_max_hits(max_hits), outputs, stream)
 
     def info(self):
         b = C.c_size_t(0)
@@ -743,26 +737,14 @@ class Camera:
 
     def rays(self, as_numpy=False, stream=None):
         """(origins, directions) float32 [height, width, 3] of every pixel's primary ray, exactly as the render kernels make it
-        (raycast.cu:156-188; rt_camera_rays): torch tensors on the current device, enqueued on `stream` (default the current torch
-        stream) without a synchronise -- or numpy arrays with as_numpy=True."""
-        h = libs()[0]
+        (raycast.cu:156-188; rt_camera_rays): torch tensors on the current device, allocated and enqueued on `stream` (default the
+        current torch stream) without a synchronise -- or numpy arrays with as_numpy=True."""
         p = self.params()
         shape = (self.height, self.width, 3)
-        if as_numpy:
-            n = self.width * self.height * 3 * 4
-            bo, bd = DeviceBuffer(nbytes=n), DeviceBuffer(nbytes=n)
-            try:
-                check(h.rt_camera_rays(C.byref(p), bo.ptr, bd.ptr, stream, 1), "rt_camera_rays")
-                return bo.to_host(np.float32).reshape(shape), bd.to_host(np.float32).reshape(shape)
-            finally:
-                bo.free()
-                bd.free()
-        import torch
-        o = torch.empty(shape, dtype=torch.float32, device="cuda")
-        d = torch.empty(shape, dtype=torch.float32, device="cuda")
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        check(h.rt_camera_rays(C.byref(p), o.data_ptr(), d.data_ptr(), st, 0), "rt_camera_rays")
-        return o, d
+        with _staging(not as_numpy, stream) as sg:
+            o, d = sg.alloc(shape, np.float32), sg.alloc(shape, np.float32)
+            check(libs()[0].rt_camera_rays(C.byref(p), sg.ptr(o), sg.ptr(d), sg.stream, sg.sync), "rt_camera_rays")
+            return sg.result(o), sg.result(d)
 
     def render_scene(self, scene, d_img, pitch, synchronize=False):
         check(libs()[1].rth_camera_render_scene(self.h, scene.h, d_img, pitch, 1 if synchronize else 0), "Camera::render_scene")
@@ -801,9 +783,7 @@ class Camera:
 
     def render_scene_batch(self, scene, poses, d_imgs, pitch, synchronize=False):
         """frames along a camera path in one launch: poses[i] -> d_imgs[i] (device pointers)"""
-        n = len(poses)
-        P = _fa(np.asarray(poses, np.float32).reshape(n, 6))
-        ptrs = (_vp * n)(*[int(x) if not isinstance(x, _vp) else x.value for x in d_imgs])
+        n, P, ptrs = _pose_batch(poses, d_imgs)
         check(libs()[1].rth_camera_render_scene_batch(self.h, scene.h, _fp(P), ptrs, pitch, n, 1 if synchronize else 0),
               "Camera::render_scene_batch")
 
@@ -812,9 +792,7 @@ class Camera:
         overhead matters when a rank's share of a frame takes tens of microseconds).  stripes = (stripe_rows, rank,
         num_ranks) renders this rank's stripes, (stripe_rows, rank, num_ranks, first_frame) with the stripe owner rotating over
         the frames (frame i renders owner (rank + first_frame + i) % num_ranks), None renders whole frames."""
-        n = len(poses)
-        P = _fa(np.asarray(poses, np.float32).reshape(n, 6))
-        ptrs = (_vp * n)(*[int(x) if not isinstance(x, _vp) else x.value for x in d_ptrs])
+        n, P, ptrs = _pose_batch(poses, d_ptrs)
         host, cam_h, scene_h, Pp = libs()[1], self.h, scene.h, _fp(P)
         if stripes is None:
             fn = host.rth_camera_render_scene_batch
@@ -843,9 +821,7 @@ class Camera:
         return call
 
     def render_scene_stripes_batch(self, scene, poses, d_locals, local_pitch, stripe_rows, rank, num_ranks, synchronize=False, rotate_first=None):
-        n = len(poses)
-        P = _fa(np.asarray(poses, np.float32).reshape(n, 6))
-        ptrs = (_vp * n)(*[int(x) if not isinstance(x, _vp) else x.value for x in d_locals])
+        n, P, ptrs = _pose_batch(poses, d_locals)
         if rotate_first is not None:
             check(libs()[1].rth_camera_render_scene_stripes_batch_rotating(self.h, scene.h, _fp(P), ptrs, local_pitch, n, stripe_rows, rank,
                                                                            num_ranks, rotate_first, 1 if synchronize else 0),
@@ -904,7 +880,6 @@ class Comm:
 
     @staticmethod
     def last_error():
-        libs()[0].rt_comm_last_error.restype = C.c_char_p
         e = libs()[0].rt_comm_last_error()
         return e.decode(errors="replace") if e else ""
 
@@ -912,7 +887,6 @@ class Comm:
     def last_error_any():
         """The most recent RT_E_COMM text of ANY thread (rt_comm_last_error() is the calling thread's own): what a watchdog
         thread reports about a main thread stuck in a collective."""
-        libs()[0].rt_comm_last_error_any.restype = C.c_char_p
         e = libs()[0].rt_comm_last_error_any()
         return e.decode(errors="replace") if e else ""
 
@@ -996,97 +970,45 @@ class DeviceBuffer:
 TRACE_BINNING = False
 
 
-def _ray_query(scene, origins, directions, tmax, outputs, stream, binning):
-    """Scene.trace_rays / Scene.occluded: every argument is checked before any device call."""
-    torch_in = type(origins).__module__.split(".")[0] == "torch"
-    if torch_in != (type(directions).__module__.split(".")[0] == "torch") or \
-            (tmax is not None and torch_in != (type(tmax).__module__.split(".")[0] == "torch")):
-        raise ValueError("origins, directions (and tmax) must all be torch tensors or all numpy arrays")
-    if not torch_in and not all(isinstance(a, np.ndarray) for a in (origins, directions) + (() if tmax is None else (tmax,))):
-        raise ValueError("rays must be numpy arrays or torch tensors")
-    arrays = (origins, directions) + (() if tmax is None else (tmax,))
-    for name, a in zip(("origins", "directions", "tmax"), arrays):
-        if str(a.dtype) not in ("float32", "torch.float32"):
-            raise ValueError("%s must be float32, got %s" % (name, a.dtype))
-        contiguous = a.is_contiguous() if torch_in else a.flags["C_CONTIGUOUS"]
-        if not contiguous:
-            raise ValueError("%s must be contiguous" % name)
-    if tuple(origins.shape) != tuple(directions.shape) or len(origins.shape) < 1 or origins.shape[-1] != 3:
-        raise ValueError("origins and directions must have the same shape [..., 3], got %s and %s"
-                         % (tuple(origins.shape), tuple(directions.shape)))
-    lead = tuple(origins.shape[:-1])
-    if tmax is not None and tuple(tmax.shape) != lead:
-        raise ValueError("tmax must have the rays' leading shape %s, got %s" % (lead, tuple(tmax.shape)))
-    n = int(np.prod(lead, dtype=np.int64))
-    if n > 2 ** 31 - 1:
-        raise ValueError("at most 2^31 - 1 rays per call, got %d" % n)
-    if torch_in:
-        import torch
-        for name, a in zip(("origins", "directions", "tmax"), arrays):
-            if not a.is_cuda:
-                raise ValueError("%s is on %s: torch rays must be on the scene's GPU" % (name, a.device))
-        dev = torch.device("cuda", torch.cuda.current_device())
-        for name, a in zip(("origins", "directions", "tmax"), arrays):
-            if a.device != dev:
-                raise ValueError("%s is on %s, the scene's device is %s" % (name, a.device, dev))
+def _trace_workspace(binning):
+    """The scratch request of Scene.trace_rays / occluded to _device_query: (h, n) -> the bytes rt_trace_workspace_bytes wants when
+    the rays are binned (binning=None: TRACE_BINNING as it is at the call), 0 otherwise"""
     if binning is None:
         binning = TRACE_BINNING
-    h = libs()[0]
-    handle = scene.device_handle
-    ws_bytes = h.rt_trace_workspace_bytes(n) if binning and n > 0 else 0
-    shapes = dict(t=(lead, np.float32), instance=(lead, np.int32), triangle=(lead, np.int32), location=(lead + (3,), np.float32),
-                  normal=(lead + (3,), np.float32), uv=(lead + (2,), np.float32), pops=(lead, np.int32), occluded=(lead, np.uint8))
-    if torch_in:
-        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}
-        out = {k: torch.empty(shapes[k][0], dtype=tdt[shapes[k][1]], device=dev) for k in outputs}
-        ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        if ws is not None:
-            ws.record_stream(ts)                                # (freed here, in use until `ts` has passed the call)
-        st = ts.cuda_stream
-        ptr = {k: v.data_ptr() for k, v in out.items()}
-        args = (origins.data_ptr(), directions.data_ptr(), None if tmax is None else tmax.data_ptr(), ws.data_ptr() if ws is not None else None)
-        sync, keep = 0, []
-    else:
-        keep = [DeviceBuffer(nbytes=max(a.nbytes, 1)) for a in arrays]
-        for b, a in zip(keep, arrays):
-            if a.nbytes:
-                check(h.rt_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes, stream), "rt_memcpy_h2d")
-        bufs = {k: DeviceBuffer(nbytes=max(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize, 1)) for k in outputs}
-        ws = DeviceBuffer(nbytes=ws_bytes) if ws_bytes else None
-        keep += list(bufs.values()) + ([ws] if ws is not None else [])
-        ptr = {k: b.ptr for k, b in bufs.items()}
-        args = (keep[0].ptr, keep[1].ptr, keep[2].ptr if tmax is not None else None, ws.ptr if ws is not None else None)
-        st, sync = stream, 1
-    try:
-        if outputs == ("occluded",):
-            check(h.rt_occluded(handle, args[0], args[1], args[2], n, ptr["occluded"], args[3], ws_bytes, st, sync), "rt_occluded")
-        else:
-            hits = RtRayHits(*[ptr.get(k) for k in Scene.RAY_OUTPUTS])
-            check(h.rt_trace_rays(handle, args[0], args[1], n, C.byref(hits), args[3], ws_bytes, st, sync), "rt_trace_rays")
-        if torch_in:
-            return out
-        return {k: b.to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0]) for k, b in bufs.items()}
-    finally:
-        for b in keep:
-            b.free()
+    return lambda h, n: h.rt_trace_workspace_bytes(n) if binning and n > 0 else 0
 
 
-def _point_query(scene, points, max_distance, outputs, stream):
-    """Scene.closest_points: every argument is checked before any device call (_device_query)."""
-    shapes = dict(distance=((), np.float32), instance=((), np.int32), triangle=((), np.int32), point=((3,), np.float32),
-                  normal=((3,), np.float32), barycentric=((2,), np.float32), uv=((2,), np.float32), pops=((), np.int32))
+# name -> (trailing shape, dtype) of every field a query returns, per query or per list slot: the same in every struct that has it
+_FIELDS = dict(
+    t=((), np.float32), distance=((), np.float32), sdf=((), np.float32), instance=((), np.int32), triangle=((), np.int32),
+    count=((), np.int32), winding=((), np.int32), pops=((), np.int32), sign=((), np.int8), occluded=((), np.uint8),
+    any=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
+    point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32))
 
-    def call(h, handle, ins, ptr, n, st, sync):
-        hits = RtPointHits(*[ptr.get(k) for k in Scene.POINT_OUTPUTS])
-        check(h.rt_closest_points(handle, ins[0], ins[1], n, C.byref(hits), st, sync), "rt_closest_points")
-    return _device_query(scene, [("points", points), ("max_distance", max_distance)], {k: shapes[k] for k in outputs}, call, stream)
+
+def _check_outputs(outputs, allowed, extras=()):
+    """`outputs` as a tuple: a non-empty choice of `allowed`, plus any of `extras` (where there are extras, nothing twice)"""
+    outputs = tuple(outputs)
+    chosen = [o for o in outputs if o not in extras]
+    if not chosen or [o for o in chosen if o not in allowed] or (extras and len(set(outputs)) != len(outputs)):
+        raise ValueError("outputs must be a non-empty subset of %s%s, got %r"
+                         % (allowed, ", optionally with " + " and ".join(extras) if extras else "", outputs))
+    return outputs
+
+
+def _check_max_hits(max_hits):
+    """max_hits of the list queries: None (CSR) or the room per query as an int"""
+    if max_hits is None:
+        return None
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) <= 2 ** 31 - 1:
+        raise ValueError("max_hits must be None or an int in [1, 2^31 - 1], got %r" % (max_hits,))
+    return int(max_hits)
 
 
 def _query_inputs(inputs, shape=(3,), ints=()):
-    """The argument checks of _device_query and _list_query, before any device call -> (torch_in, leading shape, n, device).
-    inputs: (name, array) pairs, the first [..., *shape] (default [..., 3]), "directions" of the same shape, the others of the
-    leading shape; None = not given.  Every input is float32 except those named in `ints`, which are int32."""
+    """The argument checks of every query (_device_query, _list_query), before any device call -> (torch_in, leading shape, n,
+    device).  inputs: (name, array) pairs, the first [..., *shape] (default [..., 3]), "directions" of the same shape, the others of
+    the leading shape; None = not given.  Every input is float32 except those named in `ints`, which are int32."""
     given = [(k, a) for k, a in inputs if a is not None]
     torch_in = type(given[0][1]).__module__.split(".")[0] == "torch"
     if any((type(a).__module__.split(".")[0] == "torch") != torch_in for _k, a in given):
@@ -1111,7 +1033,7 @@ def _query_inputs(inputs, shape=(3,), ints=()):
         want = tuple(a0.shape) if name == "directions" else lead
         if tuple(a.shape) != want:
             raise ValueError("%s must have the shape %s, got %s" % (name, want, tuple(a.shape)))
-    n = int(np.prod(lead, dtype=np.int64))
+    n = math.prod(lead)
     if n > 2 ** 31 - 1:
         raise ValueError("at most 2^31 - 1 queries per call, got %d" % n)
     dev = None
@@ -1127,166 +1049,200 @@ def _query_inputs(inputs, shape=(3,), ints=()):
     return torch_in, lead, n, dev
 
 
-_LIST_FIELDS = dict(t=((), np.float32), instance=((), np.int32), triangle=((), np.int32), sign=((), np.int8),
-                    barycentric=((2,), np.float32), uv=((2,), np.float32), point=((3,), np.float32))
-_NEARBY_FIELDS = dict(distance=((), np.float32), instance=((), np.int32), triangle=((), np.int32), point=((3,), np.float32),
-                      normal=((3,), np.float32), barycentric=((2,), np.float32), uv=((2,), np.float32))
+def _staging(torch_form, stream, dev=None):
+    """The staging of one "arrays in, arrays out" call (the queries, Camera.rays): a context manager in a torch and a numpy form with
+    stream / sync (what the C-ABI call is given), inputs(arrays) -> device pointers (None stays None), alloc(shape, dtype, zero=False)
+    -> an output or scratch array, ptr(array), read_int64(array, i) -> that element on the host, result(array) -> what the caller
+    gets, and run_index / run_lengths on the result of a CSR offsets array.  Leaving it frees what it made, on every exit path."""
+    return _TorchStaging(stream, dev) if torch_form else _HostStaging(stream)
+
+
+class _TorchStaging:
+    """Tensors in, tensors out, no host synchronisation but read_int64's.  `stream`: None (the current stream), a torch.cuda.Stream or
+    a raw hipStream_t.  It is the current stream inside the context, so every tensor made here is allocated under the stream of the
+    kernels that use it: the caching allocator reuses a freed tensor's memory in that stream's order only, so nothing has to be
+    recorded on another stream and the caller may drop a result at any time."""
+    sync = 0
+    _dtypes = None                              # numpy type, as _FIELDS and the callers name it -> torch dtype; made by the first call
+
+    def __init__(self, stream, dev):
+        import torch
+        self.torch = torch
+        if self._dtypes is None:
+            _TorchStaging._dtypes = {t: getattr(torch, np.dtype(t).name) for t in {dt for _tr, dt in _FIELDS.values()} | {np.int64}}
+        self.dev = dev if dev is not None else torch.device("cuda", torch.cuda.current_device())
+        ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        self.stream = ts.cuda_stream
+        self._current = None if stream is None else torch.cuda.stream(ts)
+
+    def __enter__(self):
+        if self._current is not None:
+            self._current.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        if self._current is not None:
+            self._current.__exit__(*exc)
+
+    def inputs(self, arrays):
+        return [None if a is None else a.data_ptr() for a in arrays]
+
+    def alloc(self, shape, dtype, zero=False):
+        make = self.torch.zeros if zero else self.torch.empty
+        return make(shape, dtype=self._dtypes[dtype], device=self.dev)
+
+    def ptr(self, a):
+        return a.data_ptr()
+
+    def read_int64(self, a, i):
+        return int(a[i].item())
+
+    def result(self, a):
+        return a
+
+    def run_index(self, offsets, total):
+        torch = self.torch
+        return torch.repeat_interleave(torch.arange(len(offsets) - 1, dtype=torch.int32, device=self.dev), offsets[1:] - offsets[:-1],
+                                       output_size=total)
+
+    def run_lengths(self, offsets):
+        return (offsets[1:] - offsets[:-1]).to(self.torch.int32)
+
+
+class _HostStaging:
+    """numpy arrays in, numpy arrays out: inputs are copied to device buffers, the C-ABI call synchronises, results are copied back.
+    An array here is (DeviceBuffer, shape, dtype)."""
+    sync = 1
+
+    def __init__(self, stream):
+        self.stream, self._made = stream, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for b in self._made:
+            b.free()
+
+    def _buffer(self, host=None, nbytes=0):
+        """a device buffer of nbytes, or with the contents of the host array"""
+        nbytes = nbytes if host is None else host.nbytes
+        b = DeviceBuffer(nbytes=max(nbytes, 1))
+        self._made.append(b)
+        if nbytes and host is not None:
+            check(libs()[0].rt_memcpy_h2d(b.ptr, host.ctypes.data, nbytes, self.stream), "rt_memcpy_h2d")
+        return b
+
+    def inputs(self, arrays):
+        return [None if a is None else self._buffer(a).ptr for a in arrays]
+
+    def alloc(self, shape, dtype, zero=False):
+        dtype = np.dtype(dtype)
+        if zero:
+            return self._buffer(np.zeros(shape, dtype)), tuple(shape), dtype
+        return self._buffer(nbytes=math.prod(shape) * dtype.itemsize), tuple(shape), dtype
+
+    def ptr(self, a):
+        return a[0].ptr
+
+    def read_int64(self, a, i):
+        v = np.zeros(1, np.int64)
+        check(libs()[0].rt_memcpy_d2h(v.ctypes.data, a[0].ptr.value + 8 * i, 8, None), "rt_memcpy_d2h")
+        return int(v[0])
+
+    def result(self, a):
+        b, shape, dtype = a
+        size = math.prod(shape)
+        return b.to_host(dtype)[:size].reshape(shape) if size else np.zeros(shape, dtype)
+
+    def run_index(self, offsets, total):            # (total: what the torch form needs to stay asynchronous; np.repeat finds it)
+        return np.repeat(np.arange(len(offsets) - 1, dtype=np.int32), np.diff(offsets))
+
+    def run_lengths(self, offsets):
+        return np.diff(offsets).astype(np.int32)
 
 
 class _ListKind:
-    """What _list_query needs of one list query: the slot fields in struct order and their (trailing shape, dtype), the key fields
-    (always filled: the room keeps them), the struct (slot fields, then the per-point fields `tail`), the three C-ABI calls and the
-    name of the per-slot query index of the CSR form"""
+    """What _list_query needs of one list query: the slot fields in struct order, the key fields (always filled: the room keeps them),
+    the struct (slot fields, then the per-query fields `tail`), the three C-ABI calls and the name of the per-slot query index of the
+    CSR form"""
 
-    def __init__(self, names, fields, keys, struct, tail, ws, offsets, fill, index, inputs=None):
-        self.names, self.fields, self.keys, self.struct, self.tail = names, fields, keys, struct, tail
+    def __init__(self, names, keys, struct, ws, offsets, fill, index, inputs=None):
+        self.names, self.keys, self.struct = names, keys, struct
+        self.tail = tuple(f for f, _t in struct._fields_[len(names):])
         self.ws, self.offsets, self.fill, self.index = ws, offsets, fill, index
         self.inputs = inputs or {}              # _query_inputs' shape / ints when they are not the defaults
 
 
-def _list_query(scene, kind, inputs, max_hits, outputs, per_point, stream):
-    """Scene.list_crossings / Scene.list_nearby: every argument is checked before any device call (_query_inputs).  inputs: (name,
-    array) pairs in the C-ABI's order.  The key fields are always filled (the room keeps the keys, so the kernel inserts rather than
-    selects); the ones not wanted are dropped.  per_point: the fields of kind.tail the kernel fills ([...] int32 each, returned);
-    in CSR form `count` is taken from the offsets when the kernel does not fill it."""
+def _list_query(scene, kind, inputs, max_hits, outputs, stream, per_query=None):
+    """Scene.list_crossings / list_nearby / list_intersecting: every argument is checked before any device call (_query_inputs).
+    inputs: (name, array) pairs in the C-ABI's order.  The key fields are always filled (the room keeps the keys, so the kernel inserts
+    rather than selects); the ones not wanted are dropped.  per_query: the fields of kind.tail the kernel fills ([...] int32 each,
+    returned); None: those named in outputs, `count` in fixed rooms only.  In CSR form `count` is taken from the offsets when the
+    kernel does not fill it."""
     torch_in, lead, n, dev = _query_inputs(inputs, **kind.inputs)
+    csr = max_hits is None
+    if per_query is None:
+        per_query = tuple(k for k in kind.tail if k in outputs and not (csr and k == "count"))
     h = libs()[0]
     handle = scene.device_handle
     fields = tuple(k for k in kind.names if k in outputs or k in kind.keys)
-    csr = max_hits is None
-    if torch_in:
-        import torch
-        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int8: torch.int8}
-        ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
-        st = ts.cuda_stream
-        ins = [None if a is None else a.data_ptr() for _k, a in inputs]
-        pp = {k: torch.empty(lead, dtype=torch.int32, device=dev) for k in per_point}
+    with _staging(torch_in, stream, dev) as sg:
+        ins = sg.inputs([a for _k, a in inputs])
+        tail = {k: sg.alloc(lead, np.int32) for k in per_query}
         offsets = None
         if csr:
-            with torch.cuda.stream(ts):
-                offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-                ws = torch.empty(max(int(getattr(h, kind.ws)(n)), 1), dtype=torch.uint8, device=dev)
-                check(getattr(h, kind.offsets)(handle, *ins, n, offsets.data_ptr(), ws.data_ptr(), ws.numel(), st, 0), kind.offsets)
-                total = int(offsets[n].item())                  # the one host synchronisation: the size of the outputs
-            rows = (total,)
+            offsets = sg.alloc((n + 1,), np.int64, zero=n == 0)     # (rt_*_offsets writes all n + 1 entries, or nothing when n is 0)
+            ws_bytes = max(int(getattr(h, kind.ws)(n)), 1)
+            ws = sg.alloc((ws_bytes,), np.uint8)
+            check(getattr(h, kind.offsets)(handle, *ins, n, sg.ptr(offsets), sg.ptr(ws), ws_bytes, sg.stream, sg.sync), kind.offsets)
+            rows = (sg.read_int64(offsets, n),)                     # torch: the one host synchronisation, for the size of the outputs
         else:
             rows = lead + (max_hits,)
-        with torch.cuda.stream(ts):
-            out = {k: torch.empty(rows + kind.fields[k][0], dtype=tdt[kind.fields[k][1]], device=dev) for k in fields}
-            lst = kind.struct(*[out[k].data_ptr() if k in out else None for k in kind.names],
-                              *[pp[k].data_ptr() if k in pp else None for k in kind.tail])
-            check(getattr(h, kind.fill)(handle, *ins, n, None if offsets is None else offsets.data_ptr(), 0 if csr else max_hits,
-                                        C.byref(lst), st, 0), kind.fill)
-            res = {k: out[k] for k in kind.names if k in outputs}
-            if csr:
-                res["offsets"] = offsets
-                res[kind.index] = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev), offsets[1:] - offsets[:-1],
-                                                          output_size=total)
-                if "count" not in pp:
-                    pp["count"] = (offsets[1:] - offsets[:-1]).to(torch.int32).reshape(lead)
-        res.update(pp)
-        return res
-    keep, ins = [], []
-    try:
-        for _k, a in inputs:
-            if a is None:
-                ins.append(None)
-                continue
-            b = DeviceBuffer(nbytes=max(a.nbytes, 1))
-            keep.append(b)
-            if a.nbytes:
-                check(h.rt_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes, stream), "rt_memcpy_h2d")
-            ins.append(b.ptr)
-
-        def buf(nbytes):
-            b = DeviceBuffer(nbytes=max(int(nbytes), 1))
-            keep.append(b)
-            return b
-        offsets = None
+        out = {k: sg.alloc(rows + _FIELDS[k][0], _FIELDS[k][1]) for k in fields}
+        lst = kind.struct(*[sg.ptr(out[k]) if k in out else None for k in kind.names],
+                          *[sg.ptr(tail[k]) if k in tail else None for k in kind.tail])
+        check(getattr(h, kind.fill)(handle, *ins, n, sg.ptr(offsets) if csr else None, 0 if csr else max_hits, C.byref(lst), sg.stream,
+                                    sg.sync), kind.fill)
+        res = {k: sg.result(out[k]) for k in kind.names if k in outputs}
+        res.update({k: sg.result(a) for k, a in tail.items()})
         if csr:
-            ob = buf((n + 1) * 8)
-            if n > 0:
-                wsb = int(getattr(h, kind.ws)(n))
-                ws = buf(wsb)
-                check(getattr(h, kind.offsets)(handle, *ins, n, ob.ptr, ws.ptr, wsb, stream, 1), kind.offsets)
-                offsets = ob.to_host(np.int64)[:n + 1]
-            else:
-                offsets = np.zeros(1, np.int64)
-            rows = (int(offsets[n]),)
-        else:
-            rows = lead + (max_hits,)
-        shapes = {k: (rows + kind.fields[k][0], kind.fields[k][1]) for k in fields}
-        bufs = {k: buf(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize) for k in fields}
-        pb = {k: buf(n * 4) for k in per_point}
-        lst = kind.struct(*[bufs[k].ptr if k in bufs else None for k in kind.names], *[pb[k].ptr if k in pb else None for k in kind.tail])
-        check(getattr(h, kind.fill)(handle, *ins, n, ob.ptr if csr else None, 0 if csr else max_hits, C.byref(lst), stream, 1), kind.fill)
-        res = {k: bufs[k].to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0])
-               for k in kind.names if k in outputs}
-        res.update({k: pb[k].to_host(np.int32)[:n].reshape(lead) for k in per_point})
-        if csr:
-            res["offsets"] = offsets
-            res[kind.index] = np.repeat(np.arange(n, dtype=np.int32), np.diff(offsets))
+            res["offsets"] = sg.result(offsets)
+            res[kind.index] = sg.run_index(res["offsets"], rows[0])
             if "count" not in res:
-                res["count"] = np.diff(offsets).astype(np.int32).reshape(lead)
+                res["count"] = sg.run_lengths(res["offsets"]).reshape(lead)
         return res
-    finally:
-        for b in keep:
-            b.free()
 
 
-_CROSSING_LIST = _ListKind(Scene.CROSSING_LIST_OUTPUTS, _LIST_FIELDS, ("t", "instance", "triangle"), RtCrossingList, ("count",),
+_CROSSING_LIST = _ListKind(_CROSSING_LIST_OUTPUTS, ("t", "instance", "triangle"), RtCrossingList,
                            "rt_crossing_offsets_workspace_bytes", "rt_crossing_offsets", "rt_list_crossings", "ray")
-_NEARBY_LIST = _ListKind(Scene.NEARBY_LIST_OUTPUTS, _NEARBY_FIELDS, ("distance", "instance", "triangle"), RtNearbyList, ("count", "pops"),
+_NEARBY_LIST = _ListKind(_NEARBY_LIST_OUTPUTS, ("distance", "instance", "triangle"), RtNearbyList,
                          "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby", "point_index")
 _TRIANGLE_INPUTS = dict(shape=(3, 3), ints=("skip_instance",))
-_INTERSECT_FIELDS = dict(instance=((), np.int32), triangle=((), np.int32), normal=((3,), np.float32), segment=((2, 3), np.float32))
-_INTERSECT_LIST = _ListKind(Scene.INTERSECT_LIST_OUTPUTS, _INTERSECT_FIELDS, ("instance", "triangle"), RtIntersectList, ("count", "pops"),
+_INTERSECT_LIST = _ListKind(_INTERSECT_LIST_OUTPUTS, ("instance", "triangle"), RtIntersectList,
                             "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting", "query_index",
                             inputs=_TRIANGLE_INPUTS)
 
 
-def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=()):
-    """Scene.closest_points / count_crossings / winding_numbers / signed_distance / count_intersecting: every argument is checked
-    before any device call.  inputs: (name, array) pairs, the first [..., 3] (or [..., *shape]), "directions" of the same shape, the
-    others of the leading shape; None = not given; int32 where named in `ints`.  outs: name -> (trailing shape, dtype).  call(h,
-    handle, input pointers, output pointers, n, stream, synchronize) makes the C-ABI call."""
+def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=(), scratch=None):
+    """Every query with one result per query (Scene.trace_rays / occluded / closest_points / count_crossings / winding_numbers /
+    signed_distance / count_intersecting): every argument is checked before any device call (_query_inputs, which has the rules for
+    inputs, shape and ints).  outs: names of _FIELDS.  call(h, handle, input pointers, output pointers by name, n, stream,
+    synchronize) makes the C-ABI call; with scratch, (h, n) -> bytes, it is also given a workspace of that size (None when 0) and
+    the size."""
     torch_in, lead, n, dev = _query_inputs(inputs, shape, ints)
-    if torch_in:
-        import torch
     h = libs()[0]
     handle = scene.device_handle
-    shapes = {k: (lead + tr, dt) for k, (tr, dt) in outs.items()}
-    if torch_in:
-        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}
-        out = {k: torch.empty(shapes[k][0], dtype=tdt[shapes[k][1]], device=dev) for k in outs}
-        ts = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
-        st = ts.cuda_stream
-        ptr = {k: v.data_ptr() for k, v in out.items()}
-        ins = [None if a is None else a.data_ptr() for _k, a in inputs]
-        sync, keep = 0, []
-    else:
-        keep, ins = [], []
-        for _k, a in inputs:
-            if a is None:
-                ins.append(None)
-                continue
-            b = DeviceBuffer(nbytes=max(a.nbytes, 1))
-            keep.append(b)
-            if a.nbytes:
-                check(h.rt_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes, stream), "rt_memcpy_h2d")
-            ins.append(b.ptr)
-        bufs = {k: DeviceBuffer(nbytes=max(int(np.prod(shapes[k][0], dtype=np.int64)) * np.dtype(shapes[k][1]).itemsize, 1)) for k in outs}
-        keep += list(bufs.values())
-        ptr = {k: b.ptr for k, b in bufs.items()}
-        st, sync = stream, 1
-    try:
-        call(h, handle, ins, ptr, n, st, sync)
-        if torch_in:
-            return out
-        return {k: b.to_host(shapes[k][1])[:int(np.prod(shapes[k][0], dtype=np.int64))].reshape(shapes[k][0]) for k, b in bufs.items()}
-    finally:
-        for b in keep:
-            b.free()
+    with _staging(torch_in, stream, dev) as sg:
+        ins = sg.inputs([a for _k, a in inputs])
+        out = {k: sg.alloc(lead + _FIELDS[k][0], _FIELDS[k][1]) for k in outs}
+        ws = ()
+        if scratch is not None:
+            ws_bytes = scratch(h, n)
+            workspace = sg.alloc((ws_bytes,), np.uint8) if ws_bytes else None
+            ws = (None if workspace is None else sg.ptr(workspace), ws_bytes)
+        call(h, handle, ins, {k: sg.ptr(a) for k, a in out.items()}, n, sg.stream, sg.sync, *ws)
+        return {k: sg.result(a) for k, a in out.items()}
 
 
 def render_debug(scene, camera):
