@@ -63,6 +63,8 @@ _CROSSING_LIST_OUTPUTS = ("t", "instance", "triangle", "sign", "barycentric", "u
 _NEARBY_LIST_OUTPUTS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv")
 _INTERSECT_COUNT_OUTPUTS = ("count", "any", "pops")
 _INTERSECT_LIST_OUTPUTS = ("instance", "triangle", "normal", "segment")
+_BOX_COUNT_OUTPUTS = ("count", "any", "pops")
+_BOX_LIST_OUTPUTS = ("instance", "triangle")
 
 
 class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers, any may be NULL)
@@ -93,6 +95,14 @@ class RtIntersectList(C.Structure):         # include/rt_hip.h (device pointers;
     _fields_ = [(n, _vp) for n in _INTERSECT_LIST_OUTPUTS + ("count", "pops")]
 
 
+class RtBoxCounts(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in _BOX_COUNT_OUTPUTS]
+
+
+class RtBoxList(C.Structure):               # include/rt_hip.h (device pointers; instance, triangle required)
+    _fields_ = [(n, _vp) for n in _BOX_LIST_OUTPUTS + ("count", "pops")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -109,7 +119,8 @@ RT_HIP_SYMBOLS = [
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
     "rt_closest_points", "rt_count_crossings", "rt_winding_numbers", "rt_signed_distance", "rt_crossing_offsets_workspace_bytes",
     "rt_crossing_offsets", "rt_list_crossings", "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby",
-    "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting"]
+    "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting",
+    "rt_count_in_boxes", "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "rt_occupancy_grid"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -257,6 +268,12 @@ def _declare(h, s):
     h.rt_intersecting_offsets_workspace_bytes.argtypes = [C.c_int32]
     h.rt_intersecting_offsets.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_intersecting.argtypes = [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtIntersectList), _vp, C.c_int]
+    h.rt_count_in_boxes.argtypes = [_vp, _vp, C.c_int32, C.POINTER(RtBoxCounts), _vp, C.c_int]
+    h.rt_box_offsets_workspace_bytes.restype = C.c_size_t
+    h.rt_box_offsets_workspace_bytes.argtypes = [C.c_int32]
+    h.rt_box_offsets.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_list_in_boxes.argtypes = [_vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtBoxList), _vp, C.c_int]
+    h.rt_occupancy_grid.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
     h.rt_timer_start.argtypes = [_vp, _vp]
@@ -699,6 +716,64 @@ class Scene:
         return _list_query(self, _INTERSECT_LIST, [("triangles", triangles), ("skip_instance", skip_instance)],
                            _check_max_hits(max_hits), outputs, stream)
 
+    BOX_COUNT_OUTPUTS = _BOX_COUNT_OUTPUTS                              # the fields of RtBoxCounts
+
+    def count_in_boxes(self, boxes, outputs=("count",), stream=None):
+        """How many scene triangles lie in or touch each of the caller's axis-aligned boxes (rt_count_in_boxes; the rule, equal to a
+        brute-force loop over every instance and triangle, is rule 11 of include/rt_hip.h): dict of the wanted BOX_COUNT_OUTPUTS of
+        the boxes' leading shape -- count (int32, the number of (instance, triangle) pairs), any (bool; wanted without count, the
+        traversal stops at the first pair), pops (int32, interior nodes visited).  boxes: float32 [..., 2, 3] world, lo then hi,
+        contiguous; a box with lo > hi on an axis or a NaN has no pairs.  torch tensors: asynchronous on `stream` (default the current
+        stream); numpy arrays: copied to the device and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.BOX_COUNT_OUTPUTS)
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            c = RtBoxCounts(*[ptr.get(k) for k in _BOX_COUNT_OUTPUTS])
+            check(h.rt_count_in_boxes(handle, ins[0], n, C.byref(c), st, sync), "rt_count_in_boxes")
+        return _device_query(self, [("boxes", boxes)], outputs, call, stream, **_BOX_INPUTS)
+
+    BOX_LIST_OUTPUTS = _BOX_LIST_OUTPUTS                                # the slot fields of RtBoxList
+
+    def list_in_boxes(self, boxes, max_hits=None, outputs=("instance", "triangle"), stream=None):
+        """Every scene triangle that lies in or touches each of the caller's boxes, sorted by (instance, triangle) (rt_box_offsets /
+        rt_list_in_boxes, include/rt_hip.h rule 11).  Fields: instance / triangle (int32).  boxes as in count_in_boxes.
+        max_hits=None (CSR): dict of `offsets` (int64 [n + 1], box j's pairs at offsets[j]:offsets[j+1]), the wanted fields over all
+        pairs ([total]), `query_index` (int32 [total], the flat index of each pair's box) and `count` (int32 of the leading shape, from
+        the offsets); "pops" in outputs adds the interior nodes visited by the fill.  On torch this makes exactly ONE host
+        synchronisation (reading offsets[n] to size the outputs).
+        max_hits=K >= 1: the first K pairs of each box, fields [..., K] padded with -1; `count` (the full number, so count > K means
+        truncated) and `pops` only when in outputs -- without count the traversal ends after the instance of a full room's last key,
+        with the same rooms.  On torch fully asynchronous on `stream`.  numpy arrays: copied to the device and back, the call
+        synchronises."""
+        outputs = _check_outputs(outputs, self.BOX_LIST_OUTPUTS, extras=("count", "pops"))
+        return _list_query(self, _BOX_LIST, [("boxes", boxes)], _check_max_hits(max_hits), outputs, stream)
+
+    GRID_OUTPUTS = ("occupied", "count")
+
+    def occupancy_grid(self, origin, spacing, dims, outputs=("occupied",), stream=None, as_numpy=False):
+        """count_in_boxes on the cells of a regular grid, which the kernel makes itself (rt_occupancy_grid): cell (ix, iy, iz) is the
+        box from origin + i*spacing to origin + (i + 1)*spacing per axis in float32, so neighbouring cells share their faces exactly.
+        origin, spacing: 3 floats; dims: (nx, ny, nz), each 0..2^24, at most 2^31 - 1 cells.  Dict of the wanted GRID_OUTPUTS, each
+        [nz, ny, nx]: occupied (bool; wanted without count, a cell's traversal stops at its first triangle), count (int32) -- torch
+        tensors on the current device, enqueued on `stream` (default the current torch stream) without a synchronise, or numpy
+        arrays with as_numpy=True.  A negative spacing makes every cell an inverted box: all zeros."""
+        outputs = _check_outputs(outputs, self.GRID_OUTPUTS)
+        o, sp = (np.array(a, np.float32).reshape(-1) for a in (origin, spacing))
+        d = np.array(dims).reshape(-1)
+        if o.shape != (3,) or sp.shape != (3,) or d.shape != (3,) or d.dtype.kind not in "iu":
+            raise ValueError("origin and spacing must be 3 floats and dims 3 ints, got %r, %r, %r" % (origin, spacing, dims))
+        if (d < 0).any() or (d > 2 ** 24).any() or math.prod(int(x) for x in d) > 2 ** 31 - 1:
+            raise ValueError("dims must be 0..2^24 each with at most 2^31 - 1 cells, got %r" % (tuple(int(x) for x in d),))
+        d = d.astype(np.int32)
+        shape = (int(d[2]), int(d[1]), int(d[0]))
+        handle = self.device_handle
+        with _staging(not as_numpy, stream) as sg:
+            out = {k: sg.alloc(shape, _FIELDS[k][1]) for k in outputs}
+            check(libs()[0].rt_occupancy_grid(handle, _fp(o), _fp(sp), d.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              sg.ptr(out["occupied"]) if "occupied" in out else None,
+                                              sg.ptr(out["count"]) if "count" in out else None, sg.stream, sg.sync), "rt_occupancy_grid")
+            return {k: sg.result(a) for k, a in out.items()}
+
     def info(self):
         b = C.c_size_t(0)
         d = C.c_int32(0)
@@ -982,7 +1057,7 @@ def _trace_workspace(binning):
 _FIELDS = dict(
     t=((), np.float32), distance=((), np.float32), sdf=((), np.float32), instance=((), np.int32), triangle=((), np.int32),
     count=((), np.int32), winding=((), np.int32), pops=((), np.int32), sign=((), np.int8), occluded=((), np.uint8),
-    any=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
+    any=((), np.bool_), occupied=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
     point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32))
 
 
@@ -1222,6 +1297,9 @@ _TRIANGLE_INPUTS = dict(shape=(3, 3), ints=("skip_instance",))
 _INTERSECT_LIST = _ListKind(_INTERSECT_LIST_OUTPUTS, ("instance", "triangle"), RtIntersectList,
                             "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting", "query_index",
                             inputs=_TRIANGLE_INPUTS)
+_BOX_INPUTS = dict(shape=(2, 3))
+_BOX_LIST = _ListKind(_BOX_LIST_OUTPUTS, ("instance", "triangle"), RtBoxList,
+                      "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "query_index", inputs=_BOX_INPUTS)
 
 
 def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=(), scratch=None):

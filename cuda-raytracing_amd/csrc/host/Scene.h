@@ -21,6 +21,8 @@ struct RtCrossingList;
 struct RtNearbyList;
 struct RtIntersectCounts;
 struct RtIntersectList;
+struct RtBoxCounts;
+struct RtBoxList;
 
 class Scene {
 public:
@@ -91,6 +93,16 @@ public:
                              size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
     int list_intersecting(const float* d_triangles, const int32_t* d_skip_instance, int32_t n, const int64_t* d_offsets, int32_t max_hits,
                           const RtIntersectList& out, void* stream = nullptr, bool synchronize = false);
+    // Box queries on the device scene: rt_count_in_boxes / rt_box_offsets / rt_list_in_boxes / rt_occupancy_grid of include/rt_hip.h
+    // (rule 11, rooms), where the semantics are.  Boxes ([n][2][3] world, lo then hi), offsets, workspace and outputs are DEVICE
+    // arrays; origin, spacing and dims of the grid are host arrays of 3.  Return the status.
+    int count_in_boxes(const float* d_boxes, int32_t n, const RtBoxCounts& out, void* stream = nullptr, bool synchronize = false);
+    int box_offsets(const float* d_boxes, int32_t n, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes,
+                    void* stream = nullptr, bool synchronize = false);
+    int list_in_boxes(const float* d_boxes, int32_t n, const int64_t* d_offsets, int32_t max_hits, const RtBoxList& out,
+                      void* stream = nullptr, bool synchronize = false);
+    int occupancy_grid(const float* origin, const float* spacing, const int32_t* dims, uint8_t* d_occupied, int32_t* d_count,
+                       void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

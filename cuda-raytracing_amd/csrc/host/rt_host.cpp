@@ -699,6 +699,35 @@ int Scene::list_intersecting(const float* d_triangles, const int32_t* d_skip_ins
     return last_error;
 }
 
+int Scene::count_in_boxes(const float* d_boxes, int32_t n, const RtBoxCounts& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_count_in_boxes(d_scene, d_boxes, n, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::box_offsets(const float* d_boxes, int32_t n, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream,
+                       bool synchronize)
+{
+    last_error = d_scene ? rt_box_offsets(d_scene, d_boxes, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::list_in_boxes(const float* d_boxes, int32_t n, const int64_t* d_offsets, int32_t max_hits, const RtBoxList& out, void* stream,
+                         bool synchronize)
+{
+    last_error = d_scene ? rt_list_in_boxes(d_scene, d_boxes, n, d_offsets, max_hits, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::occupancy_grid(const float* origin, const float* spacing, const int32_t* dims, uint8_t* d_occupied, int32_t* d_count,
+                          void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_occupancy_grid(d_scene, origin, spacing, dims, d_occupied, d_count, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

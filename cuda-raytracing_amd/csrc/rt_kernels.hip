@@ -3494,6 +3494,283 @@ __global__ __launch_bounds__(kTriBlock, 8) void intersect_list_kernel(const TriP
     if (p.pops) p.pops[i] = pops;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------
+// Box queries (rt_count_in_boxes / rt_box_offsets / rt_list_in_boxes / rt_occupancy_grid): every (instance, triangle) that meets a
+// caller's world axis-aligned box by rule 11 of include/rt_hip.h -- the box pre-test, then thirteen separating axes relative to the
+// box's first corner -- equal to a brute-force loop over every (instance, triangle) whatever the tree; the pruning argument is in
+// DESIGN.md section 16.  One wave per workgroup, one box per lane, the intersecting triangles' unordered traversal on the general
+// stack: every child box that overlaps the mapped box's bounds (widened as pq_gap widens it) is visited.
+// ---------------------------------------------------------------------------------------------------------
+struct BoxParams {
+    const float4* records;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* boxes;         // [n][2][3] world boxes, lo then hi (the grid kernel makes its own)
+    int32_t n;
+    const int64_t* offsets;     // the list kernel: [n + 1] (CSR rooms) or null: fixed rooms of max_hits
+    int32_t max_hits;
+    int32_t *instance, *triangle;   // the list kernel's keys, required; indexed by room slot
+    int32_t* count;             // optional, [n] (the offsets call: the workspace)
+    uint8_t* any;               // optional, [n] (the count and the grid kernel)
+    int32_t* pops;              // optional, [n]
+    float origin[3], spacing[3];    // the grid kernel: cell (ix, iy, iz) is origin + i*spacing .. origin + (i + 1)*spacing
+    int32_t dims[3];            // nx, ny, nz
+    uint32_t bricks[3];         // 4x4x4 bricks per axis
+};
+
+// corner k of the world box lo..hi (bit a of k set: hi on axis a) in instance in's scaled mesh space: apply_lre(pose, corner)
+__device__ __forceinline__ V3 bx_corner(V3 lo, V3 hi, const DevInstance& in, int k)
+{
+    return apply_quat(in.q_pose, v3(((k & 1) ? hi.x : lo.x) - in.pose_xyz[0], ((k & 2) ? hi.y : lo.y) - in.pose_xyz[1],
+                                    ((k & 4) ? hi.z : lo.z) - in.pose_xyz[2]));
+}
+__device__ __forceinline__ float bx_dot(V3 a, V3 x) { return (a.x * x.x + a.y * x.y) + a.z * x.z; }
+__device__ __forceinline__ V3 bx_cross(V3 u, V3 v) { return v3(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x); }
+
+// one axis of rule 11 step 5: whether it separates the box (corners r[0..7] relative to C0) from the triangle (ta, tb, tc); a zero
+// axis gives two intervals [0, 0], a NaN fails both compares: neither separates
+__device__ __forceinline__ bool bx_separates(V3 ax, const V3* r, V3 ta, V3 tb, V3 tc)
+{
+    float minb = bx_dot(ax, r[0]), maxb = minb;
+#pragma unroll
+    for (int k = 1; k < 8; k++) {
+        const float d = bx_dot(ax, r[k]);
+        minb = fminf(minb, d); maxb = fmaxf(maxb, d);
+    }
+    const float da = bx_dot(ax, ta), db = bx_dot(ax, tb), dc = bx_dot(ax, tc);
+    const float mint = fminf(fminf(da, db), dc), maxt = fmaxf(fmaxf(da, db), dc);
+    return maxt < minb || maxb < mint;
+}
+
+// Rule 11 steps 2, 3 and 5 for one pair that passed step 4: true when no axis separates.  The corners are mapped again here (the same
+// sequence as the traversal's bounds), and the whole test is out of line, so none of it occupies the traversal's registers.
+__device__ __noinline__ bool bx_axes(V3 lo, V3 hi, const DevInstance& in, V3 a, V3 b, V3 c)
+{
+    const V3 c0 = bx_corner(lo, hi, in, 0);
+    V3 r[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) r[k] = bx_corner(lo, hi, in, k) - c0;
+    const V3 ta = a - c0, tb = b - c0, tc = c - c0;
+    const V3 f0 = b - a, f1 = c - b, f2 = a - c;
+    if (bx_separates(r[1], r, ta, tb, tc) || bx_separates(r[2], r, ta, tb, tc) || bx_separates(r[4], r, ta, tb, tc)) return false;
+    if (bx_separates(bx_cross(f0, f1), r, ta, tb, tc)) return false;
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+        const V3 e = r[1 << m];
+        if (bx_separates(bx_cross(e, f0), r, ta, tb, tc) || bx_separates(bx_cross(e, f1), r, ta, tb, tc) ||
+            bx_separates(bx_cross(e, f2), r, ta, tb, tc))
+            return false;
+    }
+    return true;
+}
+
+// Every pair of the world box lo..hi, instance by instance in ascending order (triangles of one instance in tree order).  go(k) is
+// asked before instance k (false ends the traversal); pair(k, slot) is called at each pair and returns whether to end the traversal.
+// Returns the interior nodes visited.  An invalid box (an inverted axis or a NaN, rule 11 step 1) visits nothing.
+template <typename Go, typename Pair>
+__device__ __forceinline__ int32_t bx_trace(const BoxParams& p, TriStack& stack, V3 lo, V3 hi, Go&& go, Pair&& pair)
+{
+    int32_t pops = 0;
+    if (!(lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z)) return pops;
+    for (int32_t k = 0; k < p.num_instances; k++) {
+        if (!go(k)) break;
+        const DevInstance& in = p.instances[k];
+        V3 qlo = bx_corner(lo, hi, in, 0), qhi = qlo;           // rule 11 step 4's bounds of the mapped box: the chain over C0..C7
+#pragma unroll
+        for (int c = 1; c < 8; c++) {
+            const V3 q = bx_corner(lo, hi, in, c);
+            qlo = v3(fminf(qlo.x, q.x), fminf(qlo.y, q.y), fminf(qlo.z, q.z));
+            qhi = v3(fmaxf(qhi.x, q.x), fmaxf(qhi.y, q.y), fmaxf(qhi.z, q.z));
+        }
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        bool done = false;
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: every child whose box overlaps, no order
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const bool pa = !prune || ti_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, qlo, qhi);
+                const bool pb = !prune || ti_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, qlo, qhi);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                if (pa && pb) stack.push(rb);
+                cur = pa ? ra : (pb ? rb : kNeedPop);
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    V3 a, ab, ac;
+                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
+                    const V3 b = a + ab, c = a + ac;
+                    const V3 tlo = ti_min3(a, b, c), thi = ti_max3(a, b, c);
+                    // step 4 first (NaN fails); the thirteen axes only behind it
+                    if (tlo.x <= qhi.x && qlo.x <= thi.x && tlo.y <= qhi.y && qlo.y <= thi.y && tlo.z <= qhi.z && qlo.z <= thi.z) {
+                        if (bx_axes(lo, hi, in, a, b, c) && pair(k, slot)) done = true;
+                    }
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel && !done);
+        if (done) break;
+    }
+    return pops;
+}
+
+// ANY = false: the number of pairs of each box (rt_count_in_boxes, and rt_box_offsets' first step into the workspace).
+// ANY = true (any wanted, count not): the traversal ends at the first pair, across instances too.
+template <bool ANY>
+__global__ __launch_bounds__(kTriBlock, 8) void box_count_kernel(const BoxParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const float* B = p.boxes + (size_t)i * 6;
+    int32_t total = 0;
+    const int32_t pops = bx_trace(p, stack, v3(B[0], B[1], B[2]), v3(B[3], B[4], B[5]), [&](int32_t) { return true; },
+                                  [&](int32_t, int32_t) {
+        total++;
+        return ANY;
+    });
+    if (p.count) p.count[i] = total;
+    if (p.any) p.any[i] = total > 0 ? 1 : 0;
+    if (p.pops) p.pops[i] = pops;
+}
+
+// The count kernel on the cells of a grid, which it makes itself: a wave takes a 4x4x4 brick of cells (lane = x + 4y + 16z within the
+// brick), so its lanes walk the same part of the tree; lanes outside a partial brick do nothing.  Cell bounds are origin + (float)i *
+// spacing (the product rounded, then the sum), so neighbouring cells share their faces bit for bit.  Outputs [nz][ny][nx].
+template <bool ANY>
+__global__ __launch_bounds__(kTriBlock, 8) void box_grid_kernel(const BoxParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const uint32_t brick = blockIdx.y * gridDim.x + blockIdx.x;                     // (bricks <= cells <= INT32_MAX)
+    if (brick >= p.bricks[0] * p.bricks[1] * p.bricks[2]) return;
+    const uint32_t t = threadIdx.x, bxy = brick / p.bricks[0];
+    const int32_t ix = (int32_t)((brick - bxy * p.bricks[0]) * 4u + (t & 3u));
+    const int32_t iy = (int32_t)((bxy % p.bricks[1]) * 4u + ((t >> 2) & 3u));
+    const int32_t iz = (int32_t)((bxy / p.bricks[1]) * 4u + (t >> 4));
+    if (ix >= p.dims[0] || iy >= p.dims[1] || iz >= p.dims[2]) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const V3 lo = v3(p.origin[0] + (float)ix * p.spacing[0], p.origin[1] + (float)iy * p.spacing[1], p.origin[2] + (float)iz * p.spacing[2]);
+    const V3 hi = v3(p.origin[0] + (float)(ix + 1) * p.spacing[0], p.origin[1] + (float)(iy + 1) * p.spacing[1],
+                     p.origin[2] + (float)(iz + 1) * p.spacing[2]);
+    int32_t total = 0;
+    bx_trace(p, stack, lo, hi, [&](int32_t) { return true; }, [&](int32_t, int32_t) {
+        total++;
+        return ANY;
+    });
+    const size_t cell = ((size_t)iz * (size_t)p.dims[1] + (size_t)iy) * (size_t)p.dims[0] + (size_t)ix;   // (< cells <= INT32_MAX)
+    if (p.count) p.count[cell] = total;
+    if (p.any) p.any[cell] = total > 0 ? 1 : 0;
+}
+
+// A room's key at slot q as one number: (instance, triangle) compared as a pair (both >= 0 in a filled slot)
+__device__ __forceinline__ uint64_t bx_key(const BoxParams& p, size_t q)
+{
+    return ((uint64_t)(uint32_t)p.instance[q] << 32) | (uint64_t)(uint32_t)p.triangle[q];
+}
+__device__ __forceinline__ void bx_put(const BoxParams& p, size_t q, uint64_t key)
+{
+    p.instance[q] = (int32_t)(key >> 32);
+    p.triangle[q] = (int32_t)(uint32_t)key;
+}
+// `key` enters the max-heap of `size` slots at `start` from slot `pos` downwards: greater children move up until it fits
+__device__ __forceinline__ void bx_sift_down(const BoxParams& p, size_t start, uint64_t size, uint64_t pos, uint64_t key)
+{
+    for (;;) {
+        uint64_t child = 2 * pos + 1;
+        if (child >= size) break;
+        uint64_t ck = bx_key(p, start + (size_t)child);
+        if (child + 1 < size) {
+            const uint64_t c2 = bx_key(p, start + (size_t)child + 1);
+            if (c2 > ck) { ck = c2; child++; }
+        }
+        if (ck <= key) break;
+        bx_put(p, start + (size_t)pos, ck);
+        pos = child;
+    }
+    bx_put(p, start + (size_t)pos, key);
+}
+
+// One traversal; the room is kept as a max-heap of its keys (instance, triangle) while pairs arrive -- lane-private, no atomics --
+// and sorted in place at the end.  A box holds a volume's worth of triangles, so its lists are long where a query triangle's are
+// short: the heap takes a pair in O(log room) where intersect_list_kernel's shifting insertion takes O(room).  Until the room is full
+// a pair sifts up; a full room takes a pair only below its greatest key, the root, which leaves.  In fixed rooms without count the
+// traversal ends after the root's instance once the room is full: every later pair sorts after it (instances arrive in ascending
+// order).  Which keys stay does not depend on the order of arrival, so the rooms are the same bits with and without count and
+// whatever the tree.
+__global__ __launch_bounds__(kTriBlock, 8) void box_list_kernel(const BoxParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const float* B = p.boxes + (size_t)i * 6;
+    const bool early = !p.offsets && !p.count;
+    int32_t total = 0;
+    uint64_t filled = 0;                                        // (<= room)
+    const int32_t pops = bx_trace(p, stack, v3(B[0], B[1], B[2]), v3(B[3], B[4], B[5]), [&](int32_t k) {
+        if (!early || filled < (uint64_t)p.max_hits) return true;                   // (fixed rooms: start i*K, room K)
+        return k <= p.instance[(size_t)i * (size_t)p.max_hits];                     // (the root: the room's greatest key)
+    }, [&](int32_t k, int32_t slot) {
+        total++;
+        size_t start;
+        uint64_t room;
+        xl_room(p, i, start, room);                             // (read again per pair: not held across the traversal)
+        if (room == 0) return false;
+        const uint64_t key = ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)p.tri_id[slot];
+        if (filled < room) {                                    // sift up from the new last slot
+            uint64_t pos = filled++;
+            while (pos > 0) {
+                const uint64_t parent = (pos - 1) / 2, pk = bx_key(p, start + (size_t)parent);
+                if (pk >= key) break;
+                bx_put(p, start + (size_t)pos, pk);
+                pos = parent;
+            }
+            bx_put(p, start + (size_t)pos, key);
+        } else if (key < bx_key(p, start)) {                    // full: the root leaves
+            bx_sift_down(p, start, room, 0, key);
+        }
+        return false;
+    });
+    size_t start;
+    uint64_t room;
+    xl_room(p, i, start, room);
+    for (uint64_t end = filled; end > 1; end--) {               // heap -> ascending: the greatest key to the end, the rest a heap again
+        const uint64_t last = bx_key(p, start + (size_t)(end - 1));
+        bx_put(p, start + (size_t)(end - 1), bx_key(p, start));
+        bx_sift_down(p, start, end - 1, 0, last);
+    }
+    for (uint64_t j = filled; j < room; j++) {                  // padding
+        p.instance[start + (size_t)j] = -1;
+        p.triangle[start + (size_t)j] = -1;
+    }
+    if (p.count) p.count[i] = total;
+    if (p.pops) p.pops[i] = pops;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -5339,6 +5616,102 @@ int rt_list_intersecting(RtScene* s, const float* d_triangles, const int32_t* d_
         p.count = out->count; p.pops = out->pops;
         const QueryShape k = query_shape(n, kTriBlock, p.stack_depth);
         hipLaunchKernelGGL(intersect_list_kernel, k.groups, dim3(kTriBlock), k.lds, st, p);
+        return RT_OK;
+    });
+}
+
+// ---- boxes ------------------------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+BoxParams box_params(const RtScene* s, const float* d_boxes, int32_t n)
+{
+    BoxParams p = scene_params<BoxParams>(s);
+    p.tri_id = s->d_tri_id;
+    p.boxes = d_boxes; p.n = n;
+    return p;
+}
+void launch_box_count(const BoxParams& p, bool any_only, hipStream_t st)
+{
+    const QueryShape k = query_shape(p.n, kTriBlock, p.stack_depth);
+    if (any_only)
+        hipLaunchKernelGGL(box_count_kernel<true>, k.groups, dim3(kTriBlock), k.lds, st, p);
+    else
+        hipLaunchKernelGGL(box_count_kernel<false>, k.groups, dim3(kTriBlock), k.lds, st, p);
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_count_in_boxes(RtScene* s, const float* d_boxes, int32_t n, const RtBoxCounts* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_boxes || !out))) return RT_E_INVALID;
+    if (n > 0 && !(out->count || out->any || out->pops)) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        BoxParams p = box_params(s, d_boxes, n);
+        p.count = out->count; p.any = out->any; p.pops = out->pops;
+        launch_box_count(p, p.any && !p.count, st);             // (any without count: stop at the first pair)
+        return RT_OK;
+    });
+}
+
+size_t rt_box_offsets_workspace_bytes(int32_t n) { return offsets_workspace_bytes(n); }
+
+int rt_box_offsets(RtScene* s, const float* d_boxes, int32_t n, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes,
+                   void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_boxes || !d_offsets || !d_workspace))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
+    return query_offsets(s, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize, [&](int32_t* counts, hipStream_t st) {
+        BoxParams p = box_params(s, d_boxes, n);
+        p.count = counts;
+        launch_box_count(p, false, st);
+    });
+}
+
+int rt_list_in_boxes(RtScene* s, const float* d_boxes, int32_t n, const int64_t* d_offsets, int32_t max_hits, const RtBoxList* out,
+                     void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_boxes || !out))) return RT_E_INVALID;
+    if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
+    if (n > 0 && !(out->instance && out->triangle)) return RT_E_INVALID;     // the room holds the keys
+    if (n == 0) return RT_OK;
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        BoxParams p = box_params(s, d_boxes, n);
+        p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
+        p.instance = out->instance; p.triangle = out->triangle;
+        p.count = out->count; p.pops = out->pops;
+        const QueryShape k = query_shape(n, kTriBlock, p.stack_depth);
+        hipLaunchKernelGGL(box_list_kernel, k.groups, dim3(kTriBlock), k.lds, st, p);
+        return RT_OK;
+    });
+}
+
+int rt_occupancy_grid(RtScene* s, const float* origin, const float* spacing, const int32_t* dims, uint8_t* d_occupied, int32_t* d_count,
+                      void* stream, int synchronize)
+{
+    if (!s || !origin || !spacing || !dims) return RT_E_INVALID;
+    for (int a = 0; a < 3; a++)
+        if (dims[a] < 0 || dims[a] > (1 << 24)) return RT_E_INVALID;        // ((float)i is exact up to 2^24)
+    int64_t cells = (int64_t)dims[0] * dims[1], bricks = 1;      // (<= 2^48)
+    if (cells > (int64_t)INT32_MAX && dims[2] > 0) return RT_E_INVALID;
+    cells = dims[2] > 0 ? cells * dims[2] : 0;                   // (<= 2^55)
+    if (cells > (int64_t)INT32_MAX) return RT_E_INVALID;
+    for (int a = 0; a < 3; a++) bricks *= (dims[a] + 3) / 4;
+    if (cells > 0 && !(d_occupied || d_count)) return RT_E_INVALID;
+    if (cells == 0) return RT_OK;                                // nothing launched
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        BoxParams p = box_params(s, nullptr, (int32_t)cells);
+        for (int a = 0; a < 3; a++) {
+            p.origin[a] = origin[a]; p.spacing[a] = spacing[a]; p.dims[a] = dims[a];
+            p.bricks[a] = (uint32_t)((dims[a] + 3) / 4);
+        }
+        p.count = d_count; p.any = d_occupied;
+        const dim3 groups((unsigned)(bricks < 65536 ? bricks : 65536), (unsigned)((bricks + 65535) / 65536));    // (bricks <= cells)
+        const size_t lds = query_shape(1, kTriBlock, p.stack_depth).lds;
+        if (p.any && !p.count)                                   // (occupied without count: stop at the first pair)
+            hipLaunchKernelGGL(box_grid_kernel<true>, groups, dim3(kTriBlock), lds, st, p);
+        else
+            hipLaunchKernelGGL(box_grid_kernel<false>, groups, dim3(kTriBlock), lds, st, p);
         return RT_OK;
     });
 }

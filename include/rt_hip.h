@@ -660,6 +660,75 @@ int rt_intersecting_offsets(RtScene *scene, const float *d_triangles, const int3
 int rt_list_intersecting(RtScene *scene, const float *d_triangles, const int32_t *d_skip_instance, int32_t n, const int64_t *d_offsets,
                          int32_t max_hits, const RtIntersectList *out, void *stream, int synchronize);
 
+/* ---- box queries: every (instance, triangle) of the scene that meets a caller's world axis-aligned box, and
+ *      occupancy grids -- voxelisers, occupancy maps, culling by region.  The pairs equal a brute-force loop over every (instance,
+ *      triangle), whatever the tree (host-built, device-built, refitted) and whatever the traversal order.
+ *      11. For query box j with world lo[3], hi[3] (fp32) and instance i; every operation fp32 in one fixed sequence, no contraction:
+ *          1. Valid box: lo[a] <= hi[a] on all three axes.  A NaN or an inverted axis gives no pairs; lo == hi on an axis is a valid
+ *             flat box (so is a line and a point).
+ *          2. Corners: Ck = apply_lre(pose_i, corner_k), k = 0..7, rule 1's map into scaled mesh space; corner k takes hi on axis a
+ *             when bit a of k is set (bit 0 = x), else lo.  Rk = Ck - C0 per component (R0 = 0).  The box edges are Ex = R1, Ey = R2,
+ *             Ez = R4.
+ *          3. Scene triangle: A = v0*s, B = A + AB, C = A + AC as in rule 10 step 2.  TA = A - C0, TB = B - C0, TC = C - C0;
+ *             F0 = B - A, F1 = C - B, F2 = A - C.
+ *          4. Box pre-test: per axis loQ / hiQ are the fminf / fmaxf chain over C0..C7 in that order, loT / hiT over A, B, C as in
+ *             rule 10 step 3; the pair passes when loT <= hiQ && loQ <= hiT on all three axes (NaN fails).
+ *          5. Thirteen separating axes in this order: Ex, Ey, Ez; N = cross(F0, F1); cross(Em, Fn) for m = x, y, z (outer) and
+ *             n = 0, 1, 2 (inner).  cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x), each product rounded, then
+ *             subtracted.  The projection on axis a is p(X) = (a.x*X.x + a.y*X.y) + a.z*X.z.  The box interval is the min and max of
+ *             p(R0..R7), the triangle interval of p(TA), p(TB), p(TC), taken with fminf / fmaxf chains in the order given.  An axis
+ *             SEPARATES when maxT < minB or maxB < minT; a zero axis or a NaN never separates.
+ *          6. (i, triangle) is a PAIR of query j when step 1 holds, step 4 passes and no axis of step 5 separates.
+ *          7. ORDER: a query's pairs sorted by (instance, triangle) ascending.  ROOMS (CSR or fixed K), padding (instance = triangle
+ *             = -1) and "nothing is ever written outside a room" are rule 8's.
+ *          8. NON-FINITE boxes do not fault, do not change other queries' results and never write outside their room; their own
+ *             results are unspecified.
+ *      NOT PROMISED: the test is closed (touching counts) and decided in fp32: a box and a triangle nearer to each other than the
+ *      rounding of their coordinates can go either way.  Subtracting C0 keeps that rounding at the size of the box, not at the size
+ *      of the scene.  Under a pose that is not the identity the mapped corners carry the map's rounding, so "exactly on a face"
+ *      is decided in mesh space.
+ *      rt_count_in_boxes: count [n] (the number of pairs), any [n] (1 when there is one), pops [n] (interior nodes visited, a
+ *      statistic); all optional, at least one given.  With any and without count the traversal ends at the first pair, across
+ *      instances too.
+ *      rt_box_offsets writes offsets[0] = 0 and offsets[i+1] = offsets[i] + count_i (int64): the count traversal into the workspace,
+ *      then rt_crossing_offsets' exclusive scan on the device.  Its workspace is DEVICE memory of at least
+ *      rt_box_offsets_workspace_bytes(n) bytes (0 for n <= 0).  With n == 0 nothing is launched and d_offsets is not written.
+ *      rt_list_in_boxes fills the rooms: CSR (d_offsets) or fixed (d_offsets NULL, max_hits = K >= 1), as in rule 8.  instance and
+ *      triangle are REQUIRED (the room is where the keys live); count[n] is each query's FULL count.  In fixed rooms without count,
+ *      once a room is full the traversal ends after the instance of the room's last key; the rooms are the same bits with and without
+ *      count.
+ *      rt_occupancy_grid runs rt_count_in_boxes on the cells of a regular grid that the kernel makes itself (no box array): origin,
+ *      spacing [3] and dims [3] = (nx, ny, nz) are HOST arrays read during the call.  Cell (ix, iy, iz) is the box lo[a] = origin[a] +
+ *      (float)i_a*spacing[a], hi[a] = origin[a] + (float)(i_a + 1)*spacing[a] (the product rounded, then the sum), so neighbouring
+ *      cells share their faces bit for bit.  d_occupied (uint8) and d_count (int32) are [nz][ny][nx], x fastest, each optional, at
+ *      least one given; they are bit-equal to rt_count_in_boxes' any and count on those boxes, and occupied without count stops at the
+ *      first pair.  A negative spacing makes every cell an inverted box: all zeros.  A dimension of 0 launches nothing.
+ *      All calls: d_boxes is a DEVICE array [n][2][3], lo then hi; asynchronous on `stream` unless synchronize != 0; no host
+ *      synchronisation, allocation or scene scratch (calls may overlap each other and renders); nothing launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL boxes with n > 0; rt_count_in_boxes: NULL out or no output with n > 0; rt_box_offsets:
+ *      d_offsets or d_workspace NULL, or a workspace too small, with n > 0; rt_list_in_boxes: NULL out, or instance or triangle NULL,
+ *      with n > 0; both or neither of d_offsets and max_hits >= 1; rt_occupancy_grid: NULL origin, spacing or dims, a negative
+ *      dimension, a dimension above 2^24, more than INT32_MAX cells, no output with at least one cell. ------------------------- */
+typedef struct RtBoxCounts {        /* every pointer optional, at least one given                                              */
+    int32_t *count;             /* [n] the number of pairs                                                                 */
+    uint8_t *any;               /* [n] 1 when the query has a pair                                                         */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic, not part of the exact contract)                */
+} RtBoxCounts;
+typedef struct RtBoxList {          /* fields indexed by room slot; instance and triangle REQUIRED, the rest optional          */
+    int32_t *instance;          /* [slots] -1 = padding                                                                    */
+    int32_t *triangle;          /* [slots] the uploaded numbering; -1 = padding                                            */
+    int32_t *count;             /* [n] the full number of pairs of each query                                              */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic)                                                */
+} RtBoxList;
+int rt_count_in_boxes(RtScene *scene, const float *d_boxes, int32_t n, const RtBoxCounts *out, void *stream, int synchronize);
+size_t rt_box_offsets_workspace_bytes(int32_t n);
+int rt_box_offsets(RtScene *scene, const float *d_boxes, int32_t n, int64_t *d_offsets, void *d_workspace, size_t workspace_bytes,
+                   void *stream, int synchronize);
+int rt_list_in_boxes(RtScene *scene, const float *d_boxes, int32_t n, const int64_t *d_offsets, int32_t max_hits, const RtBoxList *out,
+                     void *stream, int synchronize);
+int rt_occupancy_grid(RtScene *scene, const float *origin, const float *spacing, const int32_t *dims, uint8_t *d_occupied,
+                      int32_t *d_count, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);

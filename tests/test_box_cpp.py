@@ -1,0 +1,41 @@
+"""Scene::count_in_boxes / Scene::box_offsets / Scene::list_in_boxes / Scene::occupancy_grid (cuda-raytracing_amd/csrc/host/) compile and
+link against the two libraries as a C++ user sees them, and refuse to run without a device scene (no GPU is touched)."""
+import os
+import subprocess
+
+from test_host_cpp_api import _gxx
+
+PROGRAM = r"""
+#include <cstdio>
+#include "Scene.h"
+#include "rt_hip.h"
+int main()
+{
+    Scene scene;                                   // never uploaded: no device scene
+    RtBoxCounts counts = {};
+    int32_t count[4];
+    counts.count = count;
+    RtBoxList out = {};
+    int32_t instance[8], triangle[8];
+    out.instance = instance; out.triangle = triangle;
+    const size_t ws = rt_box_offsets_workspace_bytes(4);
+    const float origin[3] = {0, 0, 0}, spacing[3] = {1, 1, 1};
+    const int32_t dims[3] = {2, 2, 1};
+    uint8_t occupied[4];
+    const int a = scene.count_in_boxes(nullptr, 4, counts);
+    const int b = scene.box_offsets(nullptr, 4, nullptr, nullptr, ws);
+    const int c = scene.list_in_boxes(nullptr, 4, nullptr, 2, out);
+    const int d = scene.occupancy_grid(origin, spacing, dims, occupied, count);
+    printf("%d %d %d %d %d %d\n", a, b, c, d, scene.last_error, ws > 0 ? 1 : 0);
+    return 0;
+}
+"""
+
+
+def test_scene_members_compile_link_and_refuse_without_device(rt, tmp_path):
+    src, exe = tmp_path / "boxes.cpp", tmp_path / "boxes"
+    src.write_text(PROGRAM)
+    _gxx(str(src), str(exe))
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=dict(os.environ, HIP_VISIBLE_DEVICES=""))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == ["-1", "-1", "-1", "-1", "-1", "1"], r.stdout
