@@ -139,3 +139,17 @@ def grid_boxes(origin, spacing, dims):
         b[..., 0, a] = edge[a][:-1].reshape(shape)
         b[..., 1, a] = edge[a][1:].reshape(shape)
     return b
+
+
+def grid_cells(origin, spacing, dims, cells):
+    """grid_boxes' boxes [m, 2, 3] of the cells with flat indices `cells` ((iz * ny + iy) * nx + ix) alone, by the same formula: for
+    grids too large to make whole"""
+    o, s = np.asarray(origin, np.float32), np.asarray(spacing, np.float32)
+    nx, ny, nz = (int(d) for d in dims)
+    c = np.asarray(cells, np.int64).reshape(-1)
+    assert c.size == 0 or (0 <= c.min() and c.max() < nx * ny * nz)
+    b = np.zeros((len(c), 2, 3), np.float32)
+    for a, i in enumerate((c % nx, c // nx % ny, c // (nx * ny))):
+        b[:, 0, a] = o[a] + i.astype(np.float32) * s[a]
+        b[:, 1, a] = o[a] + (i + 1).astype(np.float32) * s[a]
+    return b

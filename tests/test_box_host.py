@@ -87,6 +87,17 @@ def test_shared_face_through_a_scene_and_the_grid_formula(orc):
         so.close()
 
 
+def test_grid_cells_are_grid_boxes_at_flat_indices():
+    """the helper for grids too large to make whole: any subset of cells, in any order, and the last index of a 2^24 axis"""
+    o, s, dims = (0.1, 0.2, 0.3), (0.1, 0.13, 0.17), (9, 7, 5)
+    g = bo.grid_boxes(o, s, dims).reshape(-1, 2, 3)
+    idx = np.random.default_rng(5).permutation(len(g))[:100]
+    assert np.array_equal(bo.grid_cells(o, s, dims, np.arange(len(g))), g) and np.array_equal(bo.grid_cells(o, s, dims, idx), g[idx])
+    last = bo.grid_cells((-1, 0, 0), (1.2e-7, 1, 1), (2 ** 24, 1, 1), [2 ** 24 - 1])[0]
+    assert last[0, 0] == F32(-1) + F32(2 ** 24 - 1) * F32(1.2e-7) and last[1, 0] == F32(-1) + F32(2 ** 24) * F32(1.2e-7)
+    assert last.dtype == F32 and last[:, 1].tolist() == [0, 1]
+
+
 def test_vertex_exactly_on_a_corner():
     tri = np.array([(1, 1, 1), (2, 1.5, 1.2), (1.5, 2, 1.7)], F32)
     assert bo.pair(UNIT, tri) == (True, "pair")

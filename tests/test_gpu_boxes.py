@@ -1,7 +1,8 @@
 """Box queries on the GPU (Scene.count_in_boxes / Scene.list_in_boxes / Scene.occupancy_grid through rt_count_in_boxes / rt_box_offsets /
 rt_list_in_boxes / rt_occupancy_grid): every field equals the brute-force shim (tests/box_oracle.c) bit for bit on the library's and
 adversarial scenes, under every tree and scene change, in CSR and fixed rooms with and without count, nothing outside a room is ever
-written, and the grid equals count_in_boxes on its cells."""
+written, and the grid equals count_in_boxes on its cells.  Sizes are small here: the scan's edges, rooms at slots past 2^31, grids of
+more than 65536 bricks and the 2^24 axis are test_gpu_query_scale.py's, threads test_gpu_query_threads.py's."""
 import ctypes as C
 
 import numpy as np

@@ -1,16 +1,20 @@
 """What the query families share, at the sizes where it can go wrong (the arithmetic of each family is test_gpu_crossing_list.py's,
-test_gpu_nearby.py's and test_gpu_tri_intersect.py's business): the CSR scan behind the three *_offsets calls at its block edges and on
-its three-level path, totals and room positions past 2^31 and 2^32, and every query kernel with a partly filled last workgroup on the
-deep scene.  The C-ABI is called directly on torch buffers: the Python wrappers would allocate `total` rows.
+test_gpu_nearby.py's, test_gpu_tri_intersect.py's and test_gpu_boxes.py's business): the CSR scan behind the four *_offsets calls
+(crossing, nearby, intersecting, box) at its block edges and on its three-level path, totals and room positions past 2^31 and 2^32,
+the box list's heap rooms at slots past 2^31 and 2^32, occupancy grids that need the grid kernel's second launch row and its
+limit of 2^24 cells on an axis, and every query kernel with a partly filled last workgroup on the deep scene.  The C-ABI is called
+directly on torch buffers: the Python wrappers would allocate `total` rows.
 
 Every offsets check compares with np.concatenate([[0], np.cumsum(counts)]) of the CPU shims' counts (crossing_oracle, nearby_oracle,
-tri_intersect_oracle), never with the library's own counts.  Every buffer a kernel may write is allocated at its full size; the large
-cases read back small windows only."""
+tri_intersect_oracle, box_oracle), never with the library's own counts.  Every buffer a kernel may write is allocated at its full
+size; the large cases read back small windows only.  Totals beyond 2^32 are not repeated for boxes: the scan and its 64-bit sums are
+one piece of code for all four families, tested through rt_crossing_offsets below."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import box_oracle as bo
 import crossing_list_oracle as xl
 import crossing_oracle as xo
 import nearby_oracle as nb
@@ -28,7 +32,7 @@ F32 = np.float32
 SCAN_BLOCK = 1024                                               # elements per block of the scan over n + 1 offsets (kScanBlock)
 GUARD = 0x5A
 GUARD64 = int.from_bytes(bytes([GUARD]) * 8, "little")
-FAMILIES = ("crossing", "nearby", "intersecting")
+FAMILIES = ("crossing", "nearby", "intersecting", "box")
 
 
 def _cumsum(counts):
@@ -54,6 +58,8 @@ def _call_offsets(h, family, handle, q, n, off, ws, ws_bytes):
         return h.rt_crossing_offsets(handle, a, b, None, n, off, ws, ws_bytes, None, 1)
     if family == "nearby":
         return h.rt_nearby_offsets(handle, a, b, n, off, ws, ws_bytes, None, 1)
+    if family == "box":
+        return h.rt_box_offsets(handle, a, n, off, ws, ws_bytes, None, 1)
     return h.rt_intersecting_offsets(handle, a, b, n, off, ws, ws_bytes, None, 1)
 
 
@@ -159,9 +165,12 @@ def pools(orc, multi):
     tris = np.concatenate([f[1] for f in tri_families(rng, orc.oracle(), multi.desc, n=400)])
     tris = np.ascontiguousarray(tris[rng.permutation(len(tris))[:POOL]], F32)
     assert len(tris) == POOL
+    bc, be = rng.uniform(-1.5, 1.5, (POOL, 3)), rng.uniform(0.02, 0.3, (POOL, 3))
+    boxes = np.ascontiguousarray(np.stack([bc - be / 2, bc + be / 2], axis=1), F32)
     out = {"crossing": ((o, d), xo.count_crossings(multi.so, o, d)["count"]),
            "nearby": ((pts, md), nb.count_nearby(multi.so, pts, md)),
-           "intersecting": ((tris, None), ti.count_intersecting(multi.so, tris))}
+           "intersecting": ((tris, None), ti.count_intersecting(multi.so, tris)),
+           "box": ((boxes, None), bo.count_in_boxes(multi.so, boxes))}
     for family, (_q, c) in out.items():
         assert (c > 0).sum() >= 16 and (c == 0).sum() >= 16, (family, int((c > 0).sum()))
     return out
@@ -213,9 +222,12 @@ def cube_queries(cube):
     md = rng.uniform(0.05, 0.5, DISTINCT).astype(F32)
     cen = rng.uniform(-0.3, 1.3, (DISTINCT, 1, 3))
     tris = np.ascontiguousarray(cen + rng.normal(size=(DISTINCT, 3, 3)) * 0.15, F32)
+    bc, be = rng.uniform(-0.5, 1.5, (DISTINCT, 3)), rng.uniform(0.05, 0.5, (DISTINCT, 3))
+    boxes = np.ascontiguousarray(np.stack([bc - be / 2, bc + be / 2], axis=1), F32)
     return {"crossing": ((o, d), xo.count_crossings(cube.so, o, d)["count"]),
             "nearby": ((pts, md), nb.count_nearby(cube.so, pts, md)),
-            "intersecting": ((tris, None), ti.count_intersecting(cube.so, tris))}
+            "intersecting": ((tris, None), ti.count_intersecting(cube.so, tris)),
+            "box": ((boxes, None), bo.count_in_boxes(cube.so, boxes))}
 
 
 def _tiled(pool, n):
@@ -253,9 +265,10 @@ def test_three_level_scan_crossing(rt, cube, cube_queries, n):
     _same_offsets(got, _cumsum(counts), "crossing n=%d" % n)
 
 
-@pytest.mark.parametrize("family", ["nearby", "intersecting"])
+@pytest.mark.parametrize("family", ["nearby", "intersecting", "box"])
 def test_three_level_scan_other_families(rt, cube, cube_queries, family):
-    """The same at n = 2^20 + 1 through rt_nearby_offsets and rt_intersecting_offsets: one scan, but each family's own count launch"""
+    """The same at n = 2^20 + 1 through rt_nearby_offsets, rt_intersecting_offsets and rt_box_offsets: one scan, but each family's own
+    count launch"""
     _three_levels(rt, cube, cube_queries, family, 2 ** 20 + 1)
 
 
@@ -366,6 +379,251 @@ def test_fixed_rooms_beyond_31_bits(rt, cube):
         del buf
         torch.cuda.empty_cache()
 
+
+# ---- B4b: the box list's heap rooms at slots beyond 2^31 and 2^32 ----------------------------------------------------------------
+GUARD32 = int(np.frombuffer(bytes([GUARD]) * 4, np.int32)[0])
+QUADS = 1200                                                    # the stack scene: quad k at z = float32(k) * float32(0.01), twice
+
+
+def _slab(a, b):
+    """the box over the whole footprint of the stack's quads a..b: 2 triangles of 2 instances each, 4 * (b - a + 1) pairs"""
+    return np.array([[-0.5, -0.5, a * 0.01 - 0.005], [1.5, 1.5, b * 0.01 + 0.005]], F32)
+
+
+def _thin(rng, m):
+    """m small boxes 0.004 thick in z somewhere in and around the stack: most hold one quad's triangles or none"""
+    c = np.concatenate([rng.uniform(0.1, 0.9, (m, 2)), rng.uniform(-0.5, 12.5, (m, 1))], axis=1)
+    e = np.concatenate([rng.uniform(0.02, 0.3, (m, 2)), np.full((m, 1), 0.004)], axis=1)
+    return np.stack([c - e / 2, c + e / 2], axis=1).astype(F32)
+
+
+FAR_BOX = np.array([[50, 50, 50], [51, 51, 51]], F32)
+
+
+def _box_list(rt, handle, boxes, n, offsets_ptr, max_hits, inst, tri, cnt):
+    """rt_list_in_boxes on device buffers, synchronous on the NULL stream"""
+    import torch
+    lst = rt.RtBoxList(inst.data_ptr(), tri.data_ptr(), None if cnt is None else cnt.data_ptr(), None)
+    torch.cuda.synchronize()
+    return rt.libs()[0].rt_list_in_boxes(handle, boxes.data_ptr(), n, offsets_ptr, max_hits, C.byref(lst), None, 1)
+
+
+def _csr_boxes():
+    """400 boxes on the quad stack, shuffled: one of 1200 pairs, two of 400, four of 100, 150 far off and 243 thin ones -> (boxes,
+    rooms below, at and above each count, two of the large ones at half their count, some of 0)"""
+    rng = np.random.default_rng(67)
+    big = [_slab(100, 399), _slab(500, 599), _slab(700, 799)] + [_slab(a, a + 24) for a in (0, 450, 900, 1175)]
+    boxes = np.concatenate([np.stack(big), np.tile(FAR_BOX, (150, 1, 1)), _thin(rng, 243)])
+    boxes = np.ascontiguousarray(boxes[rng.permutation(len(boxes))])
+    return boxes, rng
+
+
+@pytest.mark.parametrize("base", [2 ** 31 + 5, 2 ** 32 + 5])
+def test_box_csr_rooms_beyond_32_bits(rt, stack, base):
+    """test_csr_rooms_beyond_32_bits for rt_list_in_boxes, whose rooms are max-heaps with 64-bit slot arithmetic of their own (bx_key,
+    bx_put, bx_sift_down, the final heap sort): 400 boxes on the quad stack with hand-made offsets base + cumsum(room), counted in
+    int32 slots, rooms below, at and above each count (two deep heaps at half their count, so most arrivals replace the root).  The
+    lists run to 1200 keys.  Both key arrays' windows around the rooms equal the shim's rooms, guard words 64 either side included,
+    and the first 4096 slots of each array (where a start cut to 32 bits would land) keep their guards.  count equals the shim's."""
+    import torch
+    boxes, rng = _csr_boxes()
+    n = len(boxes)
+    c = bo.count_in_boxes(stack.so, boxes).astype(np.int64)
+    assert c.max() == 1200 and (c >= 400).sum() == 3 and (c >= 100).sum() == 7 and (c == 0).sum() > 150 and ((c > 0) & (c <= 4)).sum() > 50
+    room = np.maximum(c + rng.integers(-1, 3, n), 0)
+    half = np.flatnonzero(c == 400)
+    room[half] = c[half] // 2
+    assert (room < c).any() and (room > c).any() and (room == c).any() and (room == 0).any()
+    rooms = int(room.sum())
+    assert rooms + 5 + 64 <= 4096                               # (offsets mod 2^32 fall inside the head window)
+    offsets = (base + _cumsum(room)).astype(np.int64)
+    nslots = base + rooms + 64
+    _need_memory(2 * 4 * nslots)
+    lo, hi = base - 64, base + rooms + 64
+    ref = bo.rooms(stack.so, boxes, offsets=offsets - lo, slots=hi - lo, fill=GUARD32)
+    bufs = None
+    try:
+        bufs = {k: torch.empty(nslots, dtype=torch.int32, device="cuda") for k in bo.FIELDS}
+        for b in bufs.values():
+            b[lo:hi].fill_(GUARD32)
+            b[:4096].fill_(GUARD32)
+        cnt = torch.full((n,), -9, dtype=torch.int32, device="cuda")
+        doff = torch.from_numpy(offsets).cuda()
+        bt, = _up((boxes,))
+        assert _box_list(rt, stack.handle, bt, n, doff.data_ptr(), 0, bufs["instance"], bufs["triangle"], cnt) == 0
+        for k in bo.FIELDS:
+            window, head = bufs[k][lo:hi].cpu().numpy(), bufs[k][:4096].cpu().numpy()
+            assert (head == GUARD32).all(), "%s: %d of the array's first 4096 slots were written" % (k, int((head != GUARD32).sum()))
+            _eq(window, ref[k], "%s rooms at slot %d" % (k, base))
+        _eq(cnt.cpu().numpy(), ref["count"], "count")
+    finally:
+        del bufs
+        torch.cuda.empty_cache()
+
+
+def test_box_fixed_rooms_beyond_31_bits(rt, stack):
+    """max_hits = 2049 and n = 2^20 + 64 on the quad stack: the rooms of the last 64 boxes, the only ones with pairs, start beyond
+    slot 2^31 of both key arrays and equal the shim's fixed rooms, with count and without it.  Their counts lie below K, between K
+    and the scene's 4800, and at 4800; 16 of them fill their room from instance 0 alone, so the run without count asks `go` before
+    instance 1 with a full room and reads the room's root at slot i * K > 2^31.  (That read cannot change a room: a full room's keys
+    all come from earlier instances, so a correct read always ends the traversal, and a wrong one that goes on finds the same keys.
+    What the run shows is that the read stays inside the array and the rooms are right.)  The rooms of a sample of the other boxes
+    (the first, the last, and those around slot 2^31) are all padding."""
+    import torch
+    K, n = 2049, 2 ** 20 + 64
+    rng = np.random.default_rng(71)
+    few, mid, full = rng.integers(100, 500, 16), rng.integers(520, 1000, 16), rng.integers(1030, 1190, 16)
+    last = [_slab(int(a), int(a + m - 1)) for m in np.concatenate([few, mid, full]) for a in [rng.integers(0, QUADS - m)]]
+    last = np.concatenate([np.stack(last), _thin(rng, 15), _slab(-10, QUADS + 10)[None]])
+    last = np.ascontiguousarray(last[rng.permutation(64)])
+    boxes = np.tile(FAR_BOX, (n, 1, 1))
+    boxes[-64:] = last
+    ref = bo.rooms(stack.so, last, max_hits=K)
+    c = ref["count"]
+    assert ((c > 0) & (c < K)).sum() >= 16 and ((c >= K) & (c < 4 * QUADS)).sum() >= 32 and (c == 4 * QUADS).sum() == 1, c
+    assert (c // 2 >= K).sum() >= 16 and (n - 64) * K > 2 ** 31
+    assert (bo.count_in_boxes(stack.so, boxes[:64]) == 0).all()
+    _need_memory(2 * 4 * n * K)
+    bufs = None
+    try:
+        bufs = {k: torch.empty(n * K, dtype=torch.int32, device="cuda") for k in bo.FIELDS}
+        sample = sorted({0, 1, 63, 64, 2 ** 19, 2 ** 31 // K - 1, 2 ** 31 // K, 2 ** 31 // K + 1, n - 66, n - 65})
+        bt, = _up((boxes,))
+        for with_count in (True, False):
+            at = "with count" if with_count else "without count"
+            for b in bufs.values():
+                for i in sample:
+                    b[i * K:(i + 1) * K].fill_(GUARD32)
+                b[(n - 64) * K:].fill_(GUARD32)
+            cnt = torch.full((n,), -9, dtype=torch.int32, device="cuda") if with_count else None
+            assert _box_list(rt, stack.handle, bt, n, None, K, bufs["instance"], bufs["triangle"], cnt) == 0
+            for k in bo.FIELDS:
+                _eq(bufs[k][(n - 64) * K:].cpu().numpy(), ref[k], "%s of the last 64 rooms, %s" % (k, at))
+                for i in sample:
+                    room = bufs[k][i * K:(i + 1) * K].cpu().numpy()
+                    assert (room == -1).all(), "%s of room %d (a box without pairs), %s: %d slots are not padding" % (
+                        k, i, at, int((room != -1).sum()))
+            if with_count:
+                got = cnt.cpu().numpy()
+                _eq(got[-64:], c, "count of the last 64")
+                assert (got[:-64] == 0).all()
+    finally:
+        del bufs
+        torch.cuda.empty_cache()
+
+
+# ---- B4c: occupancy grids on the grid kernel's second launch row and at 2^24 cells on an axis ---------------------------------------
+ROW = 65536                                                     # bricks per launch row of rt_occupancy_grid (blockIdx.y counts rows)
+GRIDS = {
+    # the cube's top face z = 1 lies in the last brick's second cell; the column stands inside the cube in x and y
+    "A": dict(dims=(1, 1, 262148), spacing=(0.37, 0.37, 0.0003), origin=(0.3, 0.3, 1 - 262145.5 * 0.0003), mix=1),
+    # the top face lies in the last layer iz = 65536, the only one of bricks 65536..65539: 25 cells, 12 over the face and 13 beside it
+    "B": dict(dims=(5, 5, 65537), spacing=(0.37, 0.47, 0.0003), origin=(-0.5, -0.6, 1 - 65536.5 * 0.0003), mix=8),
+}
+
+
+def _brick_of_cells(dims):
+    """the launch's brick index of every cell, [nz, ny, nx]"""
+    nx, ny, nz = dims
+    bx, by = (nx + 3) // 4, (ny + 3) // 4
+    iz, iy, ix = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    return (iz // 4 * by + iy // 4) * bx + ix // 4
+
+
+def _grid_raw(rt, handle, origin, spacing, dims, outputs):
+    """rt_occupancy_grid straight through the C-ABI into buffers with a brick of guard cells either side -> dict of flat arrays"""
+    import torch
+    cells = int(np.prod(dims, dtype=np.int64))
+    occ = torch.full((cells + 128,), GUARD, dtype=torch.uint8, device="cuda") if "occupied" in outputs else None
+    cnt = torch.full((cells + 128,), -9, dtype=torch.int32, device="cuda") if "count" in outputs else None
+    o, s, d = (C.c_float * 3)(*origin), (C.c_float * 3)(*spacing), (C.c_int32 * 3)(*dims)
+    torch.cuda.synchronize()
+    rc = rt.libs()[0].rt_occupancy_grid(handle, o, s, d, None if occ is None else occ.data_ptr() + 64,
+                                        None if cnt is None else cnt.data_ptr() + 4 * 64, None, 1)
+    assert rc == 0, rc
+    out = {}
+    for k, t, g in (("occupied", occ, GUARD), ("count", cnt, -9)):
+        if t is not None:
+            a = t.cpu().numpy()
+            assert (a[:64] == g).all() and (a[64 + cells:] == g).all(), "%s: cells outside the grid %s were written" % (k, dims)
+            out[k] = a[64:64 + cells]
+    return out
+
+
+@pytest.mark.parametrize("case", sorted(GRIDS))
+def test_occupancy_grid_on_the_second_launch_row(rt, cube, case):
+    """rt_occupancy_grid launches min(bricks, 65536) x ceil(bricks / 65536) workgroups and rebuilds the brick from both indices.
+    A: (1, 1, 262148), 65537 bricks, the fewest cells with a brick (one, of four cells) in the second row.  B: (5, 5, 65537),
+    2 x 2 x 16385 = 65540 bricks, partial on every axis, four of them (the 25 cells of the last layer) in the second row.  The spacing
+    is not representable; the cube's top face lies in the last cells, so the second row's cells hold both kinds: in A at least one
+    cell with a count above 0 and one with 0, in B at least 8 of each (the 16 of each that the first row's cells give cannot be asked
+    of 25 cells), and the same mix holds below brick 65536.  count with occupied, and occupied alone (the kernel that stops at the
+    first pair), equal the shim's count_in_boxes over ALL cells made by grid_boxes -- through the C-ABI into buffers guarded a brick
+    either side, whose guards stay, through the numpy path and through the torch path."""
+    g = GRIDS[case]
+    dims = g["dims"]
+    origin, spacing = np.asarray(g["origin"], F32), np.asarray(g["spacing"], F32)
+    assert all(float(F32(x)) != x for x in g["spacing"])
+    bricks = int(np.prod([(d + 3) // 4 for d in dims]))
+    assert ROW < bricks <= ROW + 4
+    ref = bo.count_in_boxes(cube.so, bo.grid_boxes(origin, spacing, dims), threads=16).reshape(dims[::-1])
+    second = _brick_of_cells(dims) >= ROW
+    assert second.sum() == {"A": 4, "B": 25}[case]
+    for where, m, want in (("second row", second, g["mix"]), ("first row", ~second, 16 if case == "B" else 1)):
+        assert (ref[m] > 0).sum() >= want and (ref[m] == 0).sum() >= want, (case, where, int((ref[m] > 0).sum()), int(m.sum()))
+    both = _grid_raw(rt, cube.handle, origin, spacing, dims, ("occupied", "count"))
+    _eq(both["count"].reshape(ref.shape), ref, "grid %s count" % case)
+    assert np.array_equal(both["occupied"].reshape(ref.shape), (ref > 0).astype(np.uint8)), "grid %s occupied beside count" % case
+    alone = _grid_raw(rt, cube.handle, origin, spacing, dims, ("occupied",))
+    assert np.array_equal(alone["occupied"].reshape(ref.shape), (ref > 0).astype(np.uint8)), "grid %s occupied alone" % case
+    r = cube.sp.occupancy_grid(origin, spacing, dims, outputs=("occupied", "count"), as_numpy=True)
+    _eq(r["count"], ref, "grid %s count (numpy path)" % case)
+    assert np.array_equal(r["occupied"], ref > 0)
+    r = cube.sp.occupancy_grid(origin, spacing, dims, as_numpy=True)
+    assert np.array_equal(r["occupied"], ref > 0), "grid %s occupied alone (numpy path)" % case
+    t = cube.sp.occupancy_grid(origin, spacing, dims, outputs=("occupied", "count"))
+    _eq(t["count"].cpu().numpy(), ref, "grid %s count (torch path)" % case)
+    assert np.array_equal(t["occupied"].cpu().numpy(), ref > 0)
+    t = cube.sp.occupancy_grid(origin, spacing, dims)
+    assert np.array_equal(t["occupied"].cpu().numpy(), ref > 0), "grid %s occupied alone (torch path)" % case
+
+
+def test_occupancy_grid_at_the_axis_limit(rt, cube):
+    """dims = (2^24, 1, 1), the documented maximum of an axis: 4 194 304 bricks in 64 launch rows, and (float)(ix + 1) reaches 2^24.
+    The row of cells runs along x inside the cube in y and z; the spacing (1.2e-7, a few units in the last place of the cells'
+    bounds, so many cells are planes) is not representable; the face x = 0 falls mid-grid and x = 1 in the last 64 cells.  The shim
+    needs minutes for 2^24 cells, so the whole GPU output is compared with it on a subset: the first and the last 65536 cells, 2^18
+    cells drawn with a fixed seed, and every cell within 64 of a cell the GPU reports as non-empty.  The GPU reports at most 1024
+    such cells, so each of them is checked against the shim, and so are the cells where the shim expects them (the last 64, and the
+    other face's).  Cells outside the subset are only known to be empty on the GPU: the shim was not asked about them, because asking
+    it about all of them is what takes minutes; a cell the kernel wrongly reports empty far from every face would go unseen unless
+    the 2^18 drawn cells hit it."""
+    dims = (2 ** 24, 1, 1)
+    cells = dims[0]
+    spacing = np.asarray((1.2e-7, 0.37, 0.37), F32)
+    origin = np.asarray((1 - (cells - 32) * 1.2e-7, 0.3, 0.3), F32)
+    assert float(spacing[0]) != 1.2e-7
+    rng = np.random.default_rng(73)
+    fixed = np.unique(np.concatenate([np.arange(ROW), np.arange(cells - ROW, cells), rng.integers(0, cells, 2 ** 18)]))
+    fixed_ref = bo.count_in_boxes(cube.so, bo.grid_cells(origin, spacing, dims, fixed), threads=16)
+    assert (fixed_ref[fixed >= cells - 64] > 0).any(), "the shim finds no face in the last 64 cells"
+
+    def check(got, where):
+        filled = np.flatnonzero(got["occupied"])
+        if "count" in got:
+            assert np.array_equal(got["occupied"] == 1, got["count"] > 0), where + ": occupied is not count > 0 on all cells"
+        assert len(filled) <= 1024, "%s: %d cells are reported non-empty" % (where, len(filled))
+        near = np.unique((filled[:, None] + np.arange(-64, 65)[None, :]).ravel())
+        near = near[(near >= 0) & (near < cells)]
+        near_ref = bo.count_in_boxes(cube.so, bo.grid_cells(origin, spacing, dims, near), threads=16)
+        assert (near_ref[near < cells - 64] > 0).any(), where + ": the shim finds no face before the last 64 cells"
+        for sub, ref, what in ((fixed, fixed_ref, "the fixed subset"), (near, near_ref, "the cells near a non-empty one")):
+            if "count" in got:
+                _eq(got["count"][sub], ref, "%s count on %s" % (where, what))
+            assert np.array_equal(got["occupied"][sub] == 1, ref > 0), "%s occupied on %s" % (where, what)
+
+    check(_grid_raw(rt, cube.handle, origin, spacing, dims, ("occupied", "count")), "count and occupied")
+    check(_grid_raw(rt, cube.handle, origin, spacing, dims, ("occupied",)), "occupied alone")
 
 # ---- B5: a partly filled last workgroup on the deep scene -------------------------------------------------------------------------
 @pytest.fixture(scope="module")

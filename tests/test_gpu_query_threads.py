@@ -1,5 +1,5 @@
-"""Every query family on ONE scene from six host threads at once, beside renders, instance updates, refits and a device-resident
-rebuild ("Threads"): the entry points share scene_launch, which takes the scene's call lock for the launches of
+"""Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes) on ONE scene from seven host threads at
+once, beside renders, instance updates, refits and a device-resident rebuild ("Threads"): the entry points share scene_launch, which takes the scene's call lock for the launches of
 one call (two nested calls for rt_signed_distance, a count launch and the scan's launches for the *_offsets calls) and leaves it before
 any wait.  test_gpu_threads.test_four_threads_on_one_scene, whose phase scheme and helpers this reuses, predates the families and
 queries with rt_trace_rays and rt_occluded only.  Every result of every call is compared bit for bit with the CPU shims' result for the
@@ -10,6 +10,7 @@ import threading
 import numpy as np
 import pytest
 
+import box_oracle as bo
 import crossing_list_oracle as xl
 import crossing_oracle as xo
 import nearby_oracle as nb
@@ -18,6 +19,7 @@ import query_points as qp
 import query_rays as qr
 import scene_defs as sd
 import tri_intersect_oracle as ti
+from test_gpu_boxes import families as box_families
 from test_gpu_crossings import _cam, _eq
 from test_gpu_threads import _Threads, _deformed, _host_arrays, _params, _render_batch_fn, _same_frame
 from test_gpu_tri_intersect import families as tri_families
@@ -28,12 +30,15 @@ _f = C.POINTER(C.c_float)
 POINT_FIELDS = ("distance", "instance", "triangle", "point", "normal", "barycentric", "uv")
 XL_FIELDS = ("t", "instance", "triangle", "sign", "barycentric", "uv", "point")
 TI_FIELDS = ("instance", "triangle", "normal", "segment")
-WORKERS = ("W1", "W2", "W3", "W4", "W5", "W6")
+BX_FIELDS = ("instance", "triangle")
+GRID_DIMS = (5, 3, 2)
+WORKERS = ("W1", "W2", "W3", "W4", "W5", "W6", "W7")
 
 
 def _oracle_results(so, q, frames_of):
     """Everything the workers ask, from the shims, for the oracle scene's current state: name -> dict or array"""
     o, d, tmax, pts, md, radius, tris, skip = (q[k] for k in ("o", "d", "tmax", "pts", "md", "radius", "tris", "skip"))
+    boxes, (origin, spacing) = q["boxes"], q["grid"]
     return {
         "closest": point_oracle.closest_points(so, pts),
         "closest_md": point_oracle.closest_points(so, pts, md),
@@ -50,6 +55,10 @@ def _oracle_results(so, q, frames_of):
         "ti_count": ti.count_intersecting(so, tris, skip),
         "ti_csr": ti.list_intersecting(so, tris, skip),
         "ti_k2": ti.list_intersecting(so, tris, skip, max_hits=2),
+        "bx_count": bo.count_in_boxes(so, boxes),
+        "bx_csr": bo.list_in_boxes(so, boxes),
+        "bx_k4": bo.list_in_boxes(so, boxes, max_hits=4),
+        "bx_grid": bo.count_in_boxes(so, bo.grid_boxes(origin, spacing, GRID_DIMS)).reshape(GRID_DIMS[::-1]),
         "frames": frames_of(so),
     }
 
@@ -63,8 +72,8 @@ def _same(got, ref, keys, where):
         _eq(_np(got[k]), ref[k], "%s %s" % (where, k))
 
 
-def test_six_query_threads_on_one_scene(rt, orc, scenes, blob5k):
-    """Six workers, each on its own torch stream with at least three calls per phase, and a mutator, through five phases that alternate
+def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
+    """Seven workers, each on its own torch stream with at least three calls per phase, and a mutator, through five phases that alternate
     two known states (S0: as uploaded; S1: instance 2 moved with rt_scene_update_instance_async and mesh 1 refitted from host arrays,
     both on the mutator's stream; the last change back to S0 is rt_scene_rebuild_mesh_device of the refitted mesh to its rest shape).
     W1: closest_points with every output, signed_distance (a nested call under one hold of the lock), closest_points bounded.
@@ -74,6 +83,9 @@ def test_six_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     W5: count_intersecting and list_intersecting CSR and max_hits = 2, all with a skip_instance column.
     W6: W3's rays through the numpy path (synchronous, its own device buffers and workspace): list_crossings CSR, count_crossings, CSR
     again -- two CSR calls of one family in flight on one scene.
+    W7: count_in_boxes for `any` alone (the kernel that stops at the first pair), list_in_boxes CSR (a count launch, the scan and the
+    fill, whose rooms are heaps), max_hits = 4 without count (rooms that end the traversal early), occupancy_grid with both outputs
+    on a (5, 3, 2) grid over the scene's box in S0.
     Between phases the state change is ordered after every worker's last call and before every worker's next by events.  Every
     result of every call equals the shims' for its phase's state, every frame the oracle's, and no call fails."""
     import torch
@@ -102,17 +114,22 @@ def test_six_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     o, d = qr.flatten(qr.families(rng, so, cam, n=340))
     pts = qp.flatten(qp.families(rng, o_, desc, so, cam, n=260))
     tris = np.ascontiguousarray(np.concatenate([f[1] for f in tri_families(rng, o_, desc, n=400)]), F32)
-    for name, a in (("rays", o), ("points", pts), ("triangles", tris)):
+    # (a generator of their own: the draws below stay what they were before the boxes came)
+    boxes = np.ascontiguousarray(np.concatenate([f[1] for f in box_families(np.random.default_rng(83), o_, desc, n=600)]), F32)
+    for name, a in (("rays", o), ("points", pts), ("triangles", tris), ("boxes", boxes)):
         assert 2000 <= len(a) <= 4000, (name, len(a))
     dist = point_oracle.closest_points(so, pts)["distance"]
     lo, hi = qp.scene_box(o_, desc, desc.oracle_meshes)
     diag = F32(np.linalg.norm((hi - lo).astype(np.float64)))
+    assert (boxes[:, 0] <= lo).all(axis=1).any() and (boxes[:, 1] >= hi).all(axis=1).any()     # (the whole scene is among the boxes)
+    span = np.maximum(hi - lo, F32(1e-3)).astype(F32)
+    grid = ((lo - F32(0.05) * span).astype(F32), (F32(1.1) * span / np.asarray(GRID_DIMS, F32)).astype(F32))
     # radii: up to 1.5 times the closest distance; a point farther off than a tenth of the scene's diagonal reaches its closest
     # triangle alone (a multiple of its distance would list most of the scene for that point)
     near = (dist * rng.uniform(1.0, 1.5, len(pts)) + diag * F32(1e-3)).astype(F32)
     q = dict(o=o, d=d, tmax=qr.special_tmax(rng, len(o)), pts=pts, md=qp.special_bounds(rng, dist),
              radius=np.ascontiguousarray(np.where(dist > F32(0.1) * diag, np.nextafter(dist, F32(np.inf)), near), F32), tris=tris,
-             skip=rng.integers(-1, len(desc.instances), len(tris)).astype(np.int32))
+             skip=rng.integers(-1, len(desc.instances), len(tris)).astype(np.int32), boxes=boxes, grid=grid)
 
     def frames_of(scene):
         return [scene.render(W, H, K, D, p, threads=16, planes=False)["img"] for p in poses]
@@ -121,14 +138,15 @@ def test_six_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     o_.mesh_refit(desc.oracle_meshes[1], moved1)
     want[1] = _oracle_results(so, q, frames_of)
     so.close()
-    for name, key in (("closest", "distance"), ("xl_csr", "offsets"), ("nb_csr", "offsets"), ("ti_csr", "offsets")):
+    for name, key in (("closest", "distance"), ("xl_csr", "offsets"), ("nb_csr", "offsets"), ("ti_csr", "offsets"),
+                      ("bx_csr", "offsets")):
         assert not np.array_equal(want[0][name][key], want[1][name][key]), name + ": the two states give one result"
     assert any(not np.array_equal(a, b) for a, b in zip(want[0]["frames"], want[1]["frames"]))
 
     phases = [0, 1, 0, 1, 0]
     streams = {w: torch.cuda.Stream() for w in WORKERS if w != "W6"}
     mut = torch.cuda.Stream()
-    dq = {k: torch.from_numpy(v).cuda() for k, v in q.items()}
+    dq = {k: torch.from_numpy(v).cuda() for k, v in q.items() if k != "grid"}
     img = torch.full((len(phases), len(poses), H, W * 3), 0xCD, dtype=torch.uint8, device="cuda")
     rest_dev = tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (rest1[:, :9], rest1[:, 9:12], rest1[:, 12:18]))
     torch.cuda.synchronize()
@@ -181,6 +199,12 @@ def test_six_query_threads_on_one_scene(rt, orc, scenes, blob5k):
                     ti_csr=sp.list_intersecting(dq["tris"], dq["skip"], outputs=TI_FIELDS, stream=s),
                     ti_k2=sp.list_intersecting(dq["tris"], dq["skip"], max_hits=2, outputs=TI_FIELDS + ("count",), stream=s))
 
+    def w7(s, ph):
+        return dict(bx_any=sp.count_in_boxes(dq["boxes"], outputs=("any",), stream=s),
+                    bx_csr=sp.list_in_boxes(dq["boxes"], outputs=BX_FIELDS, stream=s),
+                    bx_k4=sp.list_in_boxes(dq["boxes"], max_hits=4, outputs=BX_FIELDS, stream=s),
+                    bx_grid=sp.occupancy_grid(grid[0], grid[1], GRID_DIMS, outputs=("occupied", "count"), stream=s))
+
     def w6():
         for ph in range(len(phases)):
             results["W6"][ph] = dict(xl_csr=sp.list_crossings(q["o"], q["d"]),
@@ -190,7 +214,7 @@ def test_six_query_threads_on_one_scene(rt, orc, scenes, blob5k):
             next_phase.wait()
             ready[ph].synchronize()                             # (its launches go to the NULL stream, which no torch event orders)
 
-    for name, calls in (("W1", w1), ("W2", w2), ("W3", w3), ("W4", w4), ("W5", w5)):
+    for name, calls in (("W1", w1), ("W2", w2), ("W3", w3), ("W4", w4), ("W5", w5), ("W7", w7)):
         th.start(name, worker, name, calls)
     th.start("W6", w6)
     try:
@@ -247,6 +271,13 @@ def test_six_query_threads_on_one_scene(rt, orc, scenes, blob5k):
         _same(r["xl_csr"], ref["xl_csr"], XL_FIELDS + ("offsets", "ray", "count"), at + " list_crossings CSR (numpy)")
         _same(r["crossings"], ref["crossings"], ("count", "winding"), at + " count_crossings (numpy)")
         _same(r["xl_csr_again"], ref["xl_csr"], ("t", "sign", "offsets", "ray", "count"), at + " list_crossings CSR again (numpy)")
+        r = results["W7"][ph]
+        assert set(r["bx_any"]) == {"any"} and set(r["bx_k4"]) == set(BX_FIELDS)
+        assert np.array_equal(_np(r["bx_any"]["any"]), ref["bx_count"] > 0), at + " count_in_boxes any alone"
+        _same(r["bx_csr"], ref["bx_csr"], BX_FIELDS + ("offsets", "query_index", "count"), at + " list_in_boxes CSR")
+        _same(r["bx_k4"], ref["bx_k4"], BX_FIELDS, at + " list_in_boxes K=4 without count")
+        _eq(_np(r["bx_grid"]["count"]), ref["bx_grid"], at + " occupancy_grid count")
+        assert np.array_equal(_np(r["bx_grid"]["occupied"]), ref["bx_grid"] > 0), at + " occupancy_grid occupied"
     sp.close()
 
 
