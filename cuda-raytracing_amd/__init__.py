@@ -65,6 +65,8 @@ _INTERSECT_COUNT_OUTPUTS = ("count", "any", "pops")
 _INTERSECT_LIST_OUTPUTS = ("instance", "triangle", "normal", "segment")
 _BOX_COUNT_OUTPUTS = ("count", "any", "pops")
 _BOX_LIST_OUTPUTS = ("instance", "triangle")
+_SECTION_COUNT_OUTPUTS = ("count", "any", "pops")
+_SECTION_LIST_OUTPUTS = ("instance", "triangle", "segment", "normal")
 
 
 class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers, any may be NULL)
@@ -103,6 +105,14 @@ class RtBoxList(C.Structure):               # include/rt_hip.h (device pointers;
     _fields_ = [(n, _vp) for n in _BOX_LIST_OUTPUTS + ("count", "pops")]
 
 
+class RtSectionCounts(C.Structure):         # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in _SECTION_COUNT_OUTPUTS]
+
+
+class RtSectionList(C.Structure):           # include/rt_hip.h (device pointers; instance, triangle required)
+    _fields_ = [(n, _vp) for n in _SECTION_LIST_OUTPUTS + ("count", "pops")]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -120,7 +130,8 @@ RT_HIP_SYMBOLS = [
     "rt_closest_points", "rt_count_crossings", "rt_winding_numbers", "rt_signed_distance", "rt_crossing_offsets_workspace_bytes",
     "rt_crossing_offsets", "rt_list_crossings", "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby",
     "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting",
-    "rt_count_in_boxes", "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "rt_occupancy_grid"]
+    "rt_count_in_boxes", "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "rt_occupancy_grid",
+    "rt_count_sections", "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -273,6 +284,11 @@ def _declare(h, s):
     h.rt_box_offsets_workspace_bytes.argtypes = [C.c_int32]
     h.rt_box_offsets.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_in_boxes.argtypes = [_vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtBoxList), _vp, C.c_int]
+    h.rt_count_sections.argtypes = [_vp, _vp, C.c_int32, C.POINTER(RtSectionCounts), _vp, C.c_int]
+    h.rt_section_offsets_workspace_bytes.restype = C.c_size_t
+    h.rt_section_offsets_workspace_bytes.argtypes = [C.c_int32]
+    h.rt_section_offsets.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_list_sections.argtypes = [_vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtSectionList), _vp, C.c_int]
     h.rt_occupancy_grid.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
@@ -747,6 +763,41 @@ class Scene:
         synchronises."""
         outputs = _check_outputs(outputs, self.BOX_LIST_OUTPUTS, extras=("count", "pops"))
         return _list_query(self, _BOX_LIST, [("boxes", boxes)], _check_max_hits(max_hits), outputs, stream)
+
+    SECTION_COUNT_OUTPUTS = _SECTION_COUNT_OUTPUTS                      # the fields of RtSectionCounts
+
+    def count_sections(self, planes, outputs=("count",), stream=None):
+        """How many scene triangles each of the caller's planes cuts (rt_count_sections; the rule, equal to a brute-force loop over
+        every instance and triangle, is rule 12 of include/rt_hip.h: a vertex with height >= 0 and a vertex with height < 0): dict of
+        the wanted SECTION_COUNT_OUTPUTS of the planes' leading shape -- count (int32, the number of (instance, triangle) pairs), any
+        (bool; wanted without count, the traversal stops at the first pair), pops (int32, interior nodes visited).  planes: float32
+        [..., 2, 3] world, a point of the plane then its normal (any length; a zero normal has no pairs), contiguous.  torch tensors:
+        asynchronous on `stream` (default the current stream); numpy arrays: copied to the device and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.SECTION_COUNT_OUTPUTS)
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            c = RtSectionCounts(*[ptr.get(k) for k in _SECTION_COUNT_OUTPUTS])
+            check(h.rt_count_sections(handle, ins[0], n, C.byref(c), st, sync), "rt_count_sections")
+        return _device_query(self, [("planes", planes)], outputs, call, stream, **_PLANE_INPUTS)
+
+    SECTION_LIST_OUTPUTS = _SECTION_LIST_OUTPUTS                        # the slot fields of RtSectionList
+
+    def list_sections(self, planes, max_hits=None, outputs=("instance", "triangle", "segment"), stream=None):
+        """Where each of the caller's planes cuts the scene: every cut triangle, sorted by (instance, triangle), with the segment of
+        the cut (rt_section_offsets / rt_list_sections, include/rt_hip.h rule 12).  Fields: instance / triangle (int32), segment
+        ([2, 3] float32, world: end 0 then end 1, running along cross(plane normal, face normal), so on a closed mesh one triangle's
+        end 1 meets its neighbour's end 0, to rounding), normal ([3] float32, the world face normal as closest_points gives it).
+        planes as in count_sections.
+        max_hits=None (CSR): dict of `offsets` (int64 [n + 1], plane j's pairs at offsets[j]:offsets[j+1]), the wanted fields over all
+        pairs ([total], [total, 2, 3], [total, 3]), `query_index` (int32 [total], the flat index of each pair's plane) and `count`
+        (int32 of the leading shape, from the offsets); "pops" in outputs adds the interior nodes visited by the fill.  On torch this
+        makes exactly ONE host synchronisation (reading offsets[n] to size the outputs).
+        max_hits=K >= 1: the first K pairs of each plane, fields [..., K] / [..., K, 2, 3] / [..., K, 3] padded with instance =
+        triangle = -1 and float 0; `count` (the full number, so count > K means truncated) and `pops` only when in outputs -- without
+        count the traversal ends after the instance of a full room's greatest key, with the same rooms.  On torch fully asynchronous
+        on `stream`.  numpy arrays: copied to the device and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.SECTION_LIST_OUTPUTS, extras=("count", "pops"))
+        return _list_query(self, _SECTION_LIST, [("planes", planes)], _check_max_hits(max_hits), outputs, stream)
 
     GRID_OUTPUTS = ("occupied", "count")
 
@@ -1300,6 +1351,10 @@ _INTERSECT_LIST = _ListKind(_INTERSECT_LIST_OUTPUTS, ("instance", "triangle"), R
 _BOX_INPUTS = dict(shape=(2, 3))
 _BOX_LIST = _ListKind(_BOX_LIST_OUTPUTS, ("instance", "triangle"), RtBoxList,
                       "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "query_index", inputs=_BOX_INPUTS)
+_PLANE_INPUTS = dict(shape=(2, 3))                  # (a box array's shape: point then normal)
+_SECTION_LIST = _ListKind(_SECTION_LIST_OUTPUTS, ("instance", "triangle"), RtSectionList,
+                          "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections", "query_index",
+                          inputs=_PLANE_INPUTS)
 
 
 def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=(), scratch=None):

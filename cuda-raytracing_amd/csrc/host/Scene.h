@@ -23,6 +23,8 @@ struct RtIntersectCounts;
 struct RtIntersectList;
 struct RtBoxCounts;
 struct RtBoxList;
+struct RtSectionCounts;
+struct RtSectionList;
 
 class Scene {
 public:
@@ -103,6 +105,14 @@ public:
                       void* stream = nullptr, bool synchronize = false);
     int occupancy_grid(const float* origin, const float* spacing, const int32_t* dims, uint8_t* d_occupied, int32_t* d_count,
                        void* stream = nullptr, bool synchronize = false);
+    // Plane sections on the device scene: rt_count_sections / rt_section_offsets / rt_list_sections of include/rt_hip.h (rule 12,
+    // rooms), where the semantics are.  Planes ([n][2][3] world, point then normal), offsets, workspace and outputs are DEVICE
+    // arrays.  Return the status.
+    int count_sections(const float* d_planes, int32_t n, const RtSectionCounts& out, void* stream = nullptr, bool synchronize = false);
+    int section_offsets(const float* d_planes, int32_t n, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes,
+                        void* stream = nullptr, bool synchronize = false);
+    int list_sections(const float* d_planes, int32_t n, const int64_t* d_offsets, int32_t max_hits, const RtSectionList& out,
+                      void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

@@ -728,6 +728,27 @@ int Scene::occupancy_grid(const float* origin, const float* spacing, const int32
     return last_error;
 }
 
+int Scene::count_sections(const float* d_planes, int32_t n, const RtSectionCounts& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_count_sections(d_scene, d_planes, n, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::section_offsets(const float* d_planes, int32_t n, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream,
+                           bool synchronize)
+{
+    last_error = d_scene ? rt_section_offsets(d_scene, d_planes, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::list_sections(const float* d_planes, int32_t n, const int64_t* d_offsets, int32_t max_hits, const RtSectionList& out,
+                         void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_list_sections(d_scene, d_planes, n, d_offsets, max_hits, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

@@ -3771,6 +3771,290 @@ __global__ __launch_bounds__(kTriBlock, 8) void box_list_kernel(const BoxParams 
     if (p.pops) p.pops[i] = pops;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------
+// Plane sections (rt_count_sections / rt_section_offsets / rt_list_sections): every (instance, triangle) that a caller's world plane
+// cuts by rule 12 of include/rt_hip.h -- a vertex ABOVE (h >= 0) and a vertex BELOW (h < 0) -- with the oriented segment of the cut,
+// equal to a brute-force loop over every (instance, triangle) whatever the tree; the pruning argument is in DESIGN.md section 17.  One
+// wave per workgroup, one plane per lane, the boxes' unordered traversal on the general stack: a child box is skipped only when every
+// vertex that can lie in it gets the same class.
+// ---------------------------------------------------------------------------------------------------------
+struct SecParams {
+    const float4* records;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* planes;        // [n][2][3] world planes, point then normal
+    int32_t n;
+    const int64_t* offsets;     // the list kernel: [n + 1] (CSR rooms) or null: fixed rooms of max_hits
+    int32_t max_hits;
+    int32_t *instance, *triangle;   // the list kernel's keys, required; indexed by room slot
+    float *segment, *normal;    // optional, [slots][2][3] and [slots][3]
+    int32_t* count;             // optional, [n] (the offsets call: the workspace)
+    uint8_t* any;               // optional, [n] (the count kernel)
+    int32_t* pops;              // optional, [n]
+};
+
+// rule 12 step 2: the plane's point and normal in instance in's scaled mesh space
+__device__ __forceinline__ V3 sc_point(V3 P, const DevInstance& in)
+{
+    return apply_quat(in.q_pose, v3(P.x - in.pose_xyz[0], P.y - in.pose_xyz[1], P.z - in.pose_xyz[2]));
+}
+__device__ __forceinline__ V3 sc_normal(V3 N, const DevInstance& in) { return apply_quat(in.q_pose, N); }
+// rule 12 step 4: each difference rounded, each product rounded, then the two sums
+__device__ __forceinline__ float sc_height(V3 n, V3 q, V3 x) { return (n.x * (x.x - q.x) + n.y * (x.y - q.y)) + n.z * (x.z - q.z); }
+
+// One axis of a child box: the box scaled and widened exactly as pq_gap does it, then the smaller and the larger of the term
+// n*(X - q) of step 4 at its two ends, and the sum of their magnitudes (>= the larger magnitude; a NaN in either end stays a NaN
+// here, where fminf / fmaxf would drop it)
+__device__ __forceinline__ void sc_axis(float lo, float hi, float s, float q, float n, float& lower, float& upper, float& mag)
+{
+    const float x = lo * s, y = hi * s;
+    const float l = s < 0.0f ? y : x, h = s < 0.0f ? x : y;
+    const float m = fmaxf(fabsf(l), fabsf(h)) * 0x1p-16f + 0x1p-126f;
+    const float t1 = n * ((l - m) - q), t2 = n * ((h + m) - q);
+    lower = fminf(t1, t2); upper = fmaxf(t1, t2); mag = fabsf(t1) + fabsf(t2);
+}
+// Whether a child box can hold a vertex of either class: step 4's height bounded from both sides in step 4's own order of sums,
+// the bounds widened by E = 2^-16 of the terms' magnitudes plus FLT_MIN; skipped only when a compare says that every height is > 0 or
+// every height is < 0, so a NaN anywhere keeps the box
+__device__ __forceinline__ bool sc_box(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 q, V3 n)
+{
+    float ax, bx, mx, ay, by, my, az, bz, mz;
+    sc_axis(lx, hx, s.x, q.x, n.x, ax, bx, mx);
+    sc_axis(ly, hy, s.y, q.y, n.y, ay, by, my);
+    sc_axis(lz, hz, s.z, q.z, n.z, az, bz, mz);
+    const float lower = (ax + ay) + az, upper = (bx + by) + bz, e = ((mx + my) + mz) * 0x1p-16f + 0x1p-126f;
+    return !((lower - e) > 0.0f) && !((upper + e) < 0.0f);
+}
+
+// Rule 12 step 6 for one pair, out of line and from the record again (the same sequence as the traversal's test, the same bits), so none
+// of it occupies the traversal's registers: the two cut points in WORLD space, end 0 on the edge the cycle A->B->C->A runs from ABOVE to
+// BELOW, end 1 on the edge it runs from BELOW to ABOVE, each computed from the edge's BELOW vertex.
+struct ScSeg { V3 e0, e1; };
+__device__ __noinline__ ScSeg sc_segment(const float4* records, const DevInstance& in, int32_t slot, V3 P, V3 N)
+{
+    const V3 q = sc_point(P, in), n = sc_normal(N, in);
+    const float4* rec = records + (size_t)slot * 4;
+    V3 a, ab, ac;
+    pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+    const V3 b = a + ab, c = a + ac;
+    const float ha = sc_height(n, q, a), hb = sc_height(n, q, b), hc = sc_height(n, q, c);
+    ScSeg r;
+    r.e0 = v3(0.0f, 0.0f, 0.0f); r.e1 = r.e0;
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+        const V3 x = e == 0 ? a : e == 1 ? b : c, y = e == 0 ? b : e == 1 ? c : a;      // the cycle's edge x -> y
+        const float hx = e == 0 ? ha : e == 1 ? hb : hc, hy = e == 0 ? hb : e == 1 ? hc : ha;
+        const bool down = hx >= 0.0f && hy < 0.0f, up = hx < 0.0f && hy >= 0.0f;
+        if (!(down || up)) continue;
+        const V3 lo = up ? x : y, hi = up ? y : x;              // the BELOW and the ABOVE end
+        const float hl = up ? hx : hy, hh = up ? hy : hx;
+        const float t = hl / (hl - hh);
+        const V3 cut = v3(lo.x + t * (hi.x - lo.x), lo.y + t * (hi.y - lo.y), lo.z + t * (hi.z - lo.z));
+        // to world: apply_lre(inv_pose, .), closest_points' map
+        const V3 w = apply_quat(in.q_inv_pose, v3(cut.x - in.inv_pose_xyz[0], cut.y - in.inv_pose_xyz[1], cut.z - in.inv_pose_xyz[2]));
+        if (down) r.e0 = w; else r.e1 = w;
+    }
+    return r;
+}
+
+// Every pair of the world plane (P, N), instance by instance in ascending order (triangles of one instance in tree order).  go(k) is
+// asked before instance k (false ends the traversal); pair(k, slot) is called at each pair and returns whether to end the traversal.
+// Returns the interior nodes visited.  A zero normal (rule 12 step 1) visits nothing.
+template <typename Go, typename Pair>
+__device__ __forceinline__ int32_t sc_trace(const SecParams& p, TriStack& stack, V3 P, V3 N, Go&& go, Pair&& pair)
+{
+    int32_t pops = 0;
+    if (!(N.x != 0.0f || N.y != 0.0f || N.z != 0.0f)) return pops;
+    for (int32_t k = 0; k < p.num_instances; k++) {
+        if (!go(k)) break;
+        const DevInstance& in = p.instances[k];
+        const V3 q = sc_point(P, in), n = sc_normal(N, in);     // p' and n': all the node loop keeps of the plane
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        bool done = false;
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: every child that can hold both classes, no order
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const bool pa = !prune || sc_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, q, n);
+                const bool pb = !prune || sc_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, q, n);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                if (pa && pb) stack.push(rb);
+                cur = pa ? ra : (pb ? rb : kNeedPop);
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    V3 a, ab, ac;
+                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
+                    const float ha = sc_height(n, q, a), hb = sc_height(n, q, a + ab), hc = sc_height(n, q, a + ac);
+                    const int above = (ha >= 0.0f) + (hb >= 0.0f) + (hc >= 0.0f), below = (ha < 0.0f) + (hb < 0.0f) + (hc < 0.0f);
+                    // step 5: all three classified (a NaN height is neither), one ABOVE at least and one BELOW
+                    if (above + below == 3 && above > 0 && below > 0 && pair(k, slot)) done = true;
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel && !done);
+        if (done) break;
+    }
+    return pops;
+}
+
+// ANY = false: the number of pairs of each plane (rt_count_sections, and rt_section_offsets' first step into the workspace).
+// ANY = true (any wanted, count not): the traversal ends at the first pair, across instances too.
+template <bool ANY>
+__global__ __launch_bounds__(kTriBlock, 8) void section_count_kernel(const SecParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const float* B = p.planes + (size_t)i * 6;
+    int32_t total = 0;
+    const int32_t pops = sc_trace(p, stack, v3(B[0], B[1], B[2]), v3(B[3], B[4], B[5]), [&](int32_t) { return true; },
+                                  [&](int32_t, int32_t) {
+        total++;
+        return ANY;
+    });
+    if (p.count) p.count[i] = total;
+    if (p.any) p.any[i] = total > 0 ? 1 : 0;
+    if (p.pops) p.pops[i] = pops;
+}
+
+// A room's entry while the heap is at work: the key (instance, triangle) as one number, as bx_key makes it, and the pair's record
+// slot, which travels with the key when segment or normal is wanted: they are computed from it once the room is sorted.  The slot
+// lives in the first word of the entry's segment (or, without segment, of its normal), inside the room.
+struct ScItem { uint64_t key; int32_t slot; };
+__device__ __forceinline__ float* sc_aux(const SecParams& p, size_t q) { return p.segment ? p.segment + 6 * q : (p.normal ? p.normal + 3 * q : nullptr); }
+__device__ __forceinline__ ScItem sc_get(const SecParams& p, size_t q)
+{
+    ScItem it;
+    it.key = ((uint64_t)(uint32_t)p.instance[q] << 32) | (uint64_t)(uint32_t)p.triangle[q];
+    const float* aux = sc_aux(p, q);
+    it.slot = aux ? __float_as_int(*aux) : 0;
+    return it;
+}
+__device__ __forceinline__ void sc_put(const SecParams& p, size_t q, ScItem it)
+{
+    p.instance[q] = (int32_t)(it.key >> 32);
+    p.triangle[q] = (int32_t)(uint32_t)it.key;
+    float* aux = sc_aux(p, q);
+    if (aux) *aux = __int_as_float(it.slot);
+}
+// bx_sift_down with the slot travelling along
+__device__ __forceinline__ void sc_sift_down(const SecParams& p, size_t start, uint64_t size, uint64_t pos, ScItem it)
+{
+    for (;;) {
+        uint64_t child = 2 * pos + 1;
+        if (child >= size) break;
+        ScItem ci = sc_get(p, start + (size_t)child);
+        if (child + 1 < size) {
+            const ScItem c2 = sc_get(p, start + (size_t)child + 1);
+            if (c2.key > ci.key) { ci = c2; child++; }
+        }
+        if (ci.key <= it.key) break;
+        sc_put(p, start + (size_t)pos, ci);
+        pos = child;
+    }
+    sc_put(p, start + (size_t)pos, it);
+}
+
+// box_list_kernel's lane-private max-heap on (instance, triangle) and its early end for fixed rooms without count.  segment and normal
+// depend on the plane, the instance and the record alone, and are written after the sort from the slot that travelled with each key:
+// the rooms are the same bits with and without count and whatever the tree.
+__global__ __launch_bounds__(kTriBlock, 8) void section_list_kernel(const SecParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const float* B = p.planes + (size_t)i * 6;
+    const bool early = !p.offsets && !p.count;
+    int32_t total = 0;
+    uint64_t filled = 0;                                        // (<= room)
+    const int32_t pops = sc_trace(p, stack, v3(B[0], B[1], B[2]), v3(B[3], B[4], B[5]), [&](int32_t k) {
+        if (!early || filled < (uint64_t)p.max_hits) return true;                   // (fixed rooms: start i*K, room K)
+        return k <= p.instance[(size_t)i * (size_t)p.max_hits];                     // (the root: the room's greatest key)
+    }, [&](int32_t k, int32_t slot) {
+        total++;
+        size_t start;
+        uint64_t room;
+        xl_room(p, i, start, room);                             // (read again per pair: not held across the traversal)
+        if (room == 0) return false;
+        ScItem it;
+        it.key = ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)p.tri_id[slot];
+        it.slot = slot;
+        if (filled < room) {                                    // sift up from the new last slot
+            uint64_t pos = filled++;
+            while (pos > 0) {
+                const uint64_t parent = (pos - 1) / 2;
+                const ScItem pi = sc_get(p, start + (size_t)parent);
+                if (pi.key >= it.key) break;
+                sc_put(p, start + (size_t)pos, pi);
+                pos = parent;
+            }
+            sc_put(p, start + (size_t)pos, it);
+        } else if (it.key < sc_get(p, start).key) {             // full: the root leaves
+            sc_sift_down(p, start, room, 0, it);
+        }
+        return false;
+    });
+    size_t start;
+    uint64_t room;
+    xl_room(p, i, start, room);
+    for (uint64_t end = filled; end > 1; end--) {               // heap -> ascending: the greatest key to the end, the rest a heap again
+        const ScItem last = sc_get(p, start + (size_t)(end - 1));
+        sc_put(p, start + (size_t)(end - 1), sc_get(p, start));
+        sc_sift_down(p, start, end - 1, 0, last);
+    }
+    if (p.segment || p.normal) {
+        const V3 P = v3(B[0], B[1], B[2]), N = v3(B[3], B[4], B[5]);
+        for (uint64_t j = 0; j < filled; j++) {                 // the sorted entries: segment and normal from the slot
+            const size_t q = start + (size_t)j;
+            const int32_t slot = sc_get(p, q).slot;
+            const DevInstance& in = p.instances[p.instance[q]];
+            if (p.segment) {
+                const ScSeg sg = sc_segment(p.records, in, slot, P, N);
+                float* o = p.segment + 6 * q;
+                o[0] = sg.e0.x; o[1] = sg.e0.y; o[2] = sg.e0.z; o[3] = sg.e1.x; o[4] = sg.e1.y; o[5] = sg.e1.z;
+            }
+            if (p.normal) {
+                const V3 nn = pq_normal(p, in, slot);
+                p.normal[3 * q] = nn.x; p.normal[3 * q + 1] = nn.y; p.normal[3 * q + 2] = nn.z;
+            }
+        }
+    }
+    for (uint64_t j = filled; j < room; j++) {                  // padding
+        const size_t q = start + (size_t)j;
+        p.instance[q] = -1;
+        p.triangle[q] = -1;
+        if (p.segment) { for (int c = 0; c < 6; c++) p.segment[6 * q + c] = 0.0f; }
+        if (p.normal) { p.normal[3 * q] = 0.0f; p.normal[3 * q + 1] = 0.0f; p.normal[3 * q + 2] = 0.0f; }
+    }
+    if (p.count) p.count[i] = total;
+    if (p.pops) p.pops[i] = pops;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -5712,6 +5996,72 @@ int rt_occupancy_grid(RtScene* s, const float* origin, const float* spacing, con
             hipLaunchKernelGGL(box_grid_kernel<true>, groups, dim3(kTriBlock), lds, st, p);
         else
             hipLaunchKernelGGL(box_grid_kernel<false>, groups, dim3(kTriBlock), lds, st, p);
+        return RT_OK;
+    });
+}
+
+// ---- plane sections ---------------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+SecParams section_params(const RtScene* s, const float* d_planes, int32_t n)
+{
+    SecParams p = scene_params<SecParams>(s);
+    p.tri_id = s->d_tri_id;
+    p.planes = d_planes; p.n = n;
+    return p;
+}
+void launch_section_count(const SecParams& p, bool any_only, hipStream_t st)
+{
+    const QueryShape k = query_shape(p.n, kTriBlock, p.stack_depth);
+    if (any_only)
+        hipLaunchKernelGGL(section_count_kernel<true>, k.groups, dim3(kTriBlock), k.lds, st, p);
+    else
+        hipLaunchKernelGGL(section_count_kernel<false>, k.groups, dim3(kTriBlock), k.lds, st, p);
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_count_sections(RtScene* s, const float* d_planes, int32_t n, const RtSectionCounts* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_planes || !out))) return RT_E_INVALID;
+    if (n > 0 && !(out->count || out->any || out->pops)) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        SecParams p = section_params(s, d_planes, n);
+        p.count = out->count; p.any = out->any; p.pops = out->pops;
+        launch_section_count(p, p.any && !p.count, st);         // (any without count: stop at the first pair)
+        return RT_OK;
+    });
+}
+
+size_t rt_section_offsets_workspace_bytes(int32_t n) { return offsets_workspace_bytes(n); }
+
+int rt_section_offsets(RtScene* s, const float* d_planes, int32_t n, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes,
+                       void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_planes || !d_offsets || !d_workspace))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
+    return query_offsets(s, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize, [&](int32_t* counts, hipStream_t st) {
+        SecParams p = section_params(s, d_planes, n);
+        p.count = counts;
+        launch_section_count(p, false, st);
+    });
+}
+
+int rt_list_sections(RtScene* s, const float* d_planes, int32_t n, const int64_t* d_offsets, int32_t max_hits, const RtSectionList* out,
+                     void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_planes || !out))) return RT_E_INVALID;
+    if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
+    if (n > 0 && !(out->instance && out->triangle)) return RT_E_INVALID;     // the room holds the keys
+    if (n == 0) return RT_OK;
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        SecParams p = section_params(s, d_planes, n);
+        p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
+        p.instance = out->instance; p.triangle = out->triangle; p.segment = out->segment; p.normal = out->normal;
+        p.count = out->count; p.pops = out->pops;
+        const QueryShape k = query_shape(n, kTriBlock, p.stack_depth);
+        hipLaunchKernelGGL(section_list_kernel, k.groups, dim3(kTriBlock), k.lds, st, p);
         return RT_OK;
     });
 }

@@ -729,6 +729,70 @@ int rt_list_in_boxes(RtScene *scene, const float *d_boxes, int32_t n, const int6
 int rt_occupancy_grid(RtScene *scene, const float *origin, const float *spacing, const int32_t *dims, uint8_t *d_occupied,
                       int32_t *d_count, void *stream, int synchronize);
 
+/* ---- plane sections: every (instance, triangle) of the scene that a caller's world plane cuts, with the
+ *      oriented segment of the cut -- slicing for layered manufacturing, contour lines, section views.  The pairs equal a brute-force
+ *      loop over every (instance, triangle), whatever the tree (host-built, device-built, refitted) and whatever the traversal order.
+ *      12. For query plane j through the world point P with the world normal N (fp32, N not normalised) and instance i; every
+ *          operation fp32 in one fixed sequence, no contraction:
+ *          1. Valid plane: at least one component of N compares != 0.  A zero normal has no pairs.
+ *          2. Map: p' = apply_lre(pose_i, P), rule 1's map of points; n' = apply_quat(q_pose_i, N), rule 1's map of directions.  Scaled
+ *             mesh space is world space rotated and translated, so heights are world heights times |N|.
+ *          3. Scene triangle: A = v0*s, B = A + AB, C = A + AC as in rule 10 step 2.
+ *          4. Heights: h(X) = (n'.x*(X.x - p'.x) + n'.y*(X.y - p'.y)) + n'.z*(X.z - p'.z): each difference rounded, each product
+ *             rounded, then the two sums.  A vertex is ABOVE when h >= 0 (so -0 is above), BELOW when h < 0; a NaN height is neither.
+ *          5. (i, triangle) is a PAIR of plane j when step 1 holds, all three heights are classified, and at least one vertex is ABOVE
+ *             and at least one BELOW.  The rule is half-open: a triangle lying in the plane is no pair; one touching the plane from
+ *             above is no pair; one touching it from below with a vertex or an edge is a pair, with a zero-length segment or the edge
+ *             itself.  So a closed surface yields closed contours and no coincident face is reported twice.
+ *          6. Segment: exactly two edges of the cycle A->B->C->A join a BELOW and an ABOVE vertex.  On such an edge with BELOW end X and
+ *             ABOVE end Y the cut point is t = hX / (hX - hY), Q = X + t*(Y - X) per component in fp32, always computed from the BELOW
+ *             vertex whatever direction the cycle runs the edge in.  End 0 is the cut point of the edge the cycle runs from ABOVE to
+ *             BELOW, end 1 that of the edge it runs from BELOW to ABOVE: end 0 -> end 1 runs along cross(n', face normal).  For a closed
+ *             mesh counter-clockwise seen from outside, a triangle's end 1 lies on the edge that holds its neighbour's end 0, and the
+ *             outer contour runs counter-clockwise seen from the side N points to.  A mirrored instance reverses that, as it reverses
+ *             its world triangles.  Both ends go to world by apply_lre(inv_pose_i, Q), closest_points' map.
+ *             NOT PROMISED: that neighbours' shared cut points are equal bit for bit.  Triangles are stored as v0 and edge vectors, so a
+ *             shared vertex can differ by rounding between two triangles (rule 6's remark): the points coincide to rounding.
+ *          7. Per pair: instance and triangle (the uploaded numbering); segment [2][3] world; normal [3] = the world face normal exactly
+ *             as rt_closest_points gives it.  ORDER: a plane's pairs sorted by (instance, triangle) ascending.  ROOMS (CSR or fixed K),
+ *             padding (instance = triangle = -1, the floats 0) and "nothing is ever written outside a room" are rule 8's.
+ *          8. NON-FINITE planes, and planes whose heights overflow fp32 on this scene, do not fault, do not change other queries'
+ *             results and never write outside their room; their own results are unspecified.
+ *      rt_count_sections: count [n] (the number of pairs), any [n] (1 when there is one), pops [n] (interior nodes visited, a
+ *      statistic); all optional, at least one given.  With any and without count the traversal ends at the first pair, across
+ *      instances too.
+ *      rt_section_offsets writes offsets[0] = 0 and offsets[i+1] = offsets[i] + count_i (int64): the count traversal into the
+ *      workspace, then rt_crossing_offsets' exclusive scan on the device.  Its workspace is DEVICE memory of at least
+ *      rt_section_offsets_workspace_bytes(n) bytes (0 for n <= 0).  With n == 0 nothing is launched and d_offsets is not written.
+ *      rt_list_sections fills the rooms: CSR (d_offsets) or fixed (d_offsets NULL, max_hits = K >= 1), as in rule 8.  instance and
+ *      triangle are REQUIRED (the room is where the keys live), the rest optional; count[n] is each plane's FULL count even when the
+ *      room truncates.  In fixed rooms without count, once a room is full the traversal ends after the instance of the room's greatest
+ *      key; the rooms are the same bits with and without count.
+ *      All calls: d_planes is a DEVICE array [n][2][3], point then normal; asynchronous on `stream` unless synchronize != 0; no host
+ *      synchronisation, allocation or scene scratch (calls may overlap each other and renders); nothing launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL planes with n > 0; rt_count_sections: NULL out or no output with n > 0;
+ *      rt_section_offsets: d_offsets or d_workspace NULL, or a workspace too small, with n > 0; rt_list_sections: NULL out, or instance
+ *      or triangle NULL, with n > 0; both or neither of d_offsets and max_hits >= 1. ------------------------------------------- */
+typedef struct RtSectionCounts {    /* every pointer optional, at least one given                                              */
+    int32_t *count;             /* [n] the number of pairs                                                                 */
+    uint8_t *any;               /* [n] 1 when the plane has a pair                                                         */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic, not part of the exact contract)                */
+} RtSectionCounts;
+typedef struct RtSectionList {      /* fields indexed by room slot; instance and triangle REQUIRED, the rest optional          */
+    int32_t *instance;          /* [slots] -1 = padding                                                                    */
+    int32_t *triangle;          /* [slots] the uploaded numbering; -1 = padding                                            */
+    float *segment;             /* [slots][2][3] world ends of the cut, end 0 then end 1                                   */
+    float *normal;              /* [slots][3] world face normal                                                            */
+    int32_t *count;             /* [n] the full number of pairs of each plane                                              */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic)                                                */
+} RtSectionList;
+int rt_count_sections(RtScene *scene, const float *d_planes, int32_t n, const RtSectionCounts *out, void *stream, int synchronize);
+size_t rt_section_offsets_workspace_bytes(int32_t n);
+int rt_section_offsets(RtScene *scene, const float *d_planes, int32_t n, int64_t *d_offsets, void *d_workspace, size_t workspace_bytes,
+                       void *stream, int synchronize);
+int rt_list_sections(RtScene *scene, const float *d_planes, int32_t n, const int64_t *d_offsets, int32_t max_hits, const RtSectionList *out,
+                     void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
