@@ -1,14 +1,15 @@
 """What the query families share, at the sizes where it can go wrong (the arithmetic of each family is test_gpu_crossing_list.py's,
-test_gpu_nearby.py's, test_gpu_tri_intersect.py's and test_gpu_boxes.py's business): the CSR scan behind the four *_offsets calls
-(crossing, nearby, intersecting, box) at its block edges and on its three-level path, totals and room positions past 2^31 and 2^32,
-the box list's heap rooms at slots past 2^31 and 2^32, occupancy grids that need the grid kernel's second launch row and its
-limit of 2^24 cells on an axis, and every query kernel with a partly filled last workgroup on the deep scene.  The C-ABI is called
-directly on torch buffers: the Python wrappers would allocate `total` rows.
+test_gpu_nearby.py's, test_gpu_tri_intersect.py's, test_gpu_boxes.py's and test_gpu_sections.py's business): the CSR scan behind the
+five *_offsets calls (crossing, nearby, intersecting, box, section) at its block edges and on its three-level path, totals and room
+positions past 2^31 and 2^32, the box list's heap rooms at slots past 2^31 and 2^32, the section list's heap rooms where the slot
+times the width of a segment or a normal passes 2^32 and where the slot itself does, occupancy grids that need the grid kernel's
+second launch row and its limit of 2^24 cells on an axis, and every query kernel with a partly filled last workgroup on the deep
+scene.  The C-ABI is called directly on torch buffers: the Python wrappers would allocate `total` rows.
 
 Every offsets check compares with np.concatenate([[0], np.cumsum(counts)]) of the CPU shims' counts (crossing_oracle, nearby_oracle,
-tri_intersect_oracle, box_oracle), never with the library's own counts.  Every buffer a kernel may write is allocated at its full
+tri_intersect_oracle, box_oracle, section_oracle), never with the library's own counts.  Every buffer a kernel may write is allocated at its full
 size; the large cases read back small windows only.  Totals beyond 2^32 are not repeated for boxes: the scan and its 64-bit sums are
-one piece of code for all four families, tested through rt_crossing_offsets below."""
+one piece of code for all five families, tested through rt_crossing_offsets below."""
 import ctypes as C
 
 import numpy as np
@@ -22,6 +23,7 @@ import point_oracle
 import query_points as qp
 import ray_oracle
 import scene_defs as sd
+import section_oracle as sc
 import tri_intersect_oracle as ti
 from test_crossing_host import _cube
 from test_gpu_crossings import _eq, _product
@@ -32,7 +34,7 @@ F32 = np.float32
 SCAN_BLOCK = 1024                                               # elements per block of the scan over n + 1 offsets (kScanBlock)
 GUARD = 0x5A
 GUARD64 = int.from_bytes(bytes([GUARD]) * 8, "little")
-FAMILIES = ("crossing", "nearby", "intersecting", "box")
+FAMILIES = ("crossing", "nearby", "intersecting", "box", "section")
 
 
 def _cumsum(counts):
@@ -60,6 +62,8 @@ def _call_offsets(h, family, handle, q, n, off, ws, ws_bytes):
         return h.rt_nearby_offsets(handle, a, b, n, off, ws, ws_bytes, None, 1)
     if family == "box":
         return h.rt_box_offsets(handle, a, n, off, ws, ws_bytes, None, 1)
+    if family == "section":
+        return h.rt_section_offsets(handle, a, n, off, ws, ws_bytes, None, 1)
     return h.rt_intersecting_offsets(handle, a, b, n, off, ws, ws_bytes, None, 1)
 
 
@@ -167,10 +171,21 @@ def pools(orc, multi):
     assert len(tris) == POOL
     bc, be = rng.uniform(-1.5, 1.5, (POOL, 3)), rng.uniform(0.02, 0.3, (POOL, 3))
     boxes = np.ascontiguousarray(np.stack([bc - be / 2, bc + be / 2], axis=1), F32)
+    # planes: a generator of their own (the draws above stay what they were); about a quarter lie outside the scene.  Counts run
+    # to several hundred, so a count launch that stops at the first pair (every count capped at 1) changes most offsets
+    rng = np.random.default_rng(41)
+    pp, u = rng.uniform(-1.5, 1.5, (POOL, 3)), rng.normal(size=(POOL, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    lo, hi = (a.astype(np.float64) for a in qp.scene_box(orc.oracle(), multi.desc, multi.desc.oracle_meshes))
+    far = rng.random(POOL) < 0.25
+    pp[far] = (lo + hi) / 2 + u[far] * np.linalg.norm(hi - lo) * rng.uniform(1.5, 4, (int(far.sum()), 1))
+    planes = np.ascontiguousarray(np.stack([pp, u], axis=1), F32)
     out = {"crossing": ((o, d), xo.count_crossings(multi.so, o, d)["count"]),
            "nearby": ((pts, md), nb.count_nearby(multi.so, pts, md)),
            "intersecting": ((tris, None), ti.count_intersecting(multi.so, tris)),
-           "box": ((boxes, None), bo.count_in_boxes(multi.so, boxes))}
+           "box": ((boxes, None), bo.count_in_boxes(multi.so, boxes)),
+           "section": ((planes, None), sc.count_sections(multi.so, planes))}
+    assert out["section"][1].max() > 64, out["section"][1].max()
     for family, (_q, c) in out.items():
         assert (c > 0).sum() >= 16 and (c == 0).sum() >= 16, (family, int((c > 0).sum()))
     return out
@@ -224,10 +239,14 @@ def cube_queries(cube):
     tris = np.ascontiguousarray(cen + rng.normal(size=(DISTINCT, 3, 3)) * 0.15, F32)
     bc, be = rng.uniform(-0.5, 1.5, (DISTINCT, 3)), rng.uniform(0.05, 0.5, (DISTINCT, 3))
     boxes = np.ascontiguousarray(np.stack([bc - be / 2, bc + be / 2], axis=1), F32)
+    rng = np.random.default_rng(43)                             # (planes: a generator of their own, as in pools)
+    pp, u = rng.uniform(-0.5, 1.5, (DISTINCT, 3)), rng.normal(size=(DISTINCT, 3))
+    planes = np.ascontiguousarray(np.stack([pp, u / np.linalg.norm(u, axis=1, keepdims=True)], axis=1), F32)
     return {"crossing": ((o, d), xo.count_crossings(cube.so, o, d)["count"]),
             "nearby": ((pts, md), nb.count_nearby(cube.so, pts, md)),
             "intersecting": ((tris, None), ti.count_intersecting(cube.so, tris)),
-            "box": ((boxes, None), bo.count_in_boxes(cube.so, boxes))}
+            "box": ((boxes, None), bo.count_in_boxes(cube.so, boxes)),
+            "section": ((planes, None), sc.count_sections(cube.so, planes))}
 
 
 def _tiled(pool, n):
@@ -265,10 +284,10 @@ def test_three_level_scan_crossing(rt, cube, cube_queries, n):
     _same_offsets(got, _cumsum(counts), "crossing n=%d" % n)
 
 
-@pytest.mark.parametrize("family", ["nearby", "intersecting", "box"])
+@pytest.mark.parametrize("family", ["nearby", "intersecting", "box", "section"])
 def test_three_level_scan_other_families(rt, cube, cube_queries, family):
-    """The same at n = 2^20 + 1 through rt_nearby_offsets, rt_intersecting_offsets and rt_box_offsets: one scan, but each family's own
-    count launch"""
+    """The same at n = 2^20 + 1 through rt_nearby_offsets, rt_intersecting_offsets, rt_box_offsets and rt_section_offsets: one scan, but
+    each family's own count launch"""
     _three_levels(rt, cube, cube_queries, family, 2 ** 20 + 1)
 
 
@@ -503,6 +522,180 @@ def test_box_fixed_rooms_beyond_31_bits(rt, stack):
                     room = bufs[k][i * K:(i + 1) * K].cpu().numpy()
                     assert (room == -1).all(), "%s of room %d (a box without pairs), %s: %d slots are not padding" % (
                         k, i, at, int((room != -1).sum()))
+            if with_count:
+                got = cnt.cpu().numpy()
+                _eq(got[-64:], c, "count of the last 64")
+                assert (got[:-64] == 0).all()
+    finally:
+        del bufs
+        torch.cuda.empty_cache()
+
+
+# ---- B4d: the section list's heap rooms where 6 * slot and 3 * slot pass 2^32, and where the slot does --------------------------------
+GUARDF = np.frombuffer(bytes([GUARD]) * 4, F32)[0]             # the float whose words are GUARD32
+SC_WIDTH = dict(instance=1, triangle=1, segment=6, normal=3)    # int32 words per slot
+SC_FILL = dict(instance=GUARD32, triangle=GUARD32, segment=GUARDF, normal=GUARDF)
+FAR_PLANE = np.array([[50, 50, 50], [1, 1, 1]], F32)
+X_HALF = np.array([[0.5, 0.5, 6.0], [1, 0, 0]], F32)            # cuts every triangle of the stack: 4 * QUADS pairs
+
+
+def _tilt(a, m):
+    """the plane through (0.5, 0.5, z0) with normal (1, 0, 1 / (m * 0.01)): over the quads' footprint its z runs through m * 0.01, and
+    z0 is set so that this is from half a spacing below quad a to half a spacing above quad a + m - 1.  It cuts both triangles of
+    those m quads in both instances, 4 * m pairs"""
+    return np.array([[0.5, 0.5, (a + m / 2.0) * 0.01 - 0.005], [1.0, 0.0, 1.0 / (m * 0.01)]], F32)
+
+
+def _flat_plane(z):
+    return np.array([[0.5, 0.5, z], [0, 0, 1]], F32)
+
+
+def _sc_words(a, k):
+    """a shim field as flat int32 words, as the buffers below hold the product's"""
+    return np.ascontiguousarray(a).view(np.int32).reshape(-1)
+
+
+def _section_list(rt, handle, planes, n, offsets_ptr, max_hits, bufs, cnt):
+    """rt_list_sections on device buffers (bufs: field -> int32 words, a missing field is not asked for), synchronous on the NULL
+    stream"""
+    import torch
+    lst = rt.RtSectionList(*[bufs[k].data_ptr() if k in bufs else None for k in sc.FIELDS], None if cnt is None else cnt.data_ptr(), None)
+    torch.cuda.synchronize()
+    return rt.libs()[0].rt_list_sections(handle, planes.data_ptr(), n, offsets_ptr, max_hits, C.byref(lst), None, 1)
+
+
+def _csr_planes():
+    """400 planes on the quad stack, shuffled: one of 1200 pairs, two of 400, four of 100, 150 without pairs (far off, or parallel to
+    the quads, on one or between two) and 243 thin tilted ones over one to three quads -> (planes, rng)"""
+    rng = np.random.default_rng(101)
+    big = [_tilt(100, 300), _tilt(500, 100), _tilt(700, 100)] + [_tilt(a, 25) for a in (0, 450, 900, 1175)]
+    none = [FAR_PLANE] * 50 + [_flat_plane(int(k) * 0.01) for k in rng.integers(0, QUADS, 50)] + \
+           [_flat_plane(int(k) * 0.01 + 0.004) for k in rng.integers(0, QUADS, 50)]
+    thin = [_tilt(int(a), int(m)) for m in rng.choice([1, 2, 3], 243, p=[0.6, 0.3, 0.1]) for a in [rng.integers(0, QUADS - m + 1)]]
+    planes = np.stack(big + none + thin)
+    return np.ascontiguousarray(planes[rng.permutation(len(planes))]), rng
+
+
+@pytest.mark.parametrize("fields,base", [((), 2 ** 31 + 5), ((), 2 ** 32 + 5), (("normal",), -(-2 ** 32 // 3) + 5),
+                                         (("segment",), -(-2 ** 32 // 6) + 5)],
+                         ids=["keys-2^31", "keys-2^32", "normal-2^32/3", "segment-2^32/6"])
+def test_section_csr_rooms_at_large_slots(rt, stack, fields, base):
+    """test_box_csr_rooms_beyond_32_bits for rt_list_sections, whose heap has slot arithmetic of its own: sc_get, sc_put and
+    sc_sift_down index segment + 6 * q and normal + 3 * q, and the pair's record slot travels through the heap in the first word of
+    the entry's segment (of its normal when no segment is asked for).  400 planes on the quad stack with hand-made offsets base +
+    cumsum(room), counted in slots, rooms below, at and above each count (two deep heaps of 400 pairs at half their count, so most
+    arrivals replace the root and sift a long way with their slot); the lists run to 1200 entries.  With the keys alone the base is
+    2^31 + 5 and 2^32 + 5 (xl_room's start and the key index); with the normal it is ceil(2^32 / 3) + 5, with the segment
+    ceil(2^32 / 6) + 5, so that 3 * q and 6 * q pass 2^32 where q does not.  In every given field of W words per slot the window
+    around the rooms equals the shim's rooms, guard words of 64 slots either side included, and the first W * 4096 words (where a
+    start cut to 32 bits, or a product 3 * q or 6 * q taken in 32 bits, would land: W * base mod 2^32 is 17 and 32) keep their
+    guard.  Float fields are compared as int32 words.  count equals the shim's.  (Every quad has the normal (0, 0, 1), so the normal
+    case shows where the words go and no more; a slot that the sift-up or sc_sift_down leaves behind shows in the segment case, whose
+    segments differ from triangle to triangle.)"""
+    import torch
+    planes, rng = _csr_planes()
+    n = len(planes)
+    given = ("instance", "triangle") + fields
+    c = sc.count_sections(stack.so, planes).astype(np.int64)
+    assert c.max() == 1200 and (c == 400).sum() == 2 and (c == 100).sum() == 4 and (c == 0).sum() == 150, np.unique(c, return_counts=True)
+    assert set(np.unique(c)) == {0, 4, 8, 12, 100, 400, 1200}
+    room = np.maximum(c + rng.integers(-1, 3, n), 0)
+    half = np.flatnonzero(c == 400)
+    room[half] = c[half] // 2
+    assert (room < c).any() and (room > c).any() and (room == c).any() and (room == 0).any()
+    assert all((room[c == v] < v).any() and (room[c == v] > v).any() for v in (4, 8))       # (thin rooms of either kind)
+    rooms = int(room.sum())
+    assert rooms + 5 + 64 <= 4096                               # (offsets mod 2^32 fall inside the head window)
+    for k in given:                                             # (a word index cut to 32 bits falls inside the head window)
+        W = SC_WIDTH[k]
+        assert W * base < 2 ** 32 or (W * base) % 2 ** 32 + W * (rooms + 64) <= W * 4096, (k, base)
+    if fields:                                                  # (the product passes 2^32, the slot not 2^31)
+        assert base + rooms + 64 < 2 ** 31 and SC_WIDTH[fields[0]] * base > 2 ** 32
+    else:
+        assert base > 2 ** 31
+    offsets = (base + _cumsum(room)).astype(np.int64)
+    nslots = base + rooms + 64
+    _need_memory(4 * nslots * sum(SC_WIDTH[k] for k in given))
+    lo, hi = base - 64, base + rooms + 64
+    ref = sc.rooms(stack.so, planes, offsets=offsets - lo, slots=hi - lo, fill=SC_FILL)
+    _eq(ref["count"], c, "the shim's count beside its rooms")
+    bufs = None
+    try:
+        bufs = {k: torch.empty(SC_WIDTH[k] * nslots, dtype=torch.int32, device="cuda") for k in given}
+        for k, b in bufs.items():
+            b[SC_WIDTH[k] * lo:SC_WIDTH[k] * hi].fill_(GUARD32)
+            b[:SC_WIDTH[k] * 4096].fill_(GUARD32)
+        cnt = torch.full((n,), -9, dtype=torch.int32, device="cuda")
+        doff = torch.from_numpy(offsets).cuda()
+        pt, = _up((planes,))
+        assert _section_list(rt, stack.handle, pt, n, doff.data_ptr(), 0, bufs, cnt) == 0
+        for k in given:
+            W = SC_WIDTH[k]
+            window, head = bufs[k][W * lo:W * hi].cpu().numpy(), bufs[k][:W * 4096].cpu().numpy()
+            assert (head == GUARD32).all(), "%s: %d of the array's first %d words were written" % (k, int((head != GUARD32).sum()), W * 4096)
+            _eq(window, _sc_words(ref[k], k), "%s rooms at slot %d" % (k, base))
+        _eq(cnt.cpu().numpy(), ref["count"], "count")
+    finally:
+        del bufs
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("fields,n", [((), 2 ** 20 + 64), (("segment",), 2 ** 19 + 64)], ids=["keys", "segment"])
+def test_section_fixed_rooms_at_large_slots(rt, stack, fields, n):
+    """max_hits = 2049 on the quad stack; every plane but the last 64 lies far off.  With the keys alone n = 2^20 + 64 and the last 64
+    rooms start beyond slot 2^31; with the segment n = 2^19 + 64, they start at slot 1 074 266 112, and 6 * q there is about 6.4e9,
+    above 2^32.  The last 64 rooms equal the shim's fixed rooms in every given field, with count and without it.  Their counts lie
+    below K (16 planes over 25 to 124 quads, and 15 thin ones), between K and the scene's 4800 (32 planes), and at 4800 (x = 0.5);
+    17 of them fill their room from instance 0 alone, so the run without count asks `go` before instance 1 with a full room and reads
+    the room's root p.instance[i * K] at a slot beyond 2^31 (keys alone) or 2^30 (with the segment).  (That read cannot change a
+    room: a full room's keys all come from earlier instances, so a correct read always ends the traversal, and a wrong one that goes
+    on finds only greater keys.  What the run shows is that the read stays inside the array and the rooms are right, no more.)  The
+    rooms of a sample of the other planes (the first, the last, and those around the slots where q passes 2^31 and 6 * q passes
+    2^31 and 2^32) are all padding: keys of -1 and segment words of 0.0."""
+    import torch
+    K = 2049
+    rng = np.random.default_rng(103)
+    few, mid, full = rng.integers(25, 125, 16), rng.integers(520, 1000, 16), rng.integers(1030, 1190, 16)
+    ms = np.concatenate([few, mid, full, rng.integers(1, 4, 15)])
+    last = [_tilt(int(a), int(m)) for m in ms for a in [rng.integers(0, QUADS - m + 1)]] + [X_HALF]
+    order = rng.permutation(64)
+    last, want = np.ascontiguousarray(np.stack(last)[order]), np.append(4 * ms, 4 * QUADS)[order]
+    planes = np.tile(FAR_PLANE, (n, 1, 1))
+    planes[-64:] = last
+    given = ("instance", "triangle") + fields
+    ref = sc.rooms(stack.so, last, max_hits=K)
+    c = ref["count"]
+    _eq(c, want.astype(np.int32), "the shim's counts of the last 64 planes")
+    assert ((c >= 100) & (c < 500)).sum() == 16 and ((c >= K) & (c < 4 * QUADS)).sum() == 32 and (c == 4 * QUADS).sum() == 1, c
+    assert ((c > 0) & (c <= 12)).sum() == 15 and (c // 2 >= K).sum() == 17
+    W = sum(SC_WIDTH[k] for k in given)
+    assert (n - 64) * K * max(SC_WIDTH[k] for k in given) > 2 ** 31 * (1 if not fields else 2)
+    assert (sc.count_sections(stack.so, planes[:64]) == 0).all()
+    _need_memory(4 * W * n * K)
+    marks = [2 ** 31 // K, 2 ** 31 // 6 // K, 2 ** 32 // 6 // K]
+    sample = sorted({i for i in [0, 1, 63, 64, n // 2, n - 66, n - 65] + [m + j for m in marks for j in (-1, 0, 1)] if i < n - 64})
+    assert len(sample) >= 13
+    bufs = None
+    try:
+        bufs = {k: torch.empty(SC_WIDTH[k] * n * K, dtype=torch.int32, device="cuda") for k in given}
+        pt, = _up((planes,))
+        for with_count in (True, False):
+            at = "with count" if with_count else "without count"
+            for k, b in bufs.items():
+                w = SC_WIDTH[k] * K
+                for i in sample:
+                    b[i * w:(i + 1) * w].fill_(GUARD32)
+                b[(n - 64) * w:].fill_(GUARD32)
+            cnt = torch.full((n,), -9, dtype=torch.int32, device="cuda") if with_count else None
+            assert _section_list(rt, stack.handle, pt, n, None, K, bufs, cnt) == 0
+            for k in given:
+                w = SC_WIDTH[k] * K
+                _eq(bufs[k][(n - 64) * w:].cpu().numpy(), _sc_words(ref[k], k), "%s of the last 64 rooms, %s" % (k, at))
+                pad = 0 if k == "segment" else -1
+                for i in sample:
+                    room = bufs[k][i * w:(i + 1) * w].cpu().numpy()
+                    assert (room == pad).all(), "%s of room %d (a plane without pairs), %s: %d words are not padding" % (
+                        k, i, at, int((room != pad).sum()))
             if with_count:
                 got = cnt.cpu().numpy()
                 _eq(got[-64:], c, "count of the last 64")

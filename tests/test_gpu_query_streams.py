@@ -1,6 +1,6 @@
 """The `stream` argument of the query wrappers on the torch path, in both forms the docstrings promise: a torch.cuda.Stream and the raw
-hipStream_t of one.  Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes and occupancy grids)
-runs once with each on a stream that is not the current one, and both results equal the numpy path's for the same inputs bit for
+hipStream_t of one.  Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes and occupancy grids,
+plane sections) runs once with each on a stream that is not the current one, and both results equal the numpy path's for the same inputs bit for
 bit (the numpy path is held to the oracles by the family's own tests: none is needed here)."""
 import numpy as np
 import pytest
@@ -18,6 +18,7 @@ def _queries(s, q, **kw):
     nearby = s.NEARBY_LIST_OUTPUTS + ("count", "pops")
     pairs = s.INTERSECT_LIST_OUTPUTS + ("count", "pops")
     boxed = s.BOX_LIST_OUTPUTS + ("count", "pops")
+    cut = s.SECTION_LIST_OUTPUTS + ("count", "pops")
     grid_kw = kw or dict(as_numpy=True)                         # (the grid takes no arrays: numpy results are asked for by name)
     return {
         "trace_rays": lambda: s.trace_rays(o, d, outputs=s.RAY_OUTPUTS, **kw),
@@ -37,12 +38,16 @@ def _queries(s, q, **kw):
         "list_in_boxes_csr": lambda: s.list_in_boxes(q["boxes"], outputs=boxed, **kw),
         "list_in_boxes_k2": lambda: s.list_in_boxes(q["boxes"], max_hits=2, outputs=boxed, **kw),
         "occupancy_grid": lambda: s.occupancy_grid(GRID[0], GRID[1], GRID[2], outputs=s.GRID_OUTPUTS, **grid_kw),
+        "count_sections": lambda: s.count_sections(q["planes"], outputs=s.SECTION_COUNT_OUTPUTS, **kw),
+        "list_sections_csr": lambda: s.list_sections(q["planes"], outputs=cut, **kw),
+        "list_sections_k2": lambda: s.list_sections(q["planes"], max_hits=2, outputs=cut, **kw),
     }
 
 
 QUERIES = ("trace_rays", "occluded", "closest_points", "count_crossings", "winding_numbers", "signed_distance", "list_crossings_csr",
            "list_crossings_k2", "list_nearby_csr", "list_nearby_k2", "count_intersecting", "list_intersecting_csr", "list_intersecting_k2",
-           "count_in_boxes", "list_in_boxes_csr", "list_in_boxes_k2", "occupancy_grid")
+           "count_in_boxes", "list_in_boxes_csr", "list_in_boxes_k2", "occupancy_grid", "count_sections", "list_sections_csr",
+           "list_sections_k2")
 GRID = ((-1.3, -1.2, -1.1), (0.41, 0.43, 0.47), (7, 6, 5))      # origin, spacing, dims: a grid around the blob, partial bricks
 
 
@@ -61,6 +66,7 @@ def staged(rt, scenes, blob5k):
              md=rng.uniform(0.1, 0.5, N).astype(F32), tris=tris, skip=rng.integers(-1, 1, N).astype(np.int32))
     edge = rng.uniform(0.05, 0.4, (N, 3))                       # boxes around the same points: some cut the surface, some do not
     q["boxes"] = np.stack([pts - edge / 2, pts + edge / 2], axis=1).astype(F32)
+    q["planes"] = np.stack([pts, rng.normal(size=(N, 3))], axis=1).astype(F32)      # planes through the same points: most cut the blob
     q = {k: np.ascontiguousarray(v) for k, v in q.items()}
     dq = {k: torch.from_numpy(v).cuda() for k, v in q.items()}
     torch.cuda.synchronize()

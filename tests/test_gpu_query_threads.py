@@ -1,5 +1,5 @@
-"""Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes) on ONE scene from seven host threads at
-once, beside renders, instance updates, refits and a device-resident rebuild ("Threads"): the entry points share scene_launch, which takes the scene's call lock for the launches of
+"""Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes, plane sections) on ONE scene from eight host
+threads at once, beside renders, instance updates, refits and a device-resident rebuild ("Threads"): the entry points share scene_launch, which takes the scene's call lock for the launches of
 one call (two nested calls for rt_signed_distance, a count launch and the scan's launches for the *_offsets calls) and leaves it before
 any wait.  test_gpu_threads.test_four_threads_on_one_scene, whose phase scheme and helpers this reuses, predates the families and
 queries with rt_trace_rays and rt_occluded only.  Every result of every call is compared bit for bit with the CPU shims' result for the
@@ -18,9 +18,11 @@ import point_oracle
 import query_points as qp
 import query_rays as qr
 import scene_defs as sd
+import section_oracle as sc
 import tri_intersect_oracle as ti
 from test_gpu_boxes import families as box_families
 from test_gpu_crossings import _cam, _eq
+from test_gpu_sections import families as section_families
 from test_gpu_threads import _Threads, _deformed, _host_arrays, _params, _render_batch_fn, _same_frame
 from test_gpu_tri_intersect import families as tri_families
 
@@ -31,14 +33,15 @@ POINT_FIELDS = ("distance", "instance", "triangle", "point", "normal", "barycent
 XL_FIELDS = ("t", "instance", "triangle", "sign", "barycentric", "uv", "point")
 TI_FIELDS = ("instance", "triangle", "normal", "segment")
 BX_FIELDS = ("instance", "triangle")
+SC_FIELDS = ("instance", "triangle", "segment", "normal")
 GRID_DIMS = (5, 3, 2)
-WORKERS = ("W1", "W2", "W3", "W4", "W5", "W6", "W7")
+WORKERS = ("W1", "W2", "W3", "W4", "W5", "W6", "W7", "W8")
 
 
 def _oracle_results(so, q, frames_of):
     """Everything the workers ask, from the shims, for the oracle scene's current state: name -> dict or array"""
     o, d, tmax, pts, md, radius, tris, skip = (q[k] for k in ("o", "d", "tmax", "pts", "md", "radius", "tris", "skip"))
-    boxes, (origin, spacing) = q["boxes"], q["grid"]
+    boxes, (origin, spacing), planes = q["boxes"], q["grid"], q["planes"]
     return {
         "closest": point_oracle.closest_points(so, pts),
         "closest_md": point_oracle.closest_points(so, pts, md),
@@ -59,6 +62,9 @@ def _oracle_results(so, q, frames_of):
         "bx_csr": bo.list_in_boxes(so, boxes),
         "bx_k4": bo.list_in_boxes(so, boxes, max_hits=4),
         "bx_grid": bo.count_in_boxes(so, bo.grid_boxes(origin, spacing, GRID_DIMS)).reshape(GRID_DIMS[::-1]),
+        "sc_count": sc.count_sections(so, planes),
+        "sc_csr": sc.list_sections(so, planes),
+        "sc_k4": sc.list_sections(so, planes, max_hits=4),
         "frames": frames_of(so),
     }
 
@@ -72,8 +78,8 @@ def _same(got, ref, keys, where):
         _eq(_np(got[k]), ref[k], "%s %s" % (where, k))
 
 
-def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
-    """Seven workers, each on its own torch stream with at least three calls per phase, and a mutator, through five phases that alternate
+def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
+    """Eight workers, each on its own torch stream with at least three calls per phase, and a mutator, through five phases that alternate
     two known states (S0: as uploaded; S1: instance 2 moved with rt_scene_update_instance_async and mesh 1 refitted from host arrays,
     both on the mutator's stream; the last change back to S0 is rt_scene_rebuild_mesh_device of the refitted mesh to its rest shape).
     W1: closest_points with every output, signed_distance (a nested call under one hold of the lock), closest_points bounded.
@@ -86,6 +92,9 @@ def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     W7: count_in_boxes for `any` alone (the kernel that stops at the first pair), list_in_boxes CSR (a count launch, the scan and the
     fill, whose rooms are heaps), max_hits = 4 without count (rooms that end the traversal early), occupancy_grid with both outputs
     on a (5, 3, 2) grid over the scene's box in S0.
+    W8: count_sections for `any` alone (the kernel that stops at the first pair), list_sections CSR with all four fields (a count
+    launch and the scan under one hold of the lock, then the fill, whose rooms are heaps that carry each pair's record slot),
+    max_hits = 4 with the normal alone and without count (the slot travels in the normal, the rooms end the traversal early).
     Between phases the state change is ordered after every worker's last call and before every worker's next by events.  Every
     result of every call equals the shims' for its phase's state, every frame the oracle's, and no call fails."""
     import torch
@@ -116,7 +125,8 @@ def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     tris = np.ascontiguousarray(np.concatenate([f[1] for f in tri_families(rng, o_, desc, n=400)]), F32)
     # (a generator of their own: the draws below stay what they were before the boxes came)
     boxes = np.ascontiguousarray(np.concatenate([f[1] for f in box_families(np.random.default_rng(83), o_, desc, n=600)]), F32)
-    for name, a in (("rays", o), ("points", pts), ("triangles", tris), ("boxes", boxes)):
+    planes = np.ascontiguousarray(np.concatenate([f[1] for f in section_families(np.random.default_rng(89), o_, desc, n=600)]), F32)
+    for name, a in (("rays", o), ("points", pts), ("triangles", tris), ("boxes", boxes), ("planes", planes)):
         assert 2000 <= len(a) <= 4000, (name, len(a))
     dist = point_oracle.closest_points(so, pts)["distance"]
     lo, hi = qp.scene_box(o_, desc, desc.oracle_meshes)
@@ -129,7 +139,7 @@ def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     near = (dist * rng.uniform(1.0, 1.5, len(pts)) + diag * F32(1e-3)).astype(F32)
     q = dict(o=o, d=d, tmax=qr.special_tmax(rng, len(o)), pts=pts, md=qp.special_bounds(rng, dist),
              radius=np.ascontiguousarray(np.where(dist > F32(0.1) * diag, np.nextafter(dist, F32(np.inf)), near), F32), tris=tris,
-             skip=rng.integers(-1, len(desc.instances), len(tris)).astype(np.int32), boxes=boxes, grid=grid)
+             skip=rng.integers(-1, len(desc.instances), len(tris)).astype(np.int32), boxes=boxes, grid=grid, planes=planes)
 
     def frames_of(scene):
         return [scene.render(W, H, K, D, p, threads=16, planes=False)["img"] for p in poses]
@@ -139,7 +149,7 @@ def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     want[1] = _oracle_results(so, q, frames_of)
     so.close()
     for name, key in (("closest", "distance"), ("xl_csr", "offsets"), ("nb_csr", "offsets"), ("ti_csr", "offsets"),
-                      ("bx_csr", "offsets")):
+                      ("bx_csr", "offsets"), ("sc_csr", "offsets")):
         assert not np.array_equal(want[0][name][key], want[1][name][key]), name + ": the two states give one result"
     assert any(not np.array_equal(a, b) for a, b in zip(want[0]["frames"], want[1]["frames"]))
 
@@ -205,6 +215,11 @@ def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
                     bx_k4=sp.list_in_boxes(dq["boxes"], max_hits=4, outputs=BX_FIELDS, stream=s),
                     bx_grid=sp.occupancy_grid(grid[0], grid[1], GRID_DIMS, outputs=("occupied", "count"), stream=s))
 
+    def w8(s, ph):
+        return dict(sc_any=sp.count_sections(dq["planes"], outputs=("any",), stream=s),
+                    sc_csr=sp.list_sections(dq["planes"], outputs=SC_FIELDS, stream=s),
+                    sc_k4=sp.list_sections(dq["planes"], max_hits=4, outputs=("normal",), stream=s))
+
     def w6():
         for ph in range(len(phases)):
             results["W6"][ph] = dict(xl_csr=sp.list_crossings(q["o"], q["d"]),
@@ -214,7 +229,7 @@ def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
             next_phase.wait()
             ready[ph].synchronize()                             # (its launches go to the NULL stream, which no torch event orders)
 
-    for name, calls in (("W1", w1), ("W2", w2), ("W3", w3), ("W4", w4), ("W5", w5), ("W7", w7)):
+    for name, calls in (("W1", w1), ("W2", w2), ("W3", w3), ("W4", w4), ("W5", w5), ("W7", w7), ("W8", w8)):
         th.start(name, worker, name, calls)
     th.start("W6", w6)
     try:
@@ -278,6 +293,11 @@ def test_seven_query_threads_on_one_scene(rt, orc, scenes, blob5k):
         _same(r["bx_k4"], ref["bx_k4"], BX_FIELDS, at + " list_in_boxes K=4 without count")
         _eq(_np(r["bx_grid"]["count"]), ref["bx_grid"], at + " occupancy_grid count")
         assert np.array_equal(_np(r["bx_grid"]["occupied"]), ref["bx_grid"] > 0), at + " occupancy_grid occupied"
+        r = results["W8"][ph]
+        assert set(r["sc_any"]) == {"any"} and set(r["sc_k4"]) == {"normal"}
+        assert np.array_equal(_np(r["sc_any"]["any"]), ref["sc_count"] > 0), at + " count_sections any alone"
+        _same(r["sc_csr"], ref["sc_csr"], SC_FIELDS + ("offsets", "query_index", "count"), at + " list_sections CSR")
+        _same(r["sc_k4"], ref["sc_k4"], ("normal",), at + " list_sections K=4, the normal alone, without count")
     sp.close()
 
 
