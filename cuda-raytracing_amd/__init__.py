@@ -67,6 +67,8 @@ _BOX_COUNT_OUTPUTS = ("count", "any", "pops")
 _BOX_LIST_OUTPUTS = ("instance", "triangle")
 _SECTION_COUNT_OUTPUTS = ("count", "any", "pops")
 _SECTION_LIST_OUTPUTS = ("instance", "triangle", "segment", "normal")
+_SEGMENT_OUTPUTS = ("distance", "instance", "triangle", "parameter", "segment_point", "point", "normal", "barycentric", "uv", "crossings",
+                    "clearance", "within", "pops")
 
 
 class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers, any may be NULL)
@@ -113,6 +115,10 @@ class RtSectionList(C.Structure):           # include/rt_hip.h (device pointers;
     _fields_ = [(n, _vp) for n in _SECTION_LIST_OUTPUTS + ("count", "pops")]
 
 
+class RtSegmentHits(C.Structure):           # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in _SEGMENT_OUTPUTS]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -131,7 +137,8 @@ RT_HIP_SYMBOLS = [
     "rt_crossing_offsets", "rt_list_crossings", "rt_nearby_offsets_workspace_bytes", "rt_nearby_offsets", "rt_list_nearby",
     "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting",
     "rt_count_in_boxes", "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "rt_occupancy_grid",
-    "rt_count_sections", "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections"]
+    "rt_count_sections", "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections",
+    "rt_closest_to_segments"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -289,6 +296,7 @@ def _declare(h, s):
     h.rt_section_offsets_workspace_bytes.argtypes = [C.c_int32]
     h.rt_section_offsets.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_sections.argtypes = [_vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtSectionList), _vp, C.c_int]
+    h.rt_closest_to_segments.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtSegmentHits), _vp, C.c_int]
     h.rt_occupancy_grid.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
@@ -801,6 +809,29 @@ class Scene:
 
     GRID_OUTPUTS = ("occupied", "count")
 
+    SEGMENT_OUTPUTS = _SEGMENT_OUTPUTS                                  # the fields of RtSegmentHits
+
+    def closest_to_segments(self, segments, max_distance=None, outputs=("distance", "instance", "triangle", "parameter"), stream=None):
+        """The nearest point of the scene's triangles to each of the caller's segments, and whether a capsule touches anything
+        (rt_closest_to_segments; the rule, bit for bit a brute-force loop over every instance and triangle, is rule 13 of
+        include/rt_hip.h): dict of the wanted SEGMENT_OUTPUTS of the segments' leading shape -- distance (float32, FLT_MAX on a miss),
+        instance / triangle (int32, -1 on a miss), parameter (float32 in [0, 1]: where on the segment its nearest point lies),
+        segment_point / point ([3] float32, world: the nearest pair, on the segment and on the triangle), normal ([3]), barycentric /
+        uv ([2]) as closest_points gives them, crossings (int32, triangles the segment pierces: count_crossings with directions
+        P1 - P0 and tmax 1), clearance (float32, 0 where crossings > 0, else distance), within (int32 0 / 1: a triangle within
+        max_distance of the segment, or pierced by it -- the capsule overlap test; wanted alone or with pops, the distance traversal
+        stops at the first triangle in reach), pops (int32, interior nodes visited by the distance traversal).  The point fields
+        describe the nearest triangle even where the segment pierces another.  segments: float32 [..., 2, 3] world end points,
+        contiguous.  max_distance: None (+inf) or float32 of the leading shape, the capsule's radius (inclusive; NaN or negative =
+        nothing in reach).  torch tensors: asynchronous on `stream` (default the current stream); numpy arrays: copied to the device
+        and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.SEGMENT_OUTPUTS)
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            hits = RtSegmentHits(*[ptr.get(k) for k in _SEGMENT_OUTPUTS])
+            check(h.rt_closest_to_segments(handle, ins[0], ins[1], n, C.byref(hits), st, sync), "rt_closest_to_segments")
+        return _device_query(self, [("segments", segments), ("max_distance", max_distance)], outputs, call, stream, **_SEGMENT_INPUTS)
+
     def occupancy_grid(self, origin, spacing, dims, outputs=("occupied",), stream=None, as_numpy=False):
         """count_in_boxes on the cells of a regular grid, which the kernel makes itself (rt_occupancy_grid): cell (ix, iy, iz) is the
         box from origin + i*spacing to origin + (i + 1)*spacing per axis in float32, so neighbouring cells share their faces exactly.
@@ -1109,7 +1140,8 @@ _FIELDS = dict(
     t=((), np.float32), distance=((), np.float32), sdf=((), np.float32), instance=((), np.int32), triangle=((), np.int32),
     count=((), np.int32), winding=((), np.int32), pops=((), np.int32), sign=((), np.int8), occluded=((), np.uint8),
     any=((), np.bool_), occupied=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
-    point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32))
+    point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32), parameter=((), np.float32),
+    segment_point=((3,), np.float32), crossings=((), np.int32), clearance=((), np.float32), within=((), np.int32))
 
 
 def _check_outputs(outputs, allowed, extras=()):
@@ -1351,6 +1383,7 @@ _INTERSECT_LIST = _ListKind(_INTERSECT_LIST_OUTPUTS, ("instance", "triangle"), R
 _BOX_INPUTS = dict(shape=(2, 3))
 _BOX_LIST = _ListKind(_BOX_LIST_OUTPUTS, ("instance", "triangle"), RtBoxList,
                       "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "query_index", inputs=_BOX_INPUTS)
+_SEGMENT_INPUTS = dict(shape=(2, 3))                # (a box array's shape: P0 then P1)
 _PLANE_INPUTS = dict(shape=(2, 3))                  # (a box array's shape: point then normal)
 _SECTION_LIST = _ListKind(_SECTION_LIST_OUTPUTS, ("instance", "triangle"), RtSectionList,
                           "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections", "query_index",

@@ -25,6 +25,7 @@ struct RtBoxCounts;
 struct RtBoxList;
 struct RtSectionCounts;
 struct RtSectionList;
+struct RtSegmentHits;
 
 class Scene {
 public:
@@ -113,6 +114,10 @@ public:
                         void* stream = nullptr, bool synchronize = false);
     int list_sections(const float* d_planes, int32_t n, const int64_t* d_offsets, int32_t max_hits, const RtSectionList& out,
                       void* stream = nullptr, bool synchronize = false);
+    // Segment queries on the device scene: rt_closest_to_segments of include/rt_hip.h (rule 13), where the semantics are.  Segments
+    // ([n][2][3] world, P0 then P1), radii (optional, NULL = +inf) and outputs are DEVICE arrays.  Returns the status.
+    int closest_to_segments(const float* d_segments, const float* d_max_distance, int32_t n, const RtSegmentHits& out,
+                            void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

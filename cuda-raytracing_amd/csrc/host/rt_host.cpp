@@ -749,6 +749,13 @@ int Scene::list_sections(const float* d_planes, int32_t n, const int64_t* d_offs
     return last_error;
 }
 
+int Scene::closest_to_segments(const float* d_segments, const float* d_max_distance, int32_t n, const RtSegmentHits& out, void* stream,
+                               bool synchronize)
+{
+    last_error = d_scene ? rt_closest_to_segments(d_scene, d_segments, d_max_distance, n, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

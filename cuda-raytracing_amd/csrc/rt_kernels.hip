@@ -2548,6 +2548,225 @@ __global__ __launch_bounds__(kPointBlock, 8) void closest_point_kernel(const Poi
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Segment queries (rt_closest_to_segments): the nearest point of the scene's triangles to each of the caller's segments, equal bit for
+// bit to a brute-force minimum over every (instance, triangle) -- rule 13 of include/rt_hip.h, the pruning argument in DESIGN.md
+// section 18.  closest_point_kernel's shape: one wave per workgroup, one segment per lane, the nearest-first traversal, the lower
+// bound now between the segment's box and the child's.  The crossing half (step 6) is segment_crossing_kernel, after xq_trace.
+// ---------------------------------------------------------------------------------------------------------
+struct SegParams {
+    const float4* records;
+    const float* tri_uv;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* segs;          // [n][2][3] world end points
+    const float* max_distance;  // [n] or null (= +inf)
+    int32_t n;
+    float* distance;            // outputs, each optional (null = not wanted)
+    int32_t *instance, *triangle;
+    float *parameter, *segment_point, *point, *normal, *barycentric, *uv;
+    int32_t* crossings;         // written by segment_crossing_kernel
+    float* clearance;           // the distance here, set to 0 by segment_crossing_kernel where the segment crosses
+    int32_t* within;            // 1 where there is a candidate here, set to 1 by segment_crossing_kernel where the segment crosses
+    int32_t* pops;
+};
+
+__device__ __forceinline__ float sq_clamp01(float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; }    // (a NaN gives 0)
+
+// Ericson's closest pair of the segments q0 + s * d and e0 + u * f (Real-Time Collision Detection 5.1.9) as (s, u), both in [0, 1],
+// in rule 13 step 4's fixed fp32 sequence (out of line: called three times per triangle)
+__device__ __noinline__ float2 sq_segseg(V3 q0, V3 d, V3 e0, V3 f)
+{
+    const V3 r = q0 - e0;
+    const float a = dot(d, d), e = dot(f, f), ff = dot(f, r);
+    if (!(a > 0.0f)) return make_float2(0.0f, e > 0.0f ? sq_clamp01(ff / e) : 0.0f);
+    const float c = dot(d, r);
+    if (!(e > 0.0f)) return make_float2(sq_clamp01(-c / a), 0.0f);
+    const float b = dot(d, f), den = a * e - b * b;
+    float s = den > 0.0f ? sq_clamp01((b * ff - c * e) / den) : 0.0f;
+    float u = (b * s + ff) / e;
+    if (!(u >= 0.0f)) { u = 0.0f; s = sq_clamp01(-c / a); }
+    else if (u > 1.0f) { u = 1.0f; s = sq_clamp01((b - c) / a); }
+    return make_float2(s, u);
+}
+
+// One candidate (s, b1, b2) of a triangle against the best of the triangle so far (w = d2, x = s, y = b1, z = b2): the smaller d2,
+// the earlier of equals; a NaN d2 never replaces one that is not NaN
+__device__ __forceinline__ void sq_candidate(float4& best, V3 q0, V3 d, V3 a, V3 ab, V3 ac, float s, float b1, float b2)
+{
+    const V3 x = v3(q0.x + s * d.x, q0.y + s * d.y, q0.z + s * d.z);
+    const float d2 = pq_d2(x - pq_combine(a, ab, ac, b1, b2));
+    if (d2 < best.w || best.w != best.w) best = make_float4(s, b1, b2, d2);
+}
+
+// rule 13 step 3 on one triangle: (s, b1, b2, d2) of its candidate
+__device__ __forceinline__ float4 sq_triangle(V3 q0, V3 q1, V3 a, V3 ab, V3 ac)
+{
+    const V3 d = q1 - q0;
+    float4 best = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(0x7fc00000));
+    const float2 w0 = pq_weights(q0, a, ab, ac);
+    sq_candidate(best, q0, d, a, ab, ac, 0.0f, w0.x, w0.y);
+    const float2 w1 = pq_weights(q1, a, ab, ac);
+    sq_candidate(best, q0, d, a, ab, ac, 1.0f, w1.x, w1.y);
+    if (dot(d, d) > 0.0f) {                                     // (a zero-length segment is a point: closest_point_kernel's answer)
+        const float2 e0 = sq_segseg(q0, d, a, ab);
+        sq_candidate(best, q0, d, a, ab, ac, e0.x, e0.y, 0.0f);
+        const float2 e1 = sq_segseg(q0, d, a, ac);
+        sq_candidate(best, q0, d, a, ab, ac, e1.x, 0.0f, e1.y);
+        const float2 e2 = sq_segseg(q0, d, a + ab, ac - ab);
+        sq_candidate(best, q0, d, a, ab, ac, e2.x, 1.0f - e2.y, e2.y);
+    }
+    return best;
+}
+
+// One axis of the lower bound: the child's interval lo..hi scaled and widened exactly as pq_gap does it, against the segment's
+// widened interval slo..shi; the gap only where a compare says it is positive (a NaN anywhere gives 0, never a prune)
+__device__ __forceinline__ float sq_gap(float lo, float hi, float s, float slo, float shi)
+{
+    const float x = lo * s, y = hi * s;
+    const float l = s < 0.0f ? y : x, h = s < 0.0f ? x : y;
+    const float m = fmaxf(fabsf(l), fabsf(h)) * 0x1p-16f + 0x1p-126f;
+    const float a = (l - m) - shi, b = slo - (h + m);
+    return a > 0.0f ? a : (b > 0.0f ? b : 0.0f);
+}
+__device__ __forceinline__ float sq_box_lb(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 slo, V3 shi)
+{
+    const float gx = sq_gap(lx, hx, s.x, slo.x, shi.x), gy = sq_gap(ly, hy, s.y, slo.y, shi.y), gz = sq_gap(lz, hz, s.z, slo.z, shi.z);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+// the segment's interval on one axis, widened by 2^-16 of its larger end magnitude plus FLT_MIN: every computed X of rule 13 lies in it
+__device__ __forceinline__ void sq_interval(float a, float b, float& lo, float& hi)
+{
+    const float m = fmaxf(fabsf(a), fabsf(b)) * 0x1p-16f + 0x1p-126f;
+    lo = fminf(a, b) - m; hi = fmaxf(a, b) + m;
+}
+
+// segment i's ends in instance `in`'s scaled mesh space (read again wherever they are needed: not held across the traversal)
+__device__ __forceinline__ void sq_ends(const SegParams& p, int32_t i, const DevInstance& in, V3& q0, V3& q1)
+{
+    const float* g = p.segs + (size_t)i * 6;
+    q0 = apply_quat(in.q_pose, v3(g[0] - in.pose_xyz[0], g[1] - in.pose_xyz[1], g[2] - in.pose_xyz[2]));
+    q1 = apply_quat(in.q_pose, v3(g[3] - in.pose_xyz[0], g[4] - in.pose_xyz[1], g[5] - in.pose_xyz[2]));
+}
+
+// ANY: only within and / or pops are wanted of this half: the traversal ends at the first candidate, across instances too
+template <bool ANY>
+__global__ __launch_bounds__(kPointBlock, 8) void segment_closest_kernel(const SegParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kPointBlock]
+    const int32_t i = (int32_t)blockIdx.x * kPointBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const size_t i3 = (size_t)i * 3;
+    const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
+    int spill[kMaxStack - kLdsStack];
+    PointStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    // the best candidate so far by (d2, instance, tri_id); best_inst < 0 = none yet
+    float best = 0.0f, bs = 0.0f, b1 = 0.0f, b2 = 0.0f;
+    int32_t best_inst = -1, best_slot = 0, best_tid = 0, pops = 0;
+    for (int32_t k = 0; k < p.num_instances && cut2 >= 0.0f && !(ANY && best_inst >= 0); k++) {
+        const DevInstance& in = p.instances[k];
+        V3 q0, q1, slo, shi;
+        sq_ends(p, i, in, q0, q1);
+        sq_interval(q0.x, q1.x, slo.x, shi.x); sq_interval(q0.y, q1.y, slo.y, shi.y); sq_interval(q0.z, q1.z, slo.z, shi.z);
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: both child boxes, nearer first
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const float la = sq_box_lb(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, slo, shi);
+                const float lb = sq_box_lb(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, slo, shi);
+                const float lim = best_inst >= 0 ? best : cut2;
+                const bool pa = !(prune && la > lim), pb = !(prune && lb > lim);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                const bool a_near = !(lb < la);
+                if (pa && pb) stack.push(a_near ? rb : ra);
+                cur = (pa && pb) ? (a_near ? ra : rb) : (pa ? ra : (pb ? rb : kNeedPop));
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                bool found = false;
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    const float4 t0 = rec[0], t1 = rec[1], t2 = rec[2];
+                    V3 a, ab, ac;
+                    pq_triangle(t0, t1, t2, s, a, ab, ac);
+                    const float4 c = sq_triangle(q0, q1, a, ab, ac);
+                    if (c.w <= (best_inst >= 0 ? best : cut2)) {    // (NaN fails)
+                        const int32_t tid = p.tri_id[slot];
+                        if (best_inst < 0 || c.w < best || (best_inst == k && tid < best_tid)) {
+                            best = c.w; bs = c.x; b1 = c.y; b2 = c.z; best_inst = k; best_slot = slot; best_tid = tid;
+                        }
+                        found = true;
+                    }
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+                if (ANY && found) break;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel);
+    }
+    const bool got = best_inst >= 0;
+    if (p.pops) p.pops[i] = pops;
+    if (p.within) p.within[i] = got ? 1 : 0;
+    if constexpr (ANY) return;
+    const float dist = got ? sqrtf(best) : FLT_MAX;
+    if (p.distance) p.distance[i] = dist;
+    if (p.clearance) p.clearance[i] = dist;
+    if (p.instance) p.instance[i] = got ? best_inst : -1;
+    if (p.triangle) p.triangle[i] = got ? best_tid : -1;
+    if (p.parameter) p.parameter[i] = got ? bs : 0.0f;
+    if (p.barycentric) { p.barycentric[(size_t)i * 2] = got ? b1 : 0.0f; p.barycentric[(size_t)i * 2 + 1] = got ? b2 : 0.0f; }
+    if (!got) {
+        if (p.segment_point) { p.segment_point[i3] = 0.0f; p.segment_point[i3 + 1] = 0.0f; p.segment_point[i3 + 2] = 0.0f; }
+        if (p.point) { p.point[i3] = 0.0f; p.point[i3 + 1] = 0.0f; p.point[i3 + 2] = 0.0f; }
+        if (p.normal) { p.normal[i3] = 0.0f; p.normal[i3 + 1] = 0.0f; p.normal[i3 + 2] = 0.0f; }
+        if (p.uv) { p.uv[(size_t)i * 2] = 0.0f; p.uv[(size_t)i * 2 + 1] = 0.0f; }
+        return;
+    }
+    const DevInstance& in = p.instances[best_inst];
+    if (p.segment_point) {                                      // the winner's X again (same sequence), to world: apply_lre(inv_pose, X)
+        V3 q0, q1;
+        sq_ends(p, i, in, q0, q1);
+        const V3 d = q1 - q0;
+        const V3 x = v3(q0.x + bs * d.x, q0.y + bs * d.y, q0.z + bs * d.z);
+        const V3 o = apply_quat(in.q_inv_pose, v3(x.x - in.inv_pose_xyz[0], x.y - in.inv_pose_xyz[1], x.z - in.inv_pose_xyz[2]));
+        p.segment_point[i3] = o.x; p.segment_point[i3 + 1] = o.y; p.segment_point[i3 + 2] = o.z;
+    }
+    if (p.point) {                                              // the winner's c again (same sequence), closest_point_kernel's map
+        const float4* rec = p.records + (size_t)best_slot * 4;
+        V3 a, ab, ac;
+        pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+        const V3 c = pq_combine(a, ab, ac, b1, b2);
+        const V3 o = apply_quat(in.q_inv_pose, v3(c.x - in.inv_pose_xyz[0], c.y - in.inv_pose_xyz[1], c.z - in.inv_pose_xyz[2]));
+        p.point[i3] = o.x; p.point[i3 + 1] = o.y; p.point[i3 + 2] = o.z;
+    }
+    if (p.normal) {
+        const V3 n = pq_normal(p, in, best_slot);
+        p.normal[i3] = n.x; p.normal[i3 + 1] = n.y; p.normal[i3 + 2] = n.z;
+    }
+    if (p.uv) {                                                 // w = (1 - b2) - b1, uv = (w uv0 + b1 uv1) + b2 uv2 (closest_point_kernel's)
+        const float* t = p.tri_uv + (size_t)best_slot * 6;
+        const float u0 = (1.0f - b2) - b1;
+        p.uv[(size_t)i * 2] = (u0 * t[0] + b1 * t[2]) + b2 * t[4];
+        p.uv[(size_t)i * 2 + 1] = (u0 * t[1] + b1 * t[3]) + b2 * t[5];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Ray crossing counts and winding numbers (rt_count_crossings / rt_winding_numbers / rt_signed_distance): every triangle a ray
 // crosses within (0, tmax], both faces, with the sign of the crossing -- equal to a brute-force count over every (instance,
 // triangle); the rule is in include/rt_hip.h, the pruning argument in DESIGN.md section 12.  One wave per workgroup, one ray (or
@@ -2682,8 +2901,9 @@ __device__ __forceinline__ bool xq_box(float lx, float ly, float lz, float hx, f
     return !(tn > tf) && !(fz < 0.0f);
 }
 
-// One ray through every instance: count, winding and pops of rule 5
-__device__ __forceinline__ void xq_trace(const CrossParams& p, CrossStack& stack, V3 w, V3 d, float tmax, int32_t& count,
+// One ray through every instance: count, winding and pops of rule 5; P: CrossParams or SegParams
+template <typename P>
+__device__ __forceinline__ void xq_trace(const P& p, CrossStack& stack, V3 w, V3 d, float tmax, int32_t& count,
                                          int32_t& winding, int32_t& pops)
 {
     for (int32_t k = 0; k < p.num_instances; k++) {
@@ -2763,6 +2983,29 @@ __global__ __launch_bounds__(kCrossBlock, 8) void crossing_kernel(const CrossPar
         const int32_t med = max(min(w0, w1), min(max(w0, w1), w2));
         if (p.winding) p.winding[i] = med;
         if (p.sdf && med != 0) p.sdf[i] = -p.sdf[i];
+    }
+}
+
+// The crossing half of rt_closest_to_segments (rule 13 step 6): rt_count_crossings' count for the ray o = P0, d = P1 - P0, tmax = 1, one
+// segment per lane, patching what segment_closest_kernel wrote on the same stream -- clearance becomes 0 and within 1 where the
+// segment crosses a triangle (as the point form above patches sdf).  A lane whose answer cannot change any more does not traverse.
+__global__ __launch_bounds__(kCrossBlock, 8) void segment_crossing_kernel(const SegParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kCrossBlock]
+    const int32_t i = (int32_t)blockIdx.x * kCrossBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    if (!p.crossings && !p.clearance && p.within[i] != 0) return;   // (within alone, and the distance half has already said 1)
+    const float* g = p.segs + (size_t)i * 6;
+    const V3 w = v3(g[0], g[1], g[2]);
+    int spill[kMaxStack - kLdsStack];
+    CrossStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    int32_t count = 0, winding = 0, pops = 0;
+    xq_trace(p, stack, w, v3(g[3] - w.x, g[4] - w.y, g[5] - w.z), 1.0f, count, winding, pops);
+    if (p.crossings) p.crossings[i] = count;
+    if (count > 0) {
+        if (p.clearance) p.clearance[i] = 0.0f;
+        if (p.within) p.within[i] = 1;
     }
 }
 
@@ -5631,6 +5874,36 @@ int rt_closest_points(RtScene* s, const float* d_points, const float* d_max_dist
         p.point = out->point; p.normal = out->normal; p.barycentric = out->barycentric; p.uv = out->uv; p.pops = out->pops;
         const QueryShape k = query_shape(n, kPointBlock, p.stack_depth);
         hipLaunchKernelGGL(closest_point_kernel, k.groups, dim3(kPointBlock), k.lds, st, p);
+        return RT_OK;
+    });
+}
+
+// ---- segment queries --------------------------------------------------------------------------------------------------------
+int rt_closest_to_segments(RtScene* s, const float* d_segments, const float* d_max_distance, int32_t n, const RtSegmentHits* out,
+                           void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_segments || !out))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    // what only a full distance traversal gives; what the distance half feeds at all; what the crossing half feeds
+    const bool full = out->distance || out->instance || out->triangle || out->parameter || out->segment_point || out->point ||
+                      out->normal || out->barycentric || out->uv || out->clearance;
+    const bool near = full || out->within || out->pops, cross = out->crossings || out->clearance || out->within;
+    if (!near && !cross) return RT_E_INVALID;
+    // (both launches under one hold of the scene's lock: no other thread's update comes between the distance and the crossings)
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        SegParams p = scene_params<SegParams>(s);
+        p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
+        p.segs = d_segments; p.max_distance = d_max_distance; p.n = n;
+        p.distance = out->distance; p.instance = out->instance; p.triangle = out->triangle; p.parameter = out->parameter;
+        p.segment_point = out->segment_point; p.point = out->point; p.normal = out->normal; p.barycentric = out->barycentric;
+        p.uv = out->uv; p.crossings = out->crossings; p.clearance = out->clearance; p.within = out->within; p.pops = out->pops;
+        const QueryShape k = query_shape(n, kPointBlock, p.stack_depth);
+        if (near && full) hipLaunchKernelGGL(segment_closest_kernel<false>, k.groups, dim3(kPointBlock), k.lds, st, p);
+        else if (near) hipLaunchKernelGGL(segment_closest_kernel<true>, k.groups, dim3(kPointBlock), k.lds, st, p);
+        if (cross) {
+            const QueryShape c = query_shape(n, kCrossBlock, p.stack_depth);
+            hipLaunchKernelGGL(segment_crossing_kernel, c.groups, dim3(kCrossBlock), c.lds, st, p);
+        }
         return RT_OK;
     });
 }

@@ -793,6 +793,70 @@ int rt_section_offsets(RtScene *scene, const float *d_planes, int32_t n, int64_t
 int rt_list_sections(RtScene *scene, const float *d_planes, int32_t n, const int64_t *d_offsets, int32_t max_hits, const RtSectionList *out,
                      void *stream, int synchronize);
 
+/* ---- segment queries: the nearest point of the scene's triangles to each of the caller's SEGMENTS, and whether
+ *      a capsule (a segment with a radius) touches anything -- clearance and collision for characters, robot links, cables, tool
+ *      sweeps.  rt_closest_points' contract widened from a point to a segment: the result equals a brute-force loop over every
+ *      (instance, triangle) bit for bit, whatever the tree (host-built, device-built, refitted) and whatever the traversal order.
+ *      13. For query segment j with the world end points P0, P1 (fp32) and instance i; every operation fp32 in one fixed sequence, no
+ *          contraction:
+ *          1. Map: Q0 = apply_lre(pose_i, P0), Q1 = apply_lre(pose_i, P1), rule 1's map into scaled mesh space; D = Q1 - Q0 per
+ *             component.
+ *          2. Scene triangle: A, AB, AC of rule 2.  Its edges (E0, F) are, in this order, (A, AB), (A, AC), (A + AB, AC - AB): the
+ *             edges and the edge vectors of rule 2's nearest-edge fallback (A + AB and AC - AB are fp32 sums per component).
+ *          3. Five candidates (s, b1, b2) per triangle, in this order:
+ *             (a) the end Q0: (b1, b2) = rule 2's weights for the point Q0, s = 0;
+ *             (b) the end Q1: (b1, b2) = rule 2's weights for the point Q1, s = 1;
+ *             (c-e) the segment against each edge: the closest pair (s, u) of step 4, with (b1, b2) = (u, 0), (0, u), (1 - u, u).
+ *                   They are taken only when dot(D, D) > 0: a segment of zero length (or one whose squared length underflows) is a
+ *                   point, its candidates are the ends alone, and (a) is then rt_closest_points' answer bit for bit.
+ *             Every candidate has X = Q0 + s*D per component (the product rounded, then the sum), c = (A + b1*AB) + b2*AC (rule 2) and
+ *             d2 = (dx*dx + dy*dy) + dz*dz with d = X - c (rule 3).  The triangle's candidate is the one with the smallest d2, the
+ *             first of equals in the order above; a NaN d2 never wins over one that is not NaN.
+ *          4. Segment against segment (Ericson, Real-Time Collision Detection 5.1.9).  r = Q0 - E0, a = dot(D, D), e = dot(F, F),
+ *             f = dot(F, r), dot(x, y) = x.x*y.x + x.y*y.y + x.z*y.z summed left to right, clamp01(x) = x > 0 ? (x < 1 ? x : 1) : 0 (a
+ *             NaN gives 0).
+ *               Neither a > 0 nor e > 0: s = u = 0.
+ *               Not a > 0: s = 0, u = clamp01(f / e).
+ *               Otherwise c = dot(D, r).
+ *                 Not e > 0: u = 0, s = clamp01(-c / a).
+ *                 Otherwise b = dot(D, F), den = a*e - b*b, s = den > 0 ? clamp01((b*f - c*e) / den) : 0, u = (b*s + f) / e;
+ *                   if !(u >= 0): u = 0, s = clamp01(-c / a);  else if u > 1: u = 1, s = clamp01((b - c) / a).
+ *             So s and u lie in [0, 1] always.  (Step 3 never reaches the first two lines; they make the routine total.)
+ *          5. A triangle is a candidate of the query under rule 4 on its d2, with bound max_distance[j], the capsule's radius
+ *             (inclusive; d_max_distance NULL = +inf; a NaN or negative bound gives no candidate).  The winner is the candidate
+ *             with the smallest (d2, instance, triangle), rule 5's key.
+ *          6. PIERCING is not part of the minimum: a segment through the middle of a large triangle has all five candidates far away.
+ *             It is answered by rules 1-5 of rt_count_crossings for the ray o = P0, d = P1 - P0 (fp32 per component, world),
+ *             tmax = 1, unchanged:  crossings = that count;  clearance = crossings > 0 ? 0 : distance;  within = (a candidate
+ *             exists) || crossings > 0.  The point fields always describe the winner of step 5; a caller who wants the pierce points
+ *             calls rt_list_crossings.  Both halves are equal to brute force on their own.
+ *          7. NON-FINITE segments do not fault and do not change other queries' results; their own results are unspecified.
+ *      d_segments is a DEVICE array [n][2][3], P0 then P1 (a box array's shape); outputs are optional tight DEVICE arrays indexed like the
+ *      segments.  The distance half (every field but crossings) is one traversal; when within and / or pops are the only fields it
+ *      feeds, it ends at the first candidate, across instances too (pops is then at most the full traversal's).  The crossing half runs
+ *      only when crossings, clearance or within is wanted: rt_count_crossings' traversal on the same stream, patching the three in place
+ *      (for within alone, only on the segments that have no candidate).
+ *      Asynchronous on `stream` unless synchronize != 0; no workspace, no scene scratch, no host synchronisation (calls may overlap each
+ *      other and renders on other streams; a scene change on another stream is not ordered against them); nothing is launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL segments or no output at all with n > 0. ------------------------------------------- */
+typedef struct RtSegmentHits {  /* every pointer optional (NULL = not wanted), at least one given */
+    float   *distance;          /* [n] sqrtf(d2) of the winner; FLT_MAX on a miss                                            */
+    int32_t *instance;          /* [n] the winner's instance index, -1 on a miss                                             */
+    int32_t *triangle;          /* [n] the winner's triangle index as uploaded, -1 on a miss                                 */
+    float   *parameter;         /* [n] the winner's s in [0, 1]: where on the segment its nearest point lies; 0 on a miss    */
+    float   *segment_point;     /* [n][3] world position of X: apply_lre(inv_pose_i, X); 0 on a miss                         */
+    float   *point;             /* [n][3] world position of c: apply_lre(inv_pose_i, c); 0 on a miss                         */
+    float   *normal;            /* [n][3] world face normal, as rt_closest_points gives it; 0 on a miss                      */
+    float   *barycentric;       /* [n][2] (b1, b2): the weights of v1 and v2; 0 on a miss                                    */
+    float   *uv;                /* [n][2] texture uv, rt_closest_points' sequence; 0 on a miss                               */
+    int32_t *crossings;         /* [n] triangles the segment crosses (step 6)                                                */
+    float   *clearance;         /* [n] crossings > 0 ? 0 : distance                                                          */
+    int32_t *within;            /* [n] 1 when a triangle lies within max_distance of the segment or the segment crosses one, else 0 */
+    int32_t *pops;              /* [n] interior nodes visited by the distance half (a statistic, not part of the exact contract) */
+} RtSegmentHits;
+int rt_closest_to_segments(RtScene *scene, const float *d_segments, const float *d_max_distance, int32_t n, const RtSegmentHits *out,
+                           void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
