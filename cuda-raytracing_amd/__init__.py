@@ -69,6 +69,8 @@ _SECTION_COUNT_OUTPUTS = ("count", "any", "pops")
 _SECTION_LIST_OUTPUTS = ("instance", "triangle", "segment", "normal")
 _SEGMENT_OUTPUTS = ("distance", "instance", "triangle", "parameter", "segment_point", "point", "normal", "barycentric", "uv", "crossings",
                     "clearance", "within", "pops")
+_TRIANGLE_HIT_OUTPUTS = ("distance", "instance", "triangle", "query_barycentric", "query_point", "point", "normal", "barycentric", "uv",
+                         "intersections", "clearance", "within", "pops")
 
 
 class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers, any may be NULL)
@@ -119,6 +121,10 @@ class RtSegmentHits(C.Structure):           # include/rt_hip.h (device pointers,
     _fields_ = [(n, _vp) for n in _SEGMENT_OUTPUTS]
 
 
+class RtTriangleHits(C.Structure):          # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in _TRIANGLE_HIT_OUTPUTS]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [("num_meshes", C.c_int32), ("meshes", C.POINTER(RtMeshDesc)), ("num_materials", C.c_int32),
                 ("materials", C.POINTER(RtMaterialDesc)), ("num_instances", C.c_int32), ("instances", C.POINTER(RtInstanceDesc))]
@@ -138,7 +144,7 @@ RT_HIP_SYMBOLS = [
     "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting",
     "rt_count_in_boxes", "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "rt_occupancy_grid",
     "rt_count_sections", "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections",
-    "rt_closest_to_segments"]
+    "rt_closest_to_segments", "rt_closest_to_triangles"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -297,6 +303,7 @@ def _declare(h, s):
     h.rt_section_offsets.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_sections.argtypes = [_vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtSectionList), _vp, C.c_int]
     h.rt_closest_to_segments.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtSegmentHits), _vp, C.c_int]
+    h.rt_closest_to_triangles.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(RtTriangleHits), _vp, C.c_int]
     h.rt_occupancy_grid.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
     h.rt_timer_create.argtypes = [C.POINTER(_vp)]
@@ -832,6 +839,33 @@ class Scene:
             check(h.rt_closest_to_segments(handle, ins[0], ins[1], n, C.byref(hits), st, sync), "rt_closest_to_segments")
         return _device_query(self, [("segments", segments), ("max_distance", max_distance)], outputs, call, stream, **_SEGMENT_INPUTS)
 
+    TRIANGLE_HIT_OUTPUTS = _TRIANGLE_HIT_OUTPUTS                        # the fields of RtTriangleHits
+
+    def closest_to_triangles(self, triangles, max_distance=None, skip_instance=None, outputs=("distance", "instance", "triangle"),
+                             stream=None):
+        """The nearest point of the scene's triangles to each of the caller's triangles, and whether it lies within a clearance
+        (rt_closest_to_triangles; the rule, bit for bit a brute-force loop over every instance and triangle, is rule 14 of
+        include/rt_hip.h): dict of the wanted TRIANGLE_HIT_OUTPUTS of the triangles' leading shape -- distance (float32, FLT_MAX on a
+        miss), instance / triangle (int32, -1 on a miss), query_barycentric ([2] float32: the weights of the query's second and third
+        vertex at its nearest point), query_point / point ([3] float32, world: the nearest pair, on the query triangle and on the
+        scene triangle), normal ([3]), barycentric / uv ([2]) as closest_points gives them, intersections (int32, scene triangles the
+        query triangle intersects: count_intersecting's count), clearance (float32, 0 where intersections > 0, else distance), within
+        (int32 0 / 1: a triangle within max_distance of the query, or intersected by it; wanted alone or with pops, the distance
+        traversal stops at the first triangle in reach), pops (int32, interior nodes visited by the distance traversal).  The point
+        fields describe the nearest triangle even where the query intersects another.  triangles: float32 [..., 3, 3] world vertices,
+        contiguous.  max_distance: None (+inf) or float32 of the leading shape (inclusive; NaN or negative = nothing in reach).
+        skip_instance: None or int32 of the leading shape, one instance per triangle that contributes to nothing (-1 = none): an
+        instance's own triangles with its index ask how close it is to everything else.  A large triangle prunes little: subdivide it
+        first.  torch tensors: asynchronous on `stream` (default the current stream); numpy arrays: copied to the device and back, the
+        call synchronises."""
+        outputs = _check_outputs(outputs, self.TRIANGLE_HIT_OUTPUTS)
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            hits = RtTriangleHits(*[ptr.get(k) for k in _TRIANGLE_HIT_OUTPUTS])
+            check(h.rt_closest_to_triangles(handle, ins[0], ins[1], ins[2], n, C.byref(hits), st, sync), "rt_closest_to_triangles")
+        return _device_query(self, [("triangles", triangles), ("max_distance", max_distance), ("skip_instance", skip_instance)], outputs,
+                             call, stream, **_TRIANGLE_INPUTS)
+
     def occupancy_grid(self, origin, spacing, dims, outputs=("occupied",), stream=None, as_numpy=False):
         """count_in_boxes on the cells of a regular grid, which the kernel makes itself (rt_occupancy_grid): cell (ix, iy, iz) is the
         box from origin + i*spacing to origin + (i + 1)*spacing per axis in float32, so neighbouring cells share their faces exactly.
@@ -1141,7 +1175,8 @@ _FIELDS = dict(
     count=((), np.int32), winding=((), np.int32), pops=((), np.int32), sign=((), np.int8), occluded=((), np.uint8),
     any=((), np.bool_), occupied=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
     point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32), parameter=((), np.float32),
-    segment_point=((3,), np.float32), crossings=((), np.int32), clearance=((), np.float32), within=((), np.int32))
+    segment_point=((3,), np.float32), crossings=((), np.int32), clearance=((), np.float32), within=((), np.int32),
+    query_barycentric=((2,), np.float32), query_point=((3,), np.float32), intersections=((), np.int32))
 
 
 def _check_outputs(outputs, allowed, extras=()):

@@ -26,6 +26,7 @@ struct RtBoxList;
 struct RtSectionCounts;
 struct RtSectionList;
 struct RtSegmentHits;
+struct RtTriangleHits;
 
 class Scene {
 public:
@@ -118,6 +119,11 @@ public:
     // ([n][2][3] world, P0 then P1), radii (optional, NULL = +inf) and outputs are DEVICE arrays.  Returns the status.
     int closest_to_segments(const float* d_segments, const float* d_max_distance, int32_t n, const RtSegmentHits& out,
                             void* stream = nullptr, bool synchronize = false);
+    // Triangle distance queries on the device scene: rt_closest_to_triangles of include/rt_hip.h (rule 14), where the semantics are.
+    // Triangles ([n][3][3] world), radii and skipped instances (both optional, NULL = +inf / none) and outputs are DEVICE arrays.
+    // Returns the status.
+    int closest_to_triangles(const float* d_triangles, const float* d_max_distance, const int32_t* d_skip_instance, int32_t n,
+                             const RtTriangleHits& out, void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

@@ -756,6 +756,14 @@ int Scene::closest_to_segments(const float* d_segments, const float* d_max_dista
     return last_error;
 }
 
+int Scene::closest_to_triangles(const float* d_triangles, const float* d_max_distance, const int32_t* d_skip_instance, int32_t n,
+                                const RtTriangleHits& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_closest_to_triangles(d_scene, d_triangles, d_max_distance, d_skip_instance, n, &out, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

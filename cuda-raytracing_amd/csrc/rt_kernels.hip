@@ -2767,6 +2767,215 @@ __global__ __launch_bounds__(kPointBlock, 8) void segment_closest_kernel(const S
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Triangle distance queries (rt_closest_to_triangles): the nearest point of the scene's triangles to each of the caller's triangles,
+// equal bit for bit to a brute-force minimum over every (instance, triangle) -- rule 14 of include/rt_hip.h, the pruning argument in
+// DESIGN.md section 19.  segment_closest_kernel's shape: one wave per workgroup, one query triangle per lane, the nearest-first
+// traversal, the lower bound between the query's widened box and the child's.  The leaf is heavy (fifteen candidates: six
+// pq_weights, nine sq_segseg), so all of it is one out-of-line routine that maps the query's vertices itself: the node loop holds
+// the query's box and nothing else of the query.  The intersection half (step 5) is triangle_intersect_patch_kernel, after ti_trace.
+// ---------------------------------------------------------------------------------------------------------
+struct TdParams {
+    const float4* records;
+    const float* tri_uv;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* tris;          // [n][3][3] world query triangles
+    const float* max_distance;  // [n] or null (= +inf)
+    const int32_t* skip;        // [n] or null: one instance per query that contributes nothing (-1 = none)
+    int32_t n;
+    float* distance;            // outputs, each optional (null = not wanted)
+    int32_t *instance, *triangle;
+    float *query_barycentric, *query_point, *point, *normal, *barycentric, *uv;
+    float* clearance;           // the distance here, set to 0 by triangle_intersect_patch_kernel where the triangle intersects
+    int32_t* within;            // 1 where there is a candidate here, set to 1 by triangle_intersect_patch_kernel where it intersects
+    int32_t* pops;
+};
+
+// query vertex k of triangle P (world, [3][3]) in instance in's scaled mesh space: apply_lre(pose, P_k), rule 1's map
+__device__ __forceinline__ V3 td_vertex(const float* P, const DevInstance& in, int k)
+{
+    return apply_quat(in.q_pose, v3(P[3 * k] - in.pose_xyz[0], P[3 * k + 1] - in.pose_xyz[1], P[3 * k + 2] - in.pose_xyz[2]));
+}
+
+// One candidate (q1, q2, b1, b2) of a pair against the pair's best so far: the smaller d2, the earlier of equals; a NaN d2 never
+// replaces one that is not NaN
+struct TdCand { float q1, q2, b1, b2, d2; };
+__device__ __forceinline__ void td_candidate(TdCand& best, V3 q0, V3 qab, V3 qac, V3 a, V3 ab, V3 ac, float q1, float q2, float b1,
+                                             float b2)
+{
+    const float d2 = pq_d2(pq_combine(q0, qab, qac, q1, q2) - pq_combine(a, ab, ac, b1, b2));
+    if (d2 < best.d2 || best.d2 != best.d2) { best.q1 = q1; best.q2 = q2; best.b1 = b1; best.b2 = b2; best.d2 = d2; }
+}
+
+// rule 14 steps 1-3 on one scene triangle: the query's vertices mapped again (the same sequence as the traversal's box), then the
+// fifteen candidates in order.  Out of line and not unrolled -- one pq_weights and one call of sq_segseg in the code, whichever
+// triangle is projected onto and whichever edges meet -- so none of it occupies the traversal's registers.
+__device__ __noinline__ TdCand td_triangle(const float* P, const DevInstance& in, V3 a, V3 ab, V3 ac)
+{
+    const V3 q0 = td_vertex(P, in, 0);
+    const V3 qab = td_vertex(P, in, 1) - q0, qac = td_vertex(P, in, 2) - q0;
+    TdCand best;
+    best.q1 = 0.0f; best.q2 = 0.0f; best.b1 = 0.0f; best.b2 = 0.0f; best.d2 = __int_as_float(0x7fc00000);
+    // (a) 0-2: the query's vertices onto the scene triangle; (b) 3-5: the scene's vertices onto the query triangle, unless the query
+    // is a point (then (a) alone: closest_point_kernel's answer)
+    const bool spread = dot(qab, qab) > 0.0f || dot(qac, qac) > 0.0f;
+#pragma unroll 1
+    for (int k = 0; k < (spread ? 6 : 3); k++) {
+        const bool onto_query = k >= 3;
+        const int j = onto_query ? k - 3 : k;
+        const V3 f0 = onto_query ? a : q0, f1 = onto_query ? ab : qab, f2 = onto_query ? ac : qac;       // the vertex comes from here
+        const V3 t0 = onto_query ? q0 : a, t1 = onto_query ? qab : ab, t2 = onto_query ? qac : ac;       // and is projected onto this
+        const V3 v = j == 0 ? f0 : (j == 1 ? f0 + f1 : f0 + f2);
+        const float2 w = pq_weights(v, t0, t1, t2);
+        const float u1 = j == 1 ? 1.0f : 0.0f, u2 = j == 2 ? 1.0f : 0.0f;
+        if (onto_query) td_candidate(best, q0, qab, qac, a, ab, ac, w.x, w.y, u1, u2);
+        else td_candidate(best, q0, qab, qac, a, ab, ac, u1, u2, w.x, w.y);
+    }
+    // (c) 6-14: query edge m against scene edge k, rule 13's closest pair
+#pragma unroll 1
+    for (int m = 0; m < 3; m++) {
+        const V3 g0 = m == 2 ? q0 + qab : q0, d = m == 0 ? qab : (m == 1 ? qac : qac - qab);
+        if (!(dot(d, d) > 0.0f)) continue;
+#pragma unroll 1
+        for (int k = 0; k < 3; k++) {
+            const V3 e0 = k == 2 ? a + ab : a, f = k == 0 ? ab : (k == 1 ? ac : ac - ab);
+            const float2 su = sq_segseg(g0, d, e0, f);
+            const float s = su.x, u = su.y;
+            td_candidate(best, q0, qab, qac, a, ab, ac, m == 0 ? s : (m == 1 ? 0.0f : 1.0f - s), m == 0 ? 0.0f : s,
+                         k == 0 ? u : (k == 1 ? 0.0f : 1.0f - u), k == 0 ? 0.0f : u);
+        }
+    }
+    return best;
+}
+
+// the query's interval on one axis over its three mapped vertices, widened by 2^-16 of their largest magnitude plus FLT_MIN: every
+// computed X of rule 14 lies in it
+__device__ __forceinline__ void td_interval(float a, float b, float c, float& lo, float& hi)
+{
+    const float m = fmaxf(fmaxf(fabsf(a), fabsf(b)), fabsf(c)) * 0x1p-16f + 0x1p-126f;
+    lo = fminf(fminf(a, b), c) - m; hi = fmaxf(fmaxf(a, b), c) + m;
+}
+
+// ANY: only within and / or pops are wanted of this half: the traversal ends at the first candidate, across instances too
+template <bool ANY>
+__global__ __launch_bounds__(kPointBlock, 8) void triangle_closest_kernel(const TdParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kPointBlock]
+    const int32_t i = (int32_t)blockIdx.x * kPointBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const size_t i3 = (size_t)i * 3;
+    const float* P = p.tris + (size_t)i * 9;
+    const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
+    const int32_t skip = p.skip ? p.skip[i] : -1;
+    int spill[kMaxStack - kLdsStack];
+    PointStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    // the best candidate so far by (d2, instance, tri_id); best_inst < 0 = none yet
+    float best = 0.0f, bq1 = 0.0f, bq2 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+    int32_t best_inst = -1, best_slot = 0, best_tid = 0, pops = 0;
+    for (int32_t k = 0; k < p.num_instances && cut2 >= 0.0f && !(ANY && best_inst >= 0); k++) {
+        if (k == skip) continue;
+        const DevInstance& in = p.instances[k];
+        V3 slo, shi;
+        {                                                       // (the mapped vertices live only here: the leaf maps them again)
+            const V3 q0 = td_vertex(P, in, 0), q1 = td_vertex(P, in, 1), q2 = td_vertex(P, in, 2);
+            td_interval(q0.x, q1.x, q2.x, slo.x, shi.x); td_interval(q0.y, q1.y, q2.y, slo.y, shi.y);
+            td_interval(q0.z, q1.z, q2.z, slo.z, shi.z);
+        }
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: both child boxes, nearer first
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const float la = sq_box_lb(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, slo, shi);
+                const float lb = sq_box_lb(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, slo, shi);
+                const float lim = best_inst >= 0 ? best : cut2;
+                const bool pa = !(prune && la > lim), pb = !(prune && lb > lim);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                const bool a_near = !(lb < la);
+                if (pa && pb) stack.push(a_near ? rb : ra);
+                cur = (pa && pb) ? (a_near ? ra : rb) : (pa ? ra : (pb ? rb : kNeedPop));
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    const float4 t0 = rec[0], t1 = rec[1], t2 = rec[2];
+                    V3 a, ab, ac;
+                    pq_triangle(t0, t1, t2, s, a, ab, ac);
+                    const TdCand c = td_triangle(P, in, a, ab, ac);
+                    if (c.d2 <= (best_inst >= 0 ? best : cut2)) {   // (NaN fails)
+                        const int32_t tid = p.tri_id[slot];
+                        if (best_inst < 0 || c.d2 < best || (best_inst == k && tid < best_tid)) {
+                            best = c.d2; bq1 = c.q1; bq2 = c.q2; b1 = c.b1; b2 = c.b2; best_inst = k; best_slot = slot; best_tid = tid;
+                        }
+                    }
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel && !(ANY && best_inst >= 0));
+    }
+    const bool got = best_inst >= 0;
+    if (p.pops) p.pops[i] = pops;
+    if (p.within) p.within[i] = got ? 1 : 0;
+    if constexpr (ANY) return;
+    const float dist = got ? sqrtf(best) : FLT_MAX;
+    if (p.distance) p.distance[i] = dist;
+    if (p.clearance) p.clearance[i] = dist;
+    if (p.instance) p.instance[i] = got ? best_inst : -1;
+    if (p.triangle) p.triangle[i] = got ? best_tid : -1;
+    if (p.query_barycentric) { p.query_barycentric[(size_t)i * 2] = got ? bq1 : 0.0f; p.query_barycentric[(size_t)i * 2 + 1] = got ? bq2 : 0.0f; }
+    if (p.barycentric) { p.barycentric[(size_t)i * 2] = got ? b1 : 0.0f; p.barycentric[(size_t)i * 2 + 1] = got ? b2 : 0.0f; }
+    if (!got) {
+        if (p.query_point) { p.query_point[i3] = 0.0f; p.query_point[i3 + 1] = 0.0f; p.query_point[i3 + 2] = 0.0f; }
+        if (p.point) { p.point[i3] = 0.0f; p.point[i3 + 1] = 0.0f; p.point[i3 + 2] = 0.0f; }
+        if (p.normal) { p.normal[i3] = 0.0f; p.normal[i3 + 1] = 0.0f; p.normal[i3 + 2] = 0.0f; }
+        if (p.uv) { p.uv[(size_t)i * 2] = 0.0f; p.uv[(size_t)i * 2 + 1] = 0.0f; }
+        return;
+    }
+    const DevInstance& in = p.instances[best_inst];
+    if (p.query_point) {                                        // the winner's X again (same sequence), to world: apply_lre(inv_pose, X)
+        const V3 q0 = td_vertex(P, in, 0);
+        const V3 x = pq_combine(q0, td_vertex(P, in, 1) - q0, td_vertex(P, in, 2) - q0, bq1, bq2);
+        const V3 o = apply_quat(in.q_inv_pose, v3(x.x - in.inv_pose_xyz[0], x.y - in.inv_pose_xyz[1], x.z - in.inv_pose_xyz[2]));
+        p.query_point[i3] = o.x; p.query_point[i3 + 1] = o.y; p.query_point[i3 + 2] = o.z;
+    }
+    if (p.point) {                                              // the winner's c again (same sequence), closest_point_kernel's map
+        const float4* rec = p.records + (size_t)best_slot * 4;
+        V3 a, ab, ac;
+        pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+        const V3 c = pq_combine(a, ab, ac, b1, b2);
+        const V3 o = apply_quat(in.q_inv_pose, v3(c.x - in.inv_pose_xyz[0], c.y - in.inv_pose_xyz[1], c.z - in.inv_pose_xyz[2]));
+        p.point[i3] = o.x; p.point[i3 + 1] = o.y; p.point[i3 + 2] = o.z;
+    }
+    if (p.normal) {
+        const V3 n = pq_normal(p, in, best_slot);
+        p.normal[i3] = n.x; p.normal[i3 + 1] = n.y; p.normal[i3 + 2] = n.z;
+    }
+    if (p.uv) {                                                 // w = (1 - b2) - b1, uv = (w uv0 + b1 uv1) + b2 uv2 (closest_point_kernel's)
+        const float* t = p.tri_uv + (size_t)best_slot * 6;
+        const float u0 = (1.0f - b2) - b1;
+        p.uv[(size_t)i * 2] = (u0 * t[0] + b1 * t[2]) + b2 * t[4];
+        p.uv[(size_t)i * 2 + 1] = (u0 * t[1] + b1 * t[3]) + b2 * t[5];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Ray crossing counts and winding numbers (rt_count_crossings / rt_winding_numbers / rt_signed_distance): every triangle a ray
 // crosses within (0, tmax], both faces, with the sign of the crossing -- equal to a brute-force count over every (instance,
 // triangle); the rule is in include/rt_hip.h, the pruning argument in DESIGN.md section 12.  One wave per workgroup, one ray (or
@@ -3653,6 +3862,33 @@ __global__ __launch_bounds__(kTriBlock, 8) void intersect_count_kernel(const Tri
     if (p.count) p.count[i] = total;
     if (p.any) p.any[i] = total > 0 ? 1 : 0;
     if (p.pops) p.pops[i] = pops;
+}
+
+// The intersection half of rt_closest_to_triangles (rule 14 step 5): rule 10's pairs of the same triangles with the same skip, one
+// query per lane, patching what triangle_closest_kernel wrote on the same stream -- clearance becomes 0 and within 1 where the
+// triangle intersects the scene (as segment_crossing_kernel patches its three).  COUNT (intersections wanted): every pair is
+// counted; otherwise the traversal ends at the first pair, and a lane whose answer cannot change any more does not traverse.
+template <bool COUNT>
+__global__ __launch_bounds__(kTriBlock, 8) void triangle_intersect_patch_kernel(const TriParams p, int32_t* intersections, float* clearance,
+                                                                                int32_t* within)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    if (!COUNT && !clearance && within[i] != 0) return;         // (within alone, and the distance half has already said 1)
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    int32_t total = 0;
+    ti_trace(p, stack, i, false, [&](int32_t) { return true; }, [&](int32_t, int32_t, const TiHit&) {
+        total++;
+        return !COUNT;
+    });
+    if (COUNT) intersections[i] = total;
+    if (total > 0) {
+        if (clearance) clearance[i] = 0.0f;
+        if (within) within[i] = 1;
+    }
 }
 
 // slot j (absolute) of a room <- the pair (instance k, record slot, triangle tid) with the segment ends h (mesh space)
@@ -6173,6 +6409,44 @@ int rt_list_intersecting(RtScene* s, const float* d_triangles, const int32_t* d_
         p.count = out->count; p.pops = out->pops;
         const QueryShape k = query_shape(n, kTriBlock, p.stack_depth);
         hipLaunchKernelGGL(intersect_list_kernel, k.groups, dim3(kTriBlock), k.lds, st, p);
+        return RT_OK;
+    });
+}
+
+// ---- triangle distance queries (here for intersect_params: the intersection half is the family above) -----------------------
+int rt_closest_to_triangles(RtScene* s, const float* d_triangles, const float* d_max_distance, const int32_t* d_skip_instance, int32_t n,
+                            const RtTriangleHits* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_triangles || !out))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    // what only a full distance traversal gives; what the distance half feeds at all; what the intersection half feeds
+    const bool full = out->distance || out->instance || out->triangle || out->query_barycentric || out->query_point || out->point ||
+                      out->normal || out->barycentric || out->uv || out->clearance;
+    const bool near = full || out->within || out->pops, meet = out->intersections || out->clearance || out->within;
+    if (!near && !meet) return RT_E_INVALID;
+    // (both launches under one hold of the scene's lock: no other thread's update comes between the distance and the intersections)
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        if (near) {
+            TdParams p = scene_params<TdParams>(s);
+            p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
+            p.tris = d_triangles; p.max_distance = d_max_distance; p.skip = d_skip_instance; p.n = n;
+            p.distance = out->distance; p.instance = out->instance; p.triangle = out->triangle;
+            p.query_barycentric = out->query_barycentric; p.query_point = out->query_point; p.point = out->point; p.normal = out->normal;
+            p.barycentric = out->barycentric; p.uv = out->uv; p.clearance = out->clearance; p.within = out->within; p.pops = out->pops;
+            const QueryShape k = query_shape(n, kPointBlock, p.stack_depth);
+            if (full) hipLaunchKernelGGL(triangle_closest_kernel<false>, k.groups, dim3(kPointBlock), k.lds, st, p);
+            else hipLaunchKernelGGL(triangle_closest_kernel<true>, k.groups, dim3(kPointBlock), k.lds, st, p);
+        }
+        if (meet) {
+            const TriParams t = intersect_params(s, d_triangles, d_skip_instance, n);
+            const QueryShape k = query_shape(n, kTriBlock, t.stack_depth);
+            if (out->intersections)
+                hipLaunchKernelGGL(triangle_intersect_patch_kernel<true>, k.groups, dim3(kTriBlock), k.lds, st, t, out->intersections,
+                                   out->clearance, out->within);
+            else
+                hipLaunchKernelGGL(triangle_intersect_patch_kernel<false>, k.groups, dim3(kTriBlock), k.lds, st, t, (int32_t*)nullptr,
+                                   out->clearance, out->within);
+        }
         return RT_OK;
     });
 }

@@ -857,6 +857,76 @@ typedef struct RtSegmentHits {  /* every pointer optional (NULL = not wanted), a
 int rt_closest_to_segments(RtScene *scene, const float *d_segments, const float *d_max_distance, int32_t n, const RtSegmentHits *out,
                            void *stream, int synchronize);
 
+/* ---- triangle distance queries: the nearest point of the scene's triangles to each of the caller's TRIANGLES,
+ *      and whether it lies within a clearance -- is this tool, link or part within 2 mm of anything, and where.  rt_closest_to_segments'
+ *      contract widened from a segment to a triangle: the result equals a brute-force loop over every (instance, triangle) bit for bit,
+ *      whatever the tree (host-built, device-built, refitted) and whatever the traversal order.
+ *      14. For query triangle j with the world vertices P0, P1, P2 (fp32) and instance i; every operation fp32 in one fixed sequence, no
+ *          contraction:
+ *          1. Map: Qk = apply_lre(pose_i, Pk), rule 1's map into scaled mesh space; QAB = Q1 - Q0, QAC = Q2 - Q0 per component.  From
+ *             here on the query triangle is (Q0, QAB, QAC), the form a scene triangle has.  A point of it is X = (Q0 + q1*QAB) + q2*QAC
+ *             per component (rule 2's combination, each product rounded, then each sum).  Its vertices AS COMPUTED are V0 = Q0,
+ *             V1 = Q0 + QAB, V2 = Q0 + QAC (fp32 sums; V1 may differ from Q1 in the last bit).  Its edges (G0, D) are, in this order,
+ *             (Q0, QAB), (Q0, QAC), (V1, QAC - QAB).
+ *          2. Scene triangle: A, AB, AC of rule 2.  Its vertices are W0 = A, W1 = A + AB, W2 = A + AC (fp32 sums); its edges (E0, F)
+ *             are rule 13's in rule 13's order: (A, AB), (A, AC), (A + AB, AC - AB).
+ *          3. Fifteen candidates (q1, q2, b1, b2) per pair, in this order:
+ *             (a) 0-2: each query vertex against the scene triangle: (b1, b2) = rule 2's weights for the point Vk on (A, AB, AC);
+ *                 (q1, q2) = (0, 0), (1, 0), (0, 1).  The point that is projected is the point that is priced: Vk, not Qk.
+ *             (b) 3-5: each scene vertex against the query triangle: (q1, q2) = rule 2's weights for the point Wk on (Q0, QAB, QAC);
+ *                 (b1, b2) = (0, 0), (1, 0), (0, 1).  Taken only when dot(QAB, QAB) > 0 || dot(QAC, QAC) > 0.
+ *             (c) 6-14: query edge m (outer loop) against scene edge k (inner loop): (s, u) = rule 13 step 4's closest pair of
+ *                 (G0_m, D_m) and (E0_k, F_k), unchanged;  (q1, q2) = (s, 0), (0, s), (1 - s, s) for m = 0, 1, 2;  (b1, b2) = (u, 0),
+ *                 (0, u), (1 - u, u) for k = 0, 1, 2.  Edge m is taken only when dot(D_m, D_m) > 0.
+ *             Every candidate is priced the same way: X as in step 1, c = (A + b1*AB) + b2*AC (rule 2), d2 = (dx*dx + dy*dy) + dz*dz with
+ *             d = X - c (rule 3).  The pair's candidate is the one with the smallest d2, the first of equals in the order above; a NaN
+ *             d2 never replaces one that is not NaN.
+ *             The guards give one property bit for bit: a query triangle whose three vertices are equal is a point (QAB = QAC = 0),
+ *             its candidates are (a) alone, V0 = V1 = V2, candidate 0 wins every tie, and the answer is rt_closest_points' answer in
+ *             every field the two share.  No bit equality with rt_closest_to_segments is promised for a triangle that degenerates to a
+ *             segment (two equal vertices, or three on a line): its third edge runs the segment in reverse and its (b) candidates
+ *             project onto a degenerate triangle, and either may undercut rule 13's five in the last bits.
+ *          4. A pair is a candidate of the query under rule 4 on its d2, with bound max_distance[j] (inclusive; d_max_distance NULL =
+ *             +inf; a NaN or negative bound gives no candidate).  The winner is the candidate with the smallest (d2, instance,
+ *             triangle), rule 5's key.
+ *          5. INTERSECTION is not part of the minimum: two triangles that cross have fifteen small but non-zero candidates (each is a
+ *             rounded closest pair of a vertex and a face or of two edges; the distance is 0 between an edge and a face's interior).
+ *             That half is rule 10 of rt_count_intersecting on the same triangles, unchanged:  intersections = that count;
+ *             clearance = intersections > 0 ? 0 : distance;  within = (a candidate exists) || intersections > 0.  The point fields
+ *             always describe the winner of step 4; a caller who wants the contact segments calls rt_list_intersecting.  Both
+ *             halves are equal to brute force on their own.  COPLANAR OVERLAP, which rule 10 does not report reliably (a segment in
+ *             a triangle's plane counts nothing), reaches distance 0 through the edge and vertex candidates of step 3 instead: an
+ *             edge crossing an edge or a vertex on a face has d2 = 0 wherever the arithmetic is exact, and a few ulps otherwise.
+ *          6. d_skip_instance: optional int32 [n], -1 = none, as in rule 10: that instance contributes to neither half.  An instance's
+ *             own world triangles with skip_instance = k ask how close instance k is to everything else.
+ *          7. NON-FINITE triangles do not fault and do not change other queries' results; their own results are unspecified.
+ *      d_triangles is a DEVICE array [n][3][3]; outputs are optional tight DEVICE arrays indexed like the triangles.  The distance half
+ *      (every field but intersections) is one traversal; when within and / or pops are the only fields it feeds, it ends at the first
+ *      candidate, across instances too (pops is then at most the full traversal's).  The intersection half runs only when
+ *      intersections, clearance or within is wanted: rt_count_intersecting's traversal on the same stream, patching the three in place
+ *      (counting every pair when intersections is wanted, else ending at the first; for within alone, only on the triangles that have
+ *      no candidate).  A large query triangle prunes little (the bound is a box against a box): subdivide it on the host.
+ *      Asynchronous on `stream` unless synchronize != 0; no workspace, no scene scratch, no host synchronisation (calls may overlap each
+ *      other and renders on other streams; a scene change on another stream is not ordered against them); nothing is launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL triangles or no output at all with n > 0. ------------------------------------------ */
+typedef struct RtTriangleHits { /* every pointer optional (NULL = not wanted), at least one given */
+    float   *distance;          /* [n] sqrtf(d2) of the winner; FLT_MAX on a miss                                            */
+    int32_t *instance;          /* [n] the winner's instance index, -1 on a miss                                             */
+    int32_t *triangle;          /* [n] the winner's triangle index as uploaded, -1 on a miss                                 */
+    float   *query_barycentric; /* [n][2] (q1, q2): the weights of P1 and P2 at the query triangle's nearest point; 0 on a miss */
+    float   *query_point;       /* [n][3] world position of X: apply_lre(inv_pose_i, X); 0 on a miss                         */
+    float   *point;             /* [n][3] world position of c: apply_lre(inv_pose_i, c); 0 on a miss                         */
+    float   *normal;            /* [n][3] world face normal of the scene triangle, as rt_closest_points gives it; 0 on a miss */
+    float   *barycentric;       /* [n][2] (b1, b2): the weights of v1 and v2; 0 on a miss                                    */
+    float   *uv;                /* [n][2] texture uv, rt_closest_points' sequence; 0 on a miss                               */
+    int32_t *intersections;     /* [n] scene triangles the query triangle intersects (step 5: rt_count_intersecting's count) */
+    float   *clearance;         /* [n] intersections > 0 ? 0 : distance                                                      */
+    int32_t *within;            /* [n] 1 when a triangle lies within max_distance of the query or the query intersects one, else 0 */
+    int32_t *pops;              /* [n] interior nodes visited by the distance half (a statistic, not part of the exact contract) */
+} RtTriangleHits;
+int rt_closest_to_triangles(RtScene *scene, const float *d_triangles, const float *d_max_distance, const int32_t *d_skip_instance,
+                            int32_t n, const RtTriangleHits *out, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
