@@ -67,6 +67,8 @@ _BOX_COUNT_OUTPUTS = ("count", "any", "pops")
 _BOX_LIST_OUTPUTS = ("instance", "triangle")
 _SECTION_COUNT_OUTPUTS = ("count", "any", "pops")
 _SECTION_LIST_OUTPUTS = ("instance", "triangle", "segment", "normal")
+_REGION_COUNT_OUTPUTS = ("count", "inside", "any", "pops")
+_REGION_LIST_OUTPUTS = ("instance", "triangle", "inside", "normal")
 _SEGMENT_OUTPUTS = ("distance", "instance", "triangle", "parameter", "segment_point", "point", "normal", "barycentric", "uv", "crossings",
                     "clearance", "within", "pops")
 _TRIANGLE_HIT_OUTPUTS = ("distance", "instance", "triangle", "query_barycentric", "query_point", "point", "normal", "barycentric", "uv",
@@ -117,6 +119,14 @@ class RtSectionList(C.Structure):           # include/rt_hip.h (device pointers;
     _fields_ = [(n, _vp) for n in _SECTION_LIST_OUTPUTS + ("count", "pops")]
 
 
+class RtRegionCounts(C.Structure):          # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in _REGION_COUNT_OUTPUTS]
+
+
+class RtRegionList(C.Structure):            # include/rt_hip.h (device pointers; instance, triangle required)
+    _fields_ = [(n, _vp) for n in _REGION_LIST_OUTPUTS + ("count", "pops")]
+
+
 class RtSegmentHits(C.Structure):           # include/rt_hip.h (device pointers, any may be NULL, at least one given)
     _fields_ = [(n, _vp) for n in _SEGMENT_OUTPUTS]
 
@@ -144,7 +154,8 @@ RT_HIP_SYMBOLS = [
     "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting",
     "rt_count_in_boxes", "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "rt_occupancy_grid",
     "rt_count_sections", "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections",
-    "rt_closest_to_segments", "rt_closest_to_triangles"]
+    "rt_closest_to_segments", "rt_closest_to_triangles",
+    "rt_count_in_regions", "rt_region_offsets_workspace_bytes", "rt_region_offsets", "rt_list_in_regions"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
@@ -302,6 +313,11 @@ def _declare(h, s):
     h.rt_section_offsets_workspace_bytes.argtypes = [C.c_int32]
     h.rt_section_offsets.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_sections.argtypes = [_vp, _vp, C.c_int32, _vp, C.c_int32, C.POINTER(RtSectionList), _vp, C.c_int]
+    h.rt_count_in_regions.argtypes = [_vp, _vp, C.c_int32, C.c_int32, C.POINTER(RtRegionCounts), _vp, C.c_int]
+    h.rt_region_offsets_workspace_bytes.restype = C.c_size_t
+    h.rt_region_offsets_workspace_bytes.argtypes = [C.c_int32]
+    h.rt_region_offsets.argtypes = [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_list_in_regions.argtypes = [_vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.POINTER(RtRegionList), _vp, C.c_int]
     h.rt_closest_to_segments.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtSegmentHits), _vp, C.c_int]
     h.rt_closest_to_triangles.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(RtTriangleHits), _vp, C.c_int]
     h.rt_occupancy_grid.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_int]
@@ -814,6 +830,45 @@ class Scene:
         outputs = _check_outputs(outputs, self.SECTION_LIST_OUTPUTS, extras=("count", "pops"))
         return _list_query(self, _SECTION_LIST, [("planes", planes)], _check_max_hits(max_hits), outputs, stream)
 
+    REGION_COUNT_OUTPUTS = _REGION_COUNT_OUTPUTS                        # the fields of RtRegionCounts
+
+    def count_in_regions(self, regions, outputs=("count",), stream=None):
+        """How many scene triangles lie in or touch each of the caller's convex regions (rt_count_in_regions; the rule, equal to a
+        brute-force loop over every instance and triangle, is rule 15 of include/rt_hip.h: rule 12's half-open classes on each of
+        the K planes, then the triangle clipped by the planes in order): dict of the wanted REGION_COUNT_OUTPUTS of the regions'
+        leading shape -- count (int32, the number of (instance, triangle) pairs), inside (int32, how many of them lie wholly
+        inside), any (bool; wanted without count and inside, the traversal stops at the first pair), pops (int32, interior nodes
+        visited).  regions: float32 [..., K, 2, 3] world, contiguous, 1 <= K <= REGION_MAX_PLANES read from the shape: per plane a
+        point of it, then its normal pointing INTO the region (any length; a zero normal anywhere leaves the region without
+        pairs).  The test is closed (touching counts) and decided in fp32 relative to each plane's point, so put the point on the
+        region's face.  regions_from_boxes / regions_from_obbs / regions_from_frusta make common shapes.  torch tensors:
+        asynchronous on `stream` (default the current stream); numpy arrays: copied to the device and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.REGION_COUNT_OUTPUTS)
+        K = _region_planes(regions)
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            c = RtRegionCounts(*[ptr.get(k) for k in _REGION_COUNT_OUTPUTS])
+            check(h.rt_count_in_regions(handle, ins[0], n, K, C.byref(c), st, sync), "rt_count_in_regions")
+        return _device_query(self, [("regions", regions)], outputs, call, stream, shape=(K, 2, 3))
+
+    REGION_LIST_OUTPUTS = _REGION_LIST_OUTPUTS                          # the slot fields of RtRegionList
+
+    def list_in_regions(self, regions, max_hits=None, outputs=("instance", "triangle", "inside"), stream=None):
+        """Every scene triangle that lies in or touches each of the caller's convex regions, sorted by (instance, triangle)
+        (rt_region_offsets / rt_list_in_regions, include/rt_hip.h rule 15).  Fields: instance / triangle (int32), inside (uint8, 1
+        when the triangle lies wholly inside the region), normal ([3] float32, the world face normal as closest_points gives it).
+        regions as in count_in_regions.
+        max_hits=None (CSR): dict of `offsets` (int64 [n + 1], region j's pairs at offsets[j]:offsets[j+1]), the wanted fields over
+        all pairs ([total], [total, 3]), `query_index` (int32 [total], the flat index of each pair's region) and `count` (int32 of
+        the leading shape, from the offsets); "pops" in outputs adds the interior nodes visited by the fill.  On torch this makes
+        exactly ONE host synchronisation (reading offsets[n] to size the outputs).
+        max_hits=M >= 1: the first M pairs of each region, fields [..., M] / [..., M, 3] padded with instance = triangle = -1,
+        inside = 0 and float 0; `count` (the full number, so count > M means truncated) and `pops` only when in outputs -- without
+        count the traversal ends after the instance of a full room's greatest key, with the same rooms.  On torch fully
+        asynchronous on `stream`.  numpy arrays: copied to the device and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.REGION_LIST_OUTPUTS, extras=("count", "pops"))
+        return _list_query(self, _REGION_LIST[_region_planes(regions)], [("regions", regions)], _check_max_hits(max_hits), outputs, stream)
+
     GRID_OUTPUTS = ("occupied", "count")
 
     SEGMENT_OUTPUTS = _SEGMENT_OUTPUTS                                  # the fields of RtSegmentHits
@@ -1170,13 +1225,14 @@ def _trace_workspace(binning):
 
 
 # name -> (trailing shape, dtype) of every field a query returns, per query or per list slot: the same in every struct that has it
+# (but `inside`: a region's number of wholly-inside pairs here, a pair's flag in the region lists, which say so in their _ListKind)
 _FIELDS = dict(
     t=((), np.float32), distance=((), np.float32), sdf=((), np.float32), instance=((), np.int32), triangle=((), np.int32),
     count=((), np.int32), winding=((), np.int32), pops=((), np.int32), sign=((), np.int8), occluded=((), np.uint8),
     any=((), np.bool_), occupied=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
     point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32), parameter=((), np.float32),
     segment_point=((3,), np.float32), crossings=((), np.int32), clearance=((), np.float32), within=((), np.int32),
-    query_barycentric=((2,), np.float32), query_point=((3,), np.float32), intersections=((), np.int32))
+    query_barycentric=((2,), np.float32), query_point=((3,), np.float32), intersections=((), np.int32), inside=((), np.int32))
 
 
 def _check_outputs(outputs, allowed, extras=()):
@@ -1360,11 +1416,13 @@ class _ListKind:
     the struct (slot fields, then the per-query fields `tail`), the three C-ABI calls and the name of the per-slot query index of the
     CSR form"""
 
-    def __init__(self, names, keys, struct, ws, offsets, fill, index, inputs=None):
+    def __init__(self, names, keys, struct, ws, offsets, fill, index, inputs=None, extra=(), types=None):
         self.names, self.keys, self.struct = names, keys, struct
         self.tail = tuple(f for f, _t in struct._fields_[len(names):])
         self.ws, self.offsets, self.fill, self.index = ws, offsets, fill, index
         self.inputs = inputs or {}              # _query_inputs' shape / ints when they are not the defaults
+        self.extra = tuple(extra)               # integers the offsets and the fill call take after n (a region's plane count)
+        self.types = dict(_FIELDS, **(types or {}))     # a slot field whose type is not the per-query field's of that name
 
 
 def _list_query(scene, kind, inputs, max_hits, outputs, stream, per_query=None):
@@ -1388,15 +1446,16 @@ def _list_query(scene, kind, inputs, max_hits, outputs, stream, per_query=None):
             offsets = sg.alloc((n + 1,), np.int64, zero=n == 0)     # (rt_*_offsets writes all n + 1 entries, or nothing when n is 0)
             ws_bytes = max(int(getattr(h, kind.ws)(n)), 1)
             ws = sg.alloc((ws_bytes,), np.uint8)
-            check(getattr(h, kind.offsets)(handle, *ins, n, sg.ptr(offsets), sg.ptr(ws), ws_bytes, sg.stream, sg.sync), kind.offsets)
+            check(getattr(h, kind.offsets)(handle, *ins, n, *kind.extra, sg.ptr(offsets), sg.ptr(ws), ws_bytes, sg.stream, sg.sync),
+                  kind.offsets)
             rows = (sg.read_int64(offsets, n),)                     # torch: the one host synchronisation, for the size of the outputs
         else:
             rows = lead + (max_hits,)
-        out = {k: sg.alloc(rows + _FIELDS[k][0], _FIELDS[k][1]) for k in fields}
+        out = {k: sg.alloc(rows + kind.types[k][0], kind.types[k][1]) for k in fields}
         lst = kind.struct(*[sg.ptr(out[k]) if k in out else None for k in kind.names],
                           *[sg.ptr(tail[k]) if k in tail else None for k in kind.tail])
-        check(getattr(h, kind.fill)(handle, *ins, n, sg.ptr(offsets) if csr else None, 0 if csr else max_hits, C.byref(lst), sg.stream,
-                                    sg.sync), kind.fill)
+        check(getattr(h, kind.fill)(handle, *ins, n, *kind.extra, sg.ptr(offsets) if csr else None, 0 if csr else max_hits, C.byref(lst),
+                                    sg.stream, sg.sync), kind.fill)
         res = {k: sg.result(out[k]) for k in kind.names if k in outputs}
         res.update({k: sg.result(a) for k, a in tail.items()})
         if csr:
@@ -1423,6 +1482,20 @@ _PLANE_INPUTS = dict(shape=(2, 3))                  # (a box array's shape: poin
 _SECTION_LIST = _ListKind(_SECTION_LIST_OUTPUTS, ("instance", "triangle"), RtSectionList,
                           "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections", "query_index",
                           inputs=_PLANE_INPUTS)
+REGION_MAX_PLANES = 8                               # RT_REGION_MAX_PLANES of include/rt_hip.h
+# one kind per plane count: K is part of the input's shape and an argument of the calls; a slot's inside is a flag, a query's a number
+_REGION_LIST = {K: _ListKind(_REGION_LIST_OUTPUTS, ("instance", "triangle"), RtRegionList,
+                             "rt_region_offsets_workspace_bytes", "rt_region_offsets", "rt_list_in_regions", "query_index",
+                             inputs=dict(shape=(K, 2, 3)), extra=(K,), types=dict(inside=((), np.uint8)))
+                for K in range(1, REGION_MAX_PLANES + 1)}
+
+
+def _region_planes(regions):
+    """K of a regions array [..., K, 2, 3], checked before any device call (_query_inputs checks the rest)"""
+    shape = tuple(getattr(regions, "shape", ()))
+    if len(shape) < 3 or shape[-2:] != (2, 3) or not 1 <= shape[-3] <= REGION_MAX_PLANES:
+        raise ValueError("regions must have the shape [..., K, 2, 3] with 1 <= K <= %d, got %s" % (REGION_MAX_PLANES, shape or type(regions)))
+    return int(shape[-3])
 
 
 def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=(), scratch=None):
@@ -1444,6 +1517,73 @@ def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=(), scratc
             ws = (None if workspace is None else sg.ptr(workspace), ws_bytes)
         call(h, handle, ins, {k: sg.ptr(a) for k, a in out.items()}, n, sg.stream, sg.sync, *ws)
         return {k: sg.result(a) for k, a in out.items()}
+
+
+def _xp(a):
+    """numpy, or torch for a tensor: the region helpers use only what the two spell alike"""
+    if type(a).__module__.split(".")[0] == "torch":
+        import torch
+        return torch
+    return np
+
+
+def _cross(xp, u, v):
+    return xp.stack([u[..., 1] * v[..., 2] - u[..., 2] * v[..., 1], u[..., 2] * v[..., 0] - u[..., 0] * v[..., 2],
+                     u[..., 0] * v[..., 1] - u[..., 1] * v[..., 0]], -1)
+
+
+def _unit(xp, v):
+    return v / xp.sqrt((v * v).sum(-1))[..., None]
+
+
+def _plane(xp, point, normal):
+    return xp.stack([point, normal], -2)
+
+
+def regions_from_boxes(boxes):
+    """World-aligned boxes [..., 2, 3] (lo then hi) as regions [..., 6, 2, 3] for Scene.count_in_regions / list_in_regions: the planes
+    x-lo, x-hi, y-lo, y-hi, z-lo, z-hi, each with its point on its own face (the lo corner or the hi corner) and a unit normal
+    pointing inward.  numpy in, numpy out; torch in, torch out.  Plain fp32 arithmetic, OUTSIDE the exact contract of rule 15: the
+    region is what the planes say, and it is not rule 11's box test (which is decided relative to the box's first corner)."""
+    xp = _xp(boxes)
+    lo, hi = boxes[..., 0, :], boxes[..., 1, :]
+    planes = []
+    for a in range(3):
+        e = xp.zeros_like(lo)
+        e[..., a] = 1.0
+        planes += [_plane(xp, lo, e), _plane(xp, hi, -e)]
+    return xp.stack(planes, -3)
+
+
+def regions_from_obbs(centers, axes, half_extents):
+    """Oriented boxes as regions [..., 6, 2, 3]: centers [..., 3], axes [..., 3, 3] (row a is the box's a-th axis, a unit vector; the
+    three orthogonal), half_extents [..., 3].  The planes come in pairs per axis, at center - h_a*axis_a with normal +axis_a and at
+    center + h_a*axis_a with normal -axis_a, each point on its own face.  numpy in, numpy out; torch in, torch out.  Plain fp32
+    arithmetic, outside the exact contract of rule 15."""
+    xp = _xp(centers)
+    planes = []
+    for a in range(3):
+        u = axes[..., a, :]
+        d = half_extents[..., a][..., None] * u
+        planes += [_plane(xp, centers - d, u), _plane(xp, centers + d, -u)]
+    return xp.stack(planes, -3)
+
+
+def regions_from_frusta(eyes, corners, near, far):
+    """View frusta and selection pyramids as regions [..., 6, 2, 3]: eyes [..., 3]; corners [..., 4, 3], world points the four edges
+    of the pyramid pass through, counter-clockwise seen from the eye; near and far, numbers or arrays of the leading shape.  Planes 0-3
+    are the sides, each through the eye and two consecutive corner directions d_i = corner_i - eye (normal cross(d_(i+1), d_i),
+    which points inward); planes 4 and 5 are the caps at the distances near and far along the normalised mean of the four unit
+    directions, with normals along it and against it.  numpy in, numpy out; torch in, torch out.  Plain fp32 arithmetic, outside
+    the exact contract of rule 15."""
+    xp = _xp(eyes)
+    d = [corners[..., i, :] - eyes for i in range(4)]
+    planes = [_plane(xp, eyes, _cross(xp, d[(i + 1) % 4], d[i])) for i in range(4)]
+    m = _unit(xp, _unit(xp, d[0]) + _unit(xp, d[1]) + _unit(xp, d[2]) + _unit(xp, d[3]))
+    near, far = (x[..., None] if len(getattr(x, "shape", ())) else x for x in (near, far))
+    planes += [_plane(xp, eyes + near * m, m), _plane(xp, eyes + far * m, -m)]
+    out = xp.stack(planes, -3)
+    return out.astype(np.float32) if xp is np else out.float()          # (a float64 near or far does not widen the result)
 
 
 def render_debug(scene, camera):

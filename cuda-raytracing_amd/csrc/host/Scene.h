@@ -27,6 +27,8 @@ struct RtSectionCounts;
 struct RtSectionList;
 struct RtSegmentHits;
 struct RtTriangleHits;
+struct RtRegionCounts;
+struct RtRegionList;
 
 class Scene {
 public:
@@ -124,6 +126,15 @@ public:
     // Returns the status.
     int closest_to_triangles(const float* d_triangles, const float* d_max_distance, const int32_t* d_skip_instance, int32_t n,
                              const RtTriangleHits& out, void* stream = nullptr, bool synchronize = false);
+    // Region queries on the device scene: rt_count_in_regions / rt_region_offsets / rt_list_in_regions of include/rt_hip.h (rule 15,
+    // rooms), where the semantics are.  Regions ([n][planes_per_region][2][3] world, point then inward normal), offsets, workspace
+    // and outputs are DEVICE arrays.  Return the status.
+    int count_in_regions(const float* d_regions, int32_t n, int32_t planes_per_region, const RtRegionCounts& out, void* stream = nullptr,
+                         bool synchronize = false);
+    int region_offsets(const float* d_regions, int32_t n, int32_t planes_per_region, int64_t* d_offsets, void* d_workspace,
+                       size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
+    int list_in_regions(const float* d_regions, int32_t n, int32_t planes_per_region, const int64_t* d_offsets, int32_t max_hits,
+                        const RtRegionList& out, void* stream = nullptr, bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

@@ -764,6 +764,30 @@ int Scene::closest_to_triangles(const float* d_triangles, const float* d_max_dis
     return last_error;
 }
 
+int Scene::count_in_regions(const float* d_regions, int32_t n, int32_t planes_per_region, const RtRegionCounts& out, void* stream,
+                            bool synchronize)
+{
+    last_error = d_scene ? rt_count_in_regions(d_scene, d_regions, n, planes_per_region, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::region_offsets(const float* d_regions, int32_t n, int32_t planes_per_region, int64_t* d_offsets, void* d_workspace,
+                          size_t workspace_bytes, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_region_offsets(d_scene, d_regions, n, planes_per_region, d_offsets, d_workspace, workspace_bytes, stream,
+                                             synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
+int Scene::list_in_regions(const float* d_regions, int32_t n, int32_t planes_per_region, const int64_t* d_offsets, int32_t max_hits,
+                           const RtRegionList& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_list_in_regions(d_scene, d_regions, n, planes_per_region, d_offsets, max_hits, &out, stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 void Scene::update_mesh_instance(int index, MeshInstance mesh_instance)
 {
     if (index < 0 || index >= (int)mesh_instances.size()) { last_error = RT_E_INVALID; return; }

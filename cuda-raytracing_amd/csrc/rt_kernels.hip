@@ -4299,15 +4299,29 @@ __device__ __forceinline__ void sc_axis(float lo, float hi, float s, float q, fl
 }
 // Whether a child box can hold a vertex of either class: step 4's height bounded from both sides in step 4's own order of sums,
 // the bounds widened by E = 2^-16 of the terms' magnitudes plus FLT_MIN; skipped only when a compare says that every height is > 0 or
-// every height is < 0, so a NaN anywhere keeps the box
-__device__ __forceinline__ bool sc_box(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 q, V3 n)
+// every height is < 0, so a NaN anywhere keeps the box.  sc_bounds is the arithmetic, shared by the section and the region kernels.
+__device__ __forceinline__ void sc_bounds(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 q, V3 n, float& lower,
+                                          float& upper, float& e)
 {
     float ax, bx, mx, ay, by, my, az, bz, mz;
     sc_axis(lx, hx, s.x, q.x, n.x, ax, bx, mx);
     sc_axis(ly, hy, s.y, q.y, n.y, ay, by, my);
     sc_axis(lz, hz, s.z, q.z, n.z, az, bz, mz);
-    const float lower = (ax + ay) + az, upper = (bx + by) + bz, e = ((mx + my) + mz) * 0x1p-16f + 0x1p-126f;
+    lower = (ax + ay) + az; upper = (bx + by) + bz; e = ((mx + my) + mz) * 0x1p-16f + 0x1p-126f;
+}
+__device__ __forceinline__ bool sc_box(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 q, V3 n)
+{
+    float lower, upper, e;
+    sc_bounds(lx, ly, lz, hx, hy, hz, s, q, n, lower, upper, e);
     return !((lower - e) > 0.0f) && !((upper + e) < 0.0f);
+}
+// The upper half alone (rule 15): false when a compare says that every vertex that can lie in the box is BELOW
+// the plane; a NaN keeps the box
+__device__ __forceinline__ bool sc_box_above(float lx, float ly, float lz, float hx, float hy, float hz, V3 s, V3 q, V3 n)
+{
+    float lower, upper, e;
+    sc_bounds(lx, ly, lz, hx, hy, hz, s, q, n, lower, upper, e);
+    return !((upper + e) < 0.0f);
 }
 
 // Rule 12 step 6 for one pair, out of line and from the record again (the same sequence as the traversal's test, the same bits), so none
@@ -4528,6 +4542,301 @@ __global__ __launch_bounds__(kTriBlock, 8) void section_list_kernel(const SecPar
         p.instance[q] = -1;
         p.triangle[q] = -1;
         if (p.segment) { for (int c = 0; c < 6; c++) p.segment[6 * q + c] = 0.0f; }
+        if (p.normal) { p.normal[3 * q] = 0.0f; p.normal[3 * q + 1] = 0.0f; p.normal[3 * q + 2] = 0.0f; }
+    }
+    if (p.count) p.count[i] = total;
+    if (p.pops) p.pops[i] = pops;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------
+// Region queries (rt_count_in_regions / rt_region_offsets / rt_list_in_regions): every (instance, triangle) that lies in or touches
+// a caller's convex region -- the intersection of K half-spaces, K <= RT_REGION_MAX_PLANES, one K per call -- by rule 15 of
+// include/rt_hip.h: rule 12's classes on every plane, then the triangle clipped by the planes in order; equal to a brute-force loop
+// over every (instance, triangle) whatever the tree.  The pruning argument is in DESIGN.md section 20.  One wave per workgroup, one
+// region per lane, the sections' traversal on the general stack: a child box is skipped when on some plane every vertex that can lie
+// in it is BELOW.  The mapped planes (p'_k, n'_k: 6K words) live in registers through the node loop; the kernels are templated on a
+// plane capacity KT >= K, and the call's K bounds every plane loop, so no plane is padded.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int kRegionMaxPlanes = RT_REGION_MAX_PLANES;
+constexpr int kRegionMaxVerts = 3 + kRegionMaxPlanes;
+struct RegParams {
+    const float4* records;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* regions;       // [n][planes][2][3] world planes, point then inward normal
+    int32_t n;
+    int32_t planes;             // K, 1..kRegionMaxPlanes
+    const int64_t* offsets;     // the list kernel: [n + 1] (CSR rooms) or null: fixed rooms of max_hits
+    int32_t max_hits;
+    int32_t *instance, *triangle;   // the list kernel's keys, required; indexed by room slot
+    uint8_t* flag;              // the list kernel: optional, [slots] the pair's inside flag
+    float* normal;              // the list kernel: optional, [slots][3]
+    int32_t* count;             // optional, [n] (the offsets call: the workspace)
+    int32_t* inside;            // optional, [n] the number of wholly-inside pairs (the count kernel)
+    uint8_t* any;               // optional, [n] (the count kernel)
+    int32_t* pops;              // optional, [n]
+};
+
+__device__ __forceinline__ V3 rg_load(const float* R, int j) { return v3(R[3 * j], R[3 * j + 1], R[3 * j + 2]); }
+
+// Rule 15 step 5 for one triangle that passed step 3 and is not wholly inside: whether the clip leaves a polygon.  Out of line and
+// from the record and the region again (the same sequence as the traversal's heights, the same bits), so none of it occupies the
+// traversal's registers; the two polygons live in scratch, which only triangles that straddle a face pay for.  A plane that has every
+// current vertex above reproduces the polygon and is skipped.
+__device__ __noinline__ bool rg_clip(const float4* records, const DevInstance& in, int32_t slot, const float* R, int32_t K)
+{
+    const float4* rec = records + (size_t)slot * 4;
+    V3 a, ab, ac;
+    pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+    V3 poly[2][kRegionMaxVerts];
+    float g[kRegionMaxVerts];
+    poly[0][0] = a; poly[0][1] = a + ab; poly[0][2] = a + ac;
+    int m = 3, cur = 0;
+    for (int32_t j = 0; j < K; j++) {
+        const V3 q = sc_point(rg_load(R, 2 * j), in), n = sc_normal(rg_load(R, 2 * j + 1), in);
+        const V3* v = poly[cur];
+        V3* w = poly[cur ^ 1];
+        bool all = true;
+        for (int i = 0; i < m; i++) {
+            g[i] = sc_height(n, q, v[i]);
+            all = all && g[i] >= 0.0f;
+        }
+        if (all) continue;
+        int o = 0;
+        for (int i = 0; i < m; i++) {
+            const int i1 = i + 1 == m ? 0 : i + 1;
+            const bool ai = g[i] >= 0.0f, an = g[i1] >= 0.0f;
+            if (ai && o < kRegionMaxVerts) w[o++] = v[i];
+            if (ai != an && o < kRegionMaxVerts) {              // the cut, from the end that is not above towards the end that is
+                const V3 x = ai ? v[i1] : v[i], y = ai ? v[i] : v[i1];
+                const float hx = ai ? g[i1] : g[i], hy = ai ? g[i] : g[i1];
+                const float t = hx / (hx - hy);
+                w[o++] = v3(x.x + t * (y.x - x.x), x.y + t * (y.y - x.y), x.z + t * (y.z - x.z));
+            }
+        }
+        if (o == 0) return false;
+        m = o; cur ^= 1;
+    }
+    return true;
+}
+
+// Every pair of the world region R ([K][2][3]), instance by instance in ascending order (triangles of one instance in tree order).
+// go(k) is asked before instance k (false ends the traversal); pair(k, slot, inside) is called at each pair and returns whether to end
+// the traversal.  Returns the interior nodes visited.  A region with a zero normal (rule 15 step 1) visits nothing.
+template <int KT, typename Go, typename Pair>
+__device__ __forceinline__ int32_t rg_trace(const RegParams& p, TriStack& stack, const float* R, Go&& go, Pair&& pair)
+{
+    int32_t pops = 0;
+    const int32_t K = p.planes;                                 // (1 <= K <= KT: the C-ABI chooses KT)
+#pragma unroll
+    for (int j = 0; j < KT; j++) {
+        if (j >= K) break;
+        const V3 N = rg_load(R, 2 * j + 1);
+        if (!(N.x != 0.0f || N.y != 0.0f || N.z != 0.0f)) return pops;
+    }
+    for (int32_t k = 0; k < p.num_instances; k++) {
+        if (!go(k)) break;
+        const DevInstance& in = p.instances[k];
+        V3 q[KT], n[KT];                                        // p'_j and n'_j: all the node loop keeps of the region, in registers
+#pragma unroll
+        for (int j = 0; j < KT; j++) {
+            q[j] = v3(0.0f, 0.0f, 0.0f); n[j] = q[j];
+            if (j < K) { q[j] = sc_point(rg_load(R, 2 * j), in); n[j] = sc_normal(rg_load(R, 2 * j + 1), in); }
+        }
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        bool done = false;
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: every child that no plane has wholly below it
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                bool pa = true, pb = true;
+                if (prune) {
+#pragma unroll
+                    for (int j = 0; j < KT; j++) {              // left at the first plane that skips the box
+                        if (j >= K || !pa) break;
+                        pa = sc_box_above(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, q[j], n[j]);
+                    }
+#pragma unroll
+                    for (int j = 0; j < KT; j++) {
+                        if (j >= K || !pb) break;
+                        pb = sc_box_above(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, q[j], n[j]);
+                    }
+                }
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                if (pa && pb) stack.push(rb);
+                cur = pa ? ra : (pb ? rb : kNeedPop);
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    V3 a, ab, ac;
+                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
+                    const V3 b = a + ab, c = a + ac;
+                    bool pass = true, allin = true;             // steps 3 and 4
+#pragma unroll
+                    for (int j = 0; j < KT; j++) {
+                        if (j >= K || !pass) break;
+                        const float ha = sc_height(n[j], q[j], a), hb = sc_height(n[j], q[j], b), hc = sc_height(n[j], q[j], c);
+                        const int above = (ha >= 0.0f) + (hb >= 0.0f) + (hc >= 0.0f), below = (ha < 0.0f) + (hb < 0.0f) + (hc < 0.0f);
+                        pass = above + below == 3 && below != 3;     // all three classified (a NaN height is neither), not all BELOW
+                        allin = allin && above == 3;
+                    }
+                    // step 5 only for a triangle that straddles a face
+                    if (pass && (allin || rg_clip(p.records, in, slot, R, K)) && pair(k, slot, allin)) done = true;
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel && !done);
+        if (done) break;
+    }
+    return pops;
+}
+
+// Waves per SIMD asked of the compiler for a plane capacity: the planes take 6*KT registers on top of the sections' 40
+constexpr int rg_waves(int KT) { return KT <= 2 ? 8 : KT <= 4 ? 6 : KT <= 6 ? 5 : 4; }
+
+// ANY = false: the pairs of each region and how many of them are wholly inside (rt_count_in_regions, and rt_region_offsets' first
+// step into the workspace).  ANY = true (any wanted, count and inside not): the traversal ends at the first pair, across instances too.
+template <int KT, bool ANY>
+__global__ __launch_bounds__(kTriBlock, rg_waves(KT)) void region_count_kernel(const RegParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const float* R = p.regions + (size_t)i * (size_t)(6 * p.planes);
+    int32_t total = 0, inside = 0;
+    const int32_t pops = rg_trace<KT>(p, stack, R, [&](int32_t) { return true; }, [&](int32_t, int32_t, bool in) {
+        total++;
+        inside += in ? 1 : 0;
+        return ANY;
+    });
+    if (p.count) p.count[i] = total;
+    if (p.inside) p.inside[i] = inside;
+    if (p.any) p.any[i] = total > 0 ? 1 : 0;
+    if (p.pops) p.pops[i] = pops;
+}
+
+// A room's entry while the heap is at work: the key (instance, triangle) as one number, the pair's inside flag, which travels with
+// the key in the entry's own inside slot when that field is wanted, and the pair's record slot, which travels in the entry's normal
+// (its first word) when normal is wanted, as section_list_kernel carries it.
+struct RgItem { uint64_t key; int32_t slot; uint8_t flag; };
+__device__ __forceinline__ RgItem rg_get(const RegParams& p, size_t q)
+{
+    RgItem it;
+    it.key = ((uint64_t)(uint32_t)p.instance[q] << 32) | (uint64_t)(uint32_t)p.triangle[q];
+    it.slot = p.normal ? __float_as_int(p.normal[3 * q]) : 0;
+    it.flag = p.flag ? p.flag[q] : 0;
+    return it;
+}
+__device__ __forceinline__ void rg_put(const RegParams& p, size_t q, RgItem it)
+{
+    p.instance[q] = (int32_t)(it.key >> 32);
+    p.triangle[q] = (int32_t)(uint32_t)it.key;
+    if (p.normal) p.normal[3 * q] = __int_as_float(it.slot);
+    if (p.flag) p.flag[q] = it.flag;
+}
+// bx_sift_down with the flag and the slot travelling along
+__device__ __forceinline__ void rg_sift_down(const RegParams& p, size_t start, uint64_t size, uint64_t pos, RgItem it)
+{
+    for (;;) {
+        uint64_t child = 2 * pos + 1;
+        if (child >= size) break;
+        RgItem ci = rg_get(p, start + (size_t)child);
+        if (child + 1 < size) {
+            const RgItem c2 = rg_get(p, start + (size_t)child + 1);
+            if (c2.key > ci.key) { ci = c2; child++; }
+        }
+        if (ci.key <= it.key) break;
+        rg_put(p, start + (size_t)pos, ci);
+        pos = child;
+    }
+    rg_put(p, start + (size_t)pos, it);
+}
+
+// box_list_kernel's lane-private max-heap on (instance, triangle) and its early end for fixed rooms without count.  A pair's inside
+// flag depends on the region, the instance and the record alone and travels with its key; normal is written after the sort from the
+// slot that travelled with it: the rooms are the same bits with and without count and whatever the tree.
+template <int KT>
+__global__ __launch_bounds__(kTriBlock, rg_waves(KT)) void region_list_kernel(const RegParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
+    const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    int spill[kMaxStack - kLdsStack];
+    TriStack stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    const float* R = p.regions + (size_t)i * (size_t)(6 * p.planes);
+    const bool early = !p.offsets && !p.count;
+    int32_t total = 0;
+    uint64_t filled = 0;                                        // (<= room)
+    const int32_t pops = rg_trace<KT>(p, stack, R, [&](int32_t k) {
+        if (!early || filled < (uint64_t)p.max_hits) return true;                   // (fixed rooms: start i*M, room M)
+        return k <= p.instance[(size_t)i * (size_t)p.max_hits];                     // (the root: the room's greatest key)
+    }, [&](int32_t k, int32_t slot, bool in) {
+        total++;
+        size_t start;
+        uint64_t room;
+        xl_room(p, i, start, room);                             // (read again per pair: not held across the traversal)
+        if (room == 0) return false;
+        RgItem it;
+        it.key = ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)p.tri_id[slot];
+        it.slot = slot;
+        it.flag = in ? 1 : 0;
+        if (filled < room) {                                    // sift up from the new last slot
+            uint64_t pos = filled++;
+            while (pos > 0) {
+                const uint64_t parent = (pos - 1) / 2;
+                const RgItem pi = rg_get(p, start + (size_t)parent);
+                if (pi.key >= it.key) break;
+                rg_put(p, start + (size_t)pos, pi);
+                pos = parent;
+            }
+            rg_put(p, start + (size_t)pos, it);
+        } else if (it.key < rg_get(p, start).key) {             // full: the root leaves
+            rg_sift_down(p, start, room, 0, it);
+        }
+        return false;
+    });
+    size_t start;
+    uint64_t room;
+    xl_room(p, i, start, room);
+    for (uint64_t end = filled; end > 1; end--) {               // heap -> ascending: the greatest key to the end, the rest a heap again
+        const RgItem last = rg_get(p, start + (size_t)(end - 1));
+        rg_put(p, start + (size_t)(end - 1), rg_get(p, start));
+        rg_sift_down(p, start, end - 1, 0, last);
+    }
+    if (p.normal) {
+        for (uint64_t j = 0; j < filled; j++) {                 // the sorted entries: normal from the slot
+            const size_t q = start + (size_t)j;
+            const V3 nn = pq_normal(p, p.instances[p.instance[q]], rg_get(p, q).slot);
+            p.normal[3 * q] = nn.x; p.normal[3 * q + 1] = nn.y; p.normal[3 * q + 2] = nn.z;
+        }
+    }
+    for (uint64_t j = filled; j < room; j++) {                  // padding
+        const size_t q = start + (size_t)j;
+        p.instance[q] = -1;
+        p.triangle[q] = -1;
+        if (p.flag) p.flag[q] = 0;
         if (p.normal) { p.normal[3 * q] = 0.0f; p.normal[3 * q + 1] = 0.0f; p.normal[3 * q + 2] = 0.0f; }
     }
     if (p.count) p.count[i] = total;
@@ -6609,6 +6918,90 @@ int rt_list_sections(RtScene* s, const float* d_planes, int32_t n, const int64_t
         p.count = out->count; p.pops = out->pops;
         const QueryShape k = query_shape(n, kTriBlock, p.stack_depth);
         hipLaunchKernelGGL(section_list_kernel, k.groups, dim3(kTriBlock), k.lds, st, p);
+        return RT_OK;
+    });
+}
+
+// ---- region queries -----------------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+bool region_planes_ok(int32_t planes) { return planes >= 1 && planes <= kRegionMaxPlanes; }
+RegParams region_params(const RtScene* s, const float* d_regions, int32_t n, int32_t planes)
+{
+    RegParams p = scene_params<RegParams>(s);
+    p.tri_id = s->d_tri_id;
+    p.regions = d_regions; p.n = n; p.planes = planes;
+    return p;
+}
+// the kernel of the smallest plane capacity that holds the call's K
+template <int KT>
+void launch_region_count_kt(const RegParams& p, bool any_only, const QueryShape& k, hipStream_t st)
+{
+    if (any_only)
+        hipLaunchKernelGGL((region_count_kernel<KT, true>), k.groups, dim3(kTriBlock), k.lds, st, p);
+    else
+        hipLaunchKernelGGL((region_count_kernel<KT, false>), k.groups, dim3(kTriBlock), k.lds, st, p);
+}
+void launch_region_count(const RegParams& p, bool any_only, hipStream_t st)
+{
+    const QueryShape k = query_shape(p.n, kTriBlock, p.stack_depth);
+    if (p.planes <= 2) launch_region_count_kt<2>(p, any_only, k, st);
+    else if (p.planes <= 4) launch_region_count_kt<4>(p, any_only, k, st);
+    else if (p.planes <= 6) launch_region_count_kt<6>(p, any_only, k, st);
+    else launch_region_count_kt<8>(p, any_only, k, st);
+}
+void launch_region_list(const RegParams& p, hipStream_t st)
+{
+    const QueryShape k = query_shape(p.n, kTriBlock, p.stack_depth);
+    if (p.planes <= 2) hipLaunchKernelGGL(region_list_kernel<2>, k.groups, dim3(kTriBlock), k.lds, st, p);
+    else if (p.planes <= 4) hipLaunchKernelGGL(region_list_kernel<4>, k.groups, dim3(kTriBlock), k.lds, st, p);
+    else if (p.planes <= 6) hipLaunchKernelGGL(region_list_kernel<6>, k.groups, dim3(kTriBlock), k.lds, st, p);
+    else hipLaunchKernelGGL(region_list_kernel<8>, k.groups, dim3(kTriBlock), k.lds, st, p);
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_count_in_regions(RtScene* s, const float* d_regions, int32_t n, int32_t planes_per_region, const RtRegionCounts* out, void* stream,
+                        int synchronize)
+{
+    if (!s || n < 0 || !region_planes_ok(planes_per_region) || (n > 0 && (!d_regions || !out))) return RT_E_INVALID;
+    if (n > 0 && !(out->count || out->inside || out->any || out->pops)) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        RegParams p = region_params(s, d_regions, n, planes_per_region);
+        p.count = out->count; p.inside = out->inside; p.any = out->any; p.pops = out->pops;
+        launch_region_count(p, p.any && !p.count && !p.inside, st);     // (any without count or inside: stop at the first pair)
+        return RT_OK;
+    });
+}
+
+size_t rt_region_offsets_workspace_bytes(int32_t n) { return offsets_workspace_bytes(n); }
+
+int rt_region_offsets(RtScene* s, const float* d_regions, int32_t n, int32_t planes_per_region, int64_t* d_offsets, void* d_workspace,
+                      size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (!s || n < 0 || !region_planes_ok(planes_per_region) || (n > 0 && (!d_regions || !d_offsets || !d_workspace))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched, d_offsets not written
+    return query_offsets(s, n, d_offsets, d_workspace, workspace_bytes, stream, synchronize, [&](int32_t* counts, hipStream_t st) {
+        RegParams p = region_params(s, d_regions, n, planes_per_region);
+        p.count = counts;
+        launch_region_count(p, false, st);
+    });
+}
+
+int rt_list_in_regions(RtScene* s, const float* d_regions, int32_t n, int32_t planes_per_region, const int64_t* d_offsets, int32_t max_hits,
+                       const RtRegionList* out, void* stream, int synchronize)
+{
+    if (!s || n < 0 || !region_planes_ok(planes_per_region) || (n > 0 && (!d_regions || !out))) return RT_E_INVALID;
+    if ((d_offsets != nullptr) == (max_hits >= 1)) return RT_E_INVALID;     // exactly one of CSR and fixed rooms
+    if (n > 0 && !(out->instance && out->triangle)) return RT_E_INVALID;     // the room holds the keys
+    if (n == 0) return RT_OK;
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        RegParams p = region_params(s, d_regions, n, planes_per_region);
+        p.offsets = d_offsets; p.max_hits = d_offsets ? 0 : max_hits;
+        p.instance = out->instance; p.triangle = out->triangle; p.flag = out->inside; p.normal = out->normal;
+        p.count = out->count; p.pops = out->pops;
+        launch_region_list(p, st);
         return RT_OK;
     });
 }

@@ -927,6 +927,77 @@ typedef struct RtTriangleHits { /* every pointer optional (NULL = not wanted), a
 int rt_closest_to_triangles(RtScene *scene, const float *d_triangles, const float *d_max_distance, const int32_t *d_skip_instance,
                             int32_t n, const RtTriangleHits *out, void *stream, int synchronize);
 
+/* ---- region queries: every (instance, triangle) of the scene that lies in or touches a caller's convex REGION,
+ *      the intersection of K half-spaces -- a view frustum, a selection pyramid, an oriented box, a wedge, a slab between two planes --
+ *      and whether the triangle lies wholly inside.  Selection, culling, "what is in this workspace or sensor cone", clipping to a
+ *      section box.  The pairs equal a brute-force loop over every (instance, triangle), whatever the tree (host-built, device-built,
+ *      refitted) and whatever the traversal order.
+ *      15. For region j, the planes (P_k, N_k), k = 0..K-1, in world space (fp32, N_k not normalised, pointing INWARD: the inside of a
+ *          plane is its ABOVE side) and instance i; K is one value per call, 1 <= K <= RT_REGION_MAX_PLANES; every operation fp32 in
+ *          one fixed sequence, no contraction:
+ *          1. Valid region: every N_k has at least one component that compares != 0.  Any other region has no pairs.
+ *          2. Map: p'_k, n'_k by rule 12 step 2; the scene triangle A = v0*s, B = A + AB, C = A + AC by rule 10 step 2; the height
+ *             h_k(X) by rule 12 step 4 with (p'_k, n'_k), and rule 12's classes: ABOVE when h >= 0 (so -0 is above), BELOW when
+ *             h < 0, neither for a NaN.
+ *          3. Pre-test: on every plane all three vertices have a class and not all three are BELOW; otherwise no pair.
+ *          4. Wholly inside: all three vertices ABOVE on every plane: a PAIR with inside = 1.
+ *          5. Otherwise the polygon V = (A, B, C) is clipped in scaled mesh space by the planes in the order k = 0..K-1.  With m
+ *             vertices (m < 3 too) and g_i = h_k(V_i) by step 2's formula, i = 0..m-1 walks the edge V_i -> V_((i+1) mod m): V_i is
+ *             emitted when g_i >= 0; when exactly one of g_i >= 0 and g_(i+1) >= 0 holds, the cut is emitted after it, computed from
+ *             the end X that is not above towards the end Y that is, by rule 12 step 6's formula: t = hX / (hX - hY),
+ *             Q = X + t*(Y - X) per component.  A polygon holds at most 3 + RT_REGION_MAX_PLANES = 11 vertices: one that would be
+ *             the twelfth is not emitted (only inconsistent roundings on nearly collinear vertices get there; it cannot empty a
+ *             polygon).  An empty polygon after some plane: no pair.  A non-empty polygon after the last plane: a PAIR with
+ *             inside = 0.  (A plane that has every current vertex above reproduces the polygon, so skipping it gives the same bits.)
+ *          6. Per pair: instance and triangle (the uploaded numbering), inside, normal [3] = the world face normal exactly as
+ *             rt_closest_points gives it.  ORDER: a region's pairs sorted by (instance, triangle) ascending.  ROOMS (CSR or fixed
+ *             max_hits), padding (instance = triangle = -1, inside = 0, the floats 0) and "nothing is ever written outside a room"
+ *             are rule 8's.
+ *          7. NON-FINITE regions, and regions whose heights overflow fp32 on this scene, follow rule 12 step 8: no fault, no effect on
+ *             other queries, nothing written outside their room; their own results are unspecified.
+ *          NOT PROMISED: the test is CLOSED (touching counts) and decided in fp32, so a triangle nearer to a face than the rounding of
+ *          the heights can go either way.  Face k's decision is relative to P_k: a caller who wants tight rounding puts P_k on the
+ *          region's face, not at the origin.  The clipped polygon is not an output.
+ *      rt_count_in_regions: count [n] (the number of pairs), inside [n] (the number of pairs with inside = 1), any [n] (1 when there is
+ *      a pair), pops [n] (interior nodes visited, a statistic); all optional, at least one given.  With any and with neither count nor
+ *      inside the traversal ends at the first pair, across instances too.
+ *      rt_region_offsets writes offsets[0] = 0 and offsets[i+1] = offsets[i] + count_i (int64): the count traversal into the
+ *      workspace, then rt_crossing_offsets' exclusive scan on the device.  Its workspace is DEVICE memory of at least
+ *      rt_region_offsets_workspace_bytes(n) bytes (0 for n <= 0).  With n == 0 nothing is launched and d_offsets is not written.
+ *      rt_list_in_regions fills the rooms: CSR (d_offsets) or fixed (d_offsets NULL, max_hits >= 1), as in rule 8.  instance and
+ *      triangle are REQUIRED (the room is where the keys live), the rest optional; count[n] is each region's FULL count even when the
+ *      room truncates.  In fixed rooms without count, once a room is full the traversal ends after the instance of the room's greatest
+ *      key; the rooms are the same bits with and without count.
+ *      All calls: d_regions is a DEVICE array [n][planes_per_region][2][3], point then normal, like a plane array; asynchronous on
+ *      `stream` unless synchronize != 0; no host synchronisation, allocation or scene scratch (calls may overlap each other and
+ *      renders); nothing launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, planes_per_region outside 1..RT_REGION_MAX_PLANES, NULL regions with n > 0;
+ *      rt_count_in_regions: NULL out or no output with n > 0; rt_region_offsets: d_offsets or d_workspace NULL, or a workspace too
+ *      small, with n > 0; rt_list_in_regions: NULL out, or instance or triangle NULL, with n > 0; both or neither of d_offsets and
+ *      max_hits >= 1. ------------------------------------------------------------------------------------------------------------ */
+#define RT_REGION_MAX_PLANES 8
+typedef struct RtRegionCounts {     /* every pointer optional, at least one given                                              */
+    int32_t *count;             /* [n] the number of pairs                                                                 */
+    int32_t *inside;            /* [n] the number of pairs that lie wholly inside the region                               */
+    uint8_t *any;               /* [n] 1 when the region has a pair                                                        */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic, not part of the exact contract)                */
+} RtRegionCounts;
+typedef struct RtRegionList {       /* fields indexed by room slot; instance and triangle REQUIRED, the rest optional          */
+    int32_t *instance;          /* [slots] -1 = padding                                                                    */
+    int32_t *triangle;          /* [slots] the uploaded numbering; -1 = padding                                            */
+    uint8_t *inside;            /* [slots] 1 when the triangle lies wholly inside the region                               */
+    float *normal;              /* [slots][3] world face normal                                                            */
+    int32_t *count;             /* [n] the full number of pairs of each region                                             */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic)                                                */
+} RtRegionList;
+int rt_count_in_regions(RtScene *scene, const float *d_regions, int32_t n, int32_t planes_per_region, const RtRegionCounts *out,
+                        void *stream, int synchronize);
+size_t rt_region_offsets_workspace_bytes(int32_t n);
+int rt_region_offsets(RtScene *scene, const float *d_regions, int32_t n, int32_t planes_per_region, int64_t *d_offsets, void *d_workspace,
+                      size_t workspace_bytes, void *stream, int synchronize);
+int rt_list_in_regions(RtScene *scene, const float *d_regions, int32_t n, int32_t planes_per_region, const int64_t *d_offsets,
+                       int32_t max_hits, const RtRegionList *out, void *stream, int synchronize);
+
 /* ---- timing on the stream the kernels run on (hipEvent) ---------------------------------- */
 typedef struct RtTimer RtTimer;
 int rt_timer_create(RtTimer **t);
