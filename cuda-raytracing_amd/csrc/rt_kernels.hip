@@ -2342,6 +2342,113 @@ struct PointParams {
 constexpr int kPointBlock = 64;
 typedef StackT<kPointBlock> PointStack;
 
+// What the one-wave query kernels (kPointBlock, kCrossBlock, kTriBlock: one query per lane) share.
+// A lane's stack: its column of the workgroup's LDS block and the overflow array its kernel declares
+__device__ __forceinline__ StackT<64> query_stack(int* lds_stack, int* spill, int stack_depth)
+{
+    StackT<64> stack;
+    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(stack_depth); stack.sp = 0;
+    return stack;
+}
+
+// The unordered traversal of instance in's tree, for the queries that want every pair and no order: crossings, crossing lists and
+// sections (ti_trace, bx_trace and rg_trace keep this loop written out: on the walker one intersect kernel spills two more registers
+// and the long box and region lists measured under 1 % slower).
+// box(lx, ly, lz, hx, hy, hz) says whether a child box may hold a pair; it is asked only where `prune` (the caller clears it for a
+// mesh with unordered / NaN boxes: no pruning in this mesh), child a and then child b, and b is postponed when both pass.
+// leaf(slot, t0, t1, t2) gets one triangle's record, triangles in tree order, and returns whether to end the traversal.  pops counts
+// the interior nodes visited.  Returns whether leaf ended it.  P: any query's params.
+template <typename P, typename Box, typename Leaf>
+__device__ __forceinline__ bool walk_unordered(const P& p, StackT<64>& stack, const DevInstance& in, bool prune, int32_t& pops, Box&& box,
+                                               Leaf&& leaf)
+{
+    bool done = false;
+    stack.sp = 0;
+    stack.push(kSentinel);
+    int32_t cur = in.root_ref, rem = -1;
+    do {
+        if (cur >= 0) {                                         // interior node: every child that passes, no order
+            pops++;
+            const float4* rec = p.records + (size_t)cur * 4;
+            const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+            const bool pa = !prune || box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y);
+            const bool pb = !prune || box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w);
+            const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+            if (pa && pb) stack.push(rb);
+            cur = pa ? ra : (pb ? rb : kNeedPop);
+        } else {                                                // one triangle of a leaf per iteration
+            const int32_t slot = cur & kSlotMask;
+            if (rem < 0) {
+                rem = (cur >> kSlotBits) & 31;
+                if (rem == 31) rem = p.leaf_count[slot];        // (leaves of more than 30 triangles)
+            }
+            if (rem > 0) {
+                const float4* rec = p.records + (size_t)slot * 4;
+                if (leaf(slot, rec[0], rec[1], rec[2])) done = true;
+            }
+            rem--;
+            cur = rem > 0 ? cur + 1 : kNeedPop;
+            rem = rem > 0 ? rem : -1;
+        }
+        if (cur == kNeedPop) cur = stack.pop();
+    } while (cur != kSentinel && !done);
+    return done;
+}
+template <typename P>
+__device__ __forceinline__ bool boxes_ordered(const P& p, const DevInstance& in) { return (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0; }
+
+// A list room kept as a lane-private max-heap of its entries' keys while pairs arrive, and sorted in place at the end: a pair enters
+// in O(log room).  A: the room's accessor, get(q) and put(q, item) on absolute slots; an item has .key, and whatever travels with it.
+// (instance, triangle) as one key, compared as a pair (both >= 0 in a filled slot)
+__device__ __forceinline__ uint64_t pair_key(int32_t instance, int32_t triangle) { return ((uint64_t)(uint32_t)instance << 32) | (uint64_t)(uint32_t)triangle; }
+// `it` enters the heap of `size` slots at `start` from slot `pos` downwards: greater children move up until it fits
+template <typename A, typename Item>
+__device__ __forceinline__ void room_sift_down(const A& a, size_t start, uint64_t size, uint64_t pos, Item it)
+{
+    for (;;) {
+        uint64_t child = 2 * pos + 1;
+        if (child >= size) break;
+        Item ci = a.get(start + (size_t)child);
+        if (child + 1 < size) {
+            const Item c2 = a.get(start + (size_t)child + 1);
+            if (c2.key > ci.key) { ci = c2; child++; }
+        }
+        if (ci.key <= it.key) break;
+        a.put(start + (size_t)pos, ci);
+        pos = child;
+    }
+    a.put(start + (size_t)pos, it);
+}
+// One pair arrives: while the room fills it sifts up from the new last slot; a full room takes it only below its greatest key, the
+// root, which leaves.  Which keys stay does not depend on the order of arrival.
+template <typename A, typename Item>
+__device__ __forceinline__ void room_insert(const A& a, size_t start, uint64_t room, uint64_t& filled, Item it)
+{
+    if (filled < room) {
+        uint64_t pos = filled++;
+        while (pos > 0) {
+            const uint64_t parent = (pos - 1) / 2;
+            const Item pi = a.get(start + (size_t)parent);
+            if (pi.key >= it.key) break;
+            a.put(start + (size_t)pos, pi);
+            pos = parent;
+        }
+        a.put(start + (size_t)pos, it);
+    } else if (it.key < a.get(start).key) {
+        room_sift_down(a, start, room, 0, it);
+    }
+}
+// heap -> ascending: the greatest key to the end, the rest a heap again
+template <typename A>
+__device__ __forceinline__ void room_sort(const A& a, size_t start, uint64_t filled)
+{
+    for (uint64_t end = filled; end > 1; end--) {
+        const auto last = a.get(start + (size_t)(end - 1));
+        a.put(start + (size_t)(end - 1), a.get(start));
+        room_sift_down(a, start, end - 1, 0, last);
+    }
+}
+
 // Ericson's closest point on triangle (A, A + AB, A + AC) to q (Real-Time Collision Detection 5.1.5), returned as the weights (b1, b2) of
 // AB and AC, in one fixed fp32 sequence.  An edge ratio whose denominator is not > 0 is 0 (and a ratio is never above 1).  Where the
 // classification reaches the face region with a negative va, vb or vc or a sum that is not > 0 (rounding on nearly degenerate
@@ -2460,8 +2567,7 @@ __global__ __launch_bounds__(kPointBlock, 8) void closest_point_kernel(const Poi
     const V3 w = v3(p.pts[i3], p.pts[i3 + 1], p.pts[i3 + 2]);
     const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
     int spill[kMaxStack - kLdsStack];
-    PointStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    PointStack stack = query_stack(lds_stack, spill, p.stack_depth);
     // the best candidate so far by (d2, instance, tri_id); best_inst < 0 = none yet
     float best = 0.0f, b1 = 0.0f, b2 = 0.0f;
     int32_t best_inst = -1, best_slot = 0, best_tid = 0, pops = 0;
@@ -2662,8 +2768,7 @@ __global__ __launch_bounds__(kPointBlock, 8) void segment_closest_kernel(const S
     const size_t i3 = (size_t)i * 3;
     const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
     int spill[kMaxStack - kLdsStack];
-    PointStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    PointStack stack = query_stack(lds_stack, spill, p.stack_depth);
     // the best candidate so far by (d2, instance, tri_id); best_inst < 0 = none yet
     float best = 0.0f, bs = 0.0f, b1 = 0.0f, b2 = 0.0f;
     int32_t best_inst = -1, best_slot = 0, best_tid = 0, pops = 0;
@@ -2872,8 +2977,7 @@ __global__ __launch_bounds__(kPointBlock, 8) void triangle_closest_kernel(const 
     const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
     const int32_t skip = p.skip ? p.skip[i] : -1;
     int spill[kMaxStack - kLdsStack];
-    PointStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    PointStack stack = query_stack(lds_stack, spill, p.stack_depth);
     // the best candidate so far by (d2, instance, tri_id); best_inst < 0 = none yet
     float best = 0.0f, bq1 = 0.0f, bq2 = 0.0f, b1 = 0.0f, b2 = 0.0f;
     int32_t best_inst = -1, best_slot = 0, best_tid = 0, pops = 0;
@@ -3120,41 +3224,18 @@ __device__ __forceinline__ void xq_trace(const P& p, CrossStack& stack, V3 w, V3
         const XqRay r = xq_ray(in, w, d);
         if (r.zero) continue;                                   // (a zero d' counts nothing)
         const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
-        // (unordered / NaN boxes, or an origin beyond 2^60: no pruning in this instance)
-        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0 && r.omax <= 0x1p60f;
-        stack.sp = 0;
-        stack.push(kSentinel);
-        int32_t cur = in.root_ref, rem = -1;
-        do {
-            if (cur >= 0) {                                     // interior node: every child the ray may cross, no order
-                pops++;
-                const float4* rec = p.records + (size_t)cur * 4;
-                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-                const bool pa = !prune || xq_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, r);
-                const bool pb = !prune || xq_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, r);
-                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
-                if (pa && pb) stack.push(rb);
-                cur = pa ? ra : (pb ? rb : kNeedPop);
-            } else {                                            // one triangle of a leaf per iteration
-                const int32_t slot = cur & kSlotMask;
-                if (rem < 0) {
-                    rem = (cur >> kSlotBits) & 31;
-                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
-                }
-                if (rem > 0) {
-                    const float4* rec = p.records + (size_t)slot * 4;
-                    V3 a, ab, ac;
-                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
-                    const int sign = xq_triangle(r, a, ab, ac, tmax);
-                    count += sign != 0 ? 1 : 0;
-                    winding += sign;
-                }
-                rem--;
-                cur = rem > 0 ? cur + 1 : kNeedPop;
-                rem = rem > 0 ? rem : -1;
-            }
-            if (cur == kNeedPop) cur = stack.pop();
-        } while (cur != kSentinel);
+        // (an origin beyond 2^60: no pruning in this instance either); the child boxes the ray may cross
+        walk_unordered(p, stack, in, boxes_ordered(p, in) && r.omax <= 0x1p60f, pops,
+                       [&](float lx, float ly, float lz, float hx, float hy, float hz) {
+            return xq_box(lx, ly, lz, hx, hy, hz, s, r);
+        }, [&](int32_t, float4 t0, float4 t1, float4 t2) {
+            V3 a, ab, ac;
+            pq_triangle(t0, t1, t2, s, a, ab, ac);
+            const int sign = xq_triangle(r, a, ab, ac, tmax);
+            count += sign != 0 ? 1 : 0;
+            winding += sign;
+            return false;
+        });
     }
 }
 
@@ -3170,8 +3251,7 @@ __global__ __launch_bounds__(kCrossBlock, 8) void crossing_kernel(const CrossPar
     const size_t i3 = (size_t)i * 3;
     const V3 w = v3(p.org[i3], p.org[i3 + 1], p.org[i3 + 2]);
     int spill[kMaxStack - kLdsStack];
-    CrossStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    CrossStack stack = query_stack(lds_stack, spill, p.stack_depth);
     int32_t count = 0, winding = 0, pops = 0;
     if constexpr (!POINT) {
         const float tmax = p.tmax ? p.tmax[i] : __int_as_float(0x7f800000);
@@ -3207,8 +3287,7 @@ __global__ __launch_bounds__(kCrossBlock, 8) void segment_crossing_kernel(const 
     const float* g = p.segs + (size_t)i * 6;
     const V3 w = v3(g[0], g[1], g[2]);
     int spill[kMaxStack - kLdsStack];
-    CrossStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    CrossStack stack = query_stack(lds_stack, spill, p.stack_depth);
     int32_t count = 0, winding = 0, pops = 0;
     xq_trace(p, stack, w, v3(g[3] - w.x, g[4] - w.y, g[5] - w.z), 1.0f, count, winding, pops);
     if (p.crossings) p.crossings[i] = count;
@@ -3262,39 +3341,18 @@ __device__ __forceinline__ void xl_trace(const CrossListParams& p, CrossStack& s
         const XqRay r = xq_ray(in, v3(p.org[i3], p.org[i3 + 1], p.org[i3 + 2]), v3(p.dir[i3], p.dir[i3 + 1], p.dir[i3 + 2]));
         if (r.zero) continue;
         const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
-        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0 && r.omax <= 0x1p60f;
-        stack.sp = 0;
-        stack.push(kSentinel);
-        int32_t cur = in.root_ref, rem = -1;
-        do {
-            if (cur >= 0) {
-                const float4* rec = p.records + (size_t)cur * 4;
-                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-                const bool pa = !prune || xq_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, r);
-                const bool pb = !prune || xq_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, r);
-                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
-                if (pa && pb) stack.push(rb);
-                cur = pa ? ra : (pb ? rb : kNeedPop);
-            } else {
-                const int32_t slot = cur & kSlotMask;
-                if (rem < 0) {
-                    rem = (cur >> kSlotBits) & 31;
-                    if (rem == 31) rem = p.leaf_count[slot];
-                }
-                if (rem > 0) {
-                    const float4* rec = p.records + (size_t)slot * 4;
-                    V3 a, ab, ac;
-                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
-                    float t = 0.0f, tv = 0.0f, tw = 0.0f, det = 1.0f;
-                    const int sign = xq_triangle_uvw(r, a, ab, ac, tmax, t, tv, tw, det);
-                    if (sign != 0) hit(k, slot, t, tv, tw, det, sign);
-                }
-                rem--;
-                cur = rem > 0 ? cur + 1 : kNeedPop;
-                rem = rem > 0 ? rem : -1;
-            }
-            if (cur == kNeedPop) cur = stack.pop();
-        } while (cur != kSentinel);
+        int32_t pops = 0;                                       // (not reported)
+        walk_unordered(p, stack, in, boxes_ordered(p, in) && r.omax <= 0x1p60f, pops,
+                       [&](float lx, float ly, float lz, float hx, float hy, float hz) {
+            return xq_box(lx, ly, lz, hx, hy, hz, s, r);
+        }, [&](int32_t slot, float4 t0, float4 t1, float4 t2) {
+            V3 a, ab, ac;
+            pq_triangle(t0, t1, t2, s, a, ab, ac);
+            float t = 0.0f, tv = 0.0f, tw = 0.0f, det = 1.0f;
+            const int sign = xq_triangle_uvw(r, a, ab, ac, tmax, t, tv, tw, det);
+            if (sign != 0) hit(k, slot, t, tv, tw, det, sign);
+            return false;
+        });
     }
 }
 
@@ -3347,8 +3405,7 @@ __global__ __launch_bounds__(kCrossBlock, 8) void crossing_list_kernel(const Cro
     const size_t i3 = (size_t)i * 3;
     const float tmax = p.tmax ? p.tmax[i] : __int_as_float(0x7f800000);
     int spill[kMaxStack - kLdsStack];
-    CrossStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    CrossStack stack = query_stack(lds_stack, spill, p.stack_depth);
     int32_t total = 0, filled = 0;                              // (filled <= total: int32)
     if constexpr (!SELECT) {
         xl_trace(p, stack, i3, tmax, [&](int32_t k, int32_t slot, float t, float tv, float tw, float det, int sign) {
@@ -3575,8 +3632,7 @@ __global__ __launch_bounds__(kPointBlock, 8) void nearby_count_kernel(const Near
     if (i >= p.n) return;
     const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
     int spill[kMaxStack - kLdsStack];
-    PointStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    PointStack stack = query_stack(lds_stack, spill, p.stack_depth);
     int32_t total = 0;
     if (cut2 >= 0.0f)
         nb_trace(p, stack, (size_t)i * 3, [&] { return cut2; }, [&](int32_t, int32_t, float, float, float) { total++; });
@@ -3625,8 +3681,7 @@ __global__ __launch_bounds__(kPointBlock, 8) void nearby_list_kernel(const Nearb
     if (i >= p.n) return;
     const float cut2 = pq_cut2(p.max_distance ? p.max_distance[i] : __int_as_float(0x7f800000));
     int spill[kMaxStack - kLdsStack];
-    PointStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    PointStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const bool knn = !p.offsets && !p.count;
     float lim = cut2;
     int32_t total = 0, filled = 0, pops = 0;                    // (filled <= total: int32)
@@ -3852,8 +3907,7 @@ __global__ __launch_bounds__(kTriBlock, 8) void intersect_count_kernel(const Tri
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     int32_t total = 0;
     const int32_t pops = ti_trace(p, stack, i, false, [&](int32_t) { return true; }, [&](int32_t, int32_t, const TiHit&) {
         total++;
@@ -3877,8 +3931,7 @@ __global__ __launch_bounds__(kTriBlock, 8) void triangle_intersect_patch_kernel(
     if (i >= p.n) return;
     if (!COUNT && !clearance && within[i] != 0) return;         // (within alone, and the distance half has already said 1)
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     int32_t total = 0;
     ti_trace(p, stack, i, false, [&](int32_t) { return true; }, [&](int32_t, int32_t, const TiHit&) {
         total++;
@@ -3921,8 +3974,7 @@ __global__ __launch_bounds__(kTriBlock, 8) void intersect_list_kernel(const TriP
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const bool early = !p.offsets && !p.count;
     int32_t total = 0, filled = 0;                              // (filled <= total: int32)
     const int32_t pops = ti_trace(p, stack, i, p.segment != nullptr, [&](int32_t k) {
@@ -4119,8 +4171,7 @@ __global__ __launch_bounds__(kTriBlock, 8) void box_count_kernel(const BoxParams
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const float* B = p.boxes + (size_t)i * 6;
     int32_t total = 0;
     const int32_t pops = bx_trace(p, stack, v3(B[0], B[1], B[2]), v3(B[3], B[4], B[5]), [&](int32_t) { return true; },
@@ -4148,8 +4199,7 @@ __global__ __launch_bounds__(kTriBlock, 8) void box_grid_kernel(const BoxParams 
     const int32_t iz = (int32_t)((bxy / p.bricks[1]) * 4u + (t >> 4));
     if (ix >= p.dims[0] || iy >= p.dims[1] || iz >= p.dims[2]) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const V3 lo = v3(p.origin[0] + (float)ix * p.spacing[0], p.origin[1] + (float)iy * p.spacing[1], p.origin[2] + (float)iz * p.spacing[2]);
     const V3 hi = v3(p.origin[0] + (float)(ix + 1) * p.spacing[0], p.origin[1] + (float)(iy + 1) * p.spacing[1],
                      p.origin[2] + (float)(iz + 1) * p.spacing[2]);
@@ -4163,49 +4213,31 @@ __global__ __launch_bounds__(kTriBlock, 8) void box_grid_kernel(const BoxParams 
     if (p.any) p.any[cell] = total > 0 ? 1 : 0;
 }
 
-// A room's key at slot q as one number: (instance, triangle) compared as a pair (both >= 0 in a filled slot)
-__device__ __forceinline__ uint64_t bx_key(const BoxParams& p, size_t q)
-{
-    return ((uint64_t)(uint32_t)p.instance[q] << 32) | (uint64_t)(uint32_t)p.triangle[q];
-}
-__device__ __forceinline__ void bx_put(const BoxParams& p, size_t q, uint64_t key)
-{
-    p.instance[q] = (int32_t)(key >> 32);
-    p.triangle[q] = (int32_t)(uint32_t)key;
-}
-// `key` enters the max-heap of `size` slots at `start` from slot `pos` downwards: greater children move up until it fits
-__device__ __forceinline__ void bx_sift_down(const BoxParams& p, size_t start, uint64_t size, uint64_t pos, uint64_t key)
-{
-    for (;;) {
-        uint64_t child = 2 * pos + 1;
-        if (child >= size) break;
-        uint64_t ck = bx_key(p, start + (size_t)child);
-        if (child + 1 < size) {
-            const uint64_t c2 = bx_key(p, start + (size_t)child + 1);
-            if (c2 > ck) { ck = c2; child++; }
-        }
-        if (ck <= key) break;
-        bx_put(p, start + (size_t)pos, ck);
-        pos = child;
+// A box room's entry is its key alone: the (instance, triangle) of slot q
+struct BxItem { uint64_t key; };
+struct BxRoom {
+    const BoxParams& p;
+    __device__ __forceinline__ BxItem get(size_t q) const { return {pair_key(p.instance[q], p.triangle[q])}; }
+    __device__ __forceinline__ void put(size_t q, BxItem it) const
+    {
+        p.instance[q] = (int32_t)(it.key >> 32);
+        p.triangle[q] = (int32_t)(uint32_t)it.key;
     }
-    bx_put(p, start + (size_t)pos, key);
-}
+};
 
-// One traversal; the room is kept as a max-heap of its keys (instance, triangle) while pairs arrive -- lane-private, no atomics --
+// One traversal; the room is kept as the room heap of its keys (instance, triangle) while pairs arrive -- lane-private, no atomics --
 // and sorted in place at the end.  A box holds a volume's worth of triangles, so its lists are long where a query triangle's are
-// short: the heap takes a pair in O(log room) where intersect_list_kernel's shifting insertion takes O(room).  Until the room is full
-// a pair sifts up; a full room takes a pair only below its greatest key, the root, which leaves.  In fixed rooms without count the
-// traversal ends after the root's instance once the room is full: every later pair sorts after it (instances arrive in ascending
-// order).  Which keys stay does not depend on the order of arrival, so the rooms are the same bits with and without count and
-// whatever the tree.
+// short: the heap takes a pair in O(log room) where intersect_list_kernel's shifting insertion takes O(room).  In fixed rooms
+// without count the traversal ends after the root's instance once the room is full: every later pair sorts after it (instances
+// arrive in ascending order).  Which keys stay does not depend on the order of arrival, so the rooms are the same bits with and
+// without count and whatever the tree.
 __global__ __launch_bounds__(kTriBlock, 8) void box_list_kernel(const BoxParams p)
 {
     extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kTriBlock]
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const float* B = p.boxes + (size_t)i * 6;
     const bool early = !p.offsets && !p.count;
     int32_t total = 0;
@@ -4219,29 +4251,13 @@ __global__ __launch_bounds__(kTriBlock, 8) void box_list_kernel(const BoxParams 
         uint64_t room;
         xl_room(p, i, start, room);                             // (read again per pair: not held across the traversal)
         if (room == 0) return false;
-        const uint64_t key = ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)p.tri_id[slot];
-        if (filled < room) {                                    // sift up from the new last slot
-            uint64_t pos = filled++;
-            while (pos > 0) {
-                const uint64_t parent = (pos - 1) / 2, pk = bx_key(p, start + (size_t)parent);
-                if (pk >= key) break;
-                bx_put(p, start + (size_t)pos, pk);
-                pos = parent;
-            }
-            bx_put(p, start + (size_t)pos, key);
-        } else if (key < bx_key(p, start)) {                    // full: the root leaves
-            bx_sift_down(p, start, room, 0, key);
-        }
+        room_insert(BxRoom{p}, start, room, filled, BxItem{pair_key(k, p.tri_id[slot])});
         return false;
     });
     size_t start;
     uint64_t room;
     xl_room(p, i, start, room);
-    for (uint64_t end = filled; end > 1; end--) {               // heap -> ascending: the greatest key to the end, the rest a heap again
-        const uint64_t last = bx_key(p, start + (size_t)(end - 1));
-        bx_put(p, start + (size_t)(end - 1), bx_key(p, start));
-        bx_sift_down(p, start, end - 1, 0, last);
-    }
+    room_sort(BxRoom{p}, start, filled);
     for (uint64_t j = filled; j < room; j++) {                  // padding
         p.instance[start + (size_t)j] = -1;
         p.triangle[start + (size_t)j] = -1;
@@ -4368,42 +4384,18 @@ __device__ __forceinline__ int32_t sc_trace(const SecParams& p, TriStack& stack,
         const DevInstance& in = p.instances[k];
         const V3 q = sc_point(P, in), n = sc_normal(N, in);     // p' and n': all the node loop keeps of the plane
         const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
-        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
-        bool done = false;
-        stack.sp = 0;
-        stack.push(kSentinel);
-        int32_t cur = in.root_ref, rem = -1;
-        do {
-            if (cur >= 0) {                                     // interior node: every child that can hold both classes, no order
-                pops++;
-                const float4* rec = p.records + (size_t)cur * 4;
-                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-                const bool pa = !prune || sc_box(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, q, n);
-                const bool pb = !prune || sc_box(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, q, n);
-                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
-                if (pa && pb) stack.push(rb);
-                cur = pa ? ra : (pb ? rb : kNeedPop);
-            } else {                                            // one triangle of a leaf per iteration
-                const int32_t slot = cur & kSlotMask;
-                if (rem < 0) {
-                    rem = (cur >> kSlotBits) & 31;
-                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
-                }
-                if (rem > 0) {
-                    const float4* rec = p.records + (size_t)slot * 4;
-                    V3 a, ab, ac;
-                    pq_triangle(rec[0], rec[1], rec[2], s, a, ab, ac);
-                    const float ha = sc_height(n, q, a), hb = sc_height(n, q, a + ab), hc = sc_height(n, q, a + ac);
-                    const int above = (ha >= 0.0f) + (hb >= 0.0f) + (hc >= 0.0f), below = (ha < 0.0f) + (hb < 0.0f) + (hc < 0.0f);
-                    // step 5: all three classified (a NaN height is neither), one ABOVE at least and one BELOW
-                    if (above + below == 3 && above > 0 && below > 0 && pair(k, slot)) done = true;
-                }
-                rem--;
-                cur = rem > 0 ? cur + 1 : kNeedPop;
-                rem = rem > 0 ? rem : -1;
-            }
-            if (cur == kNeedPop) cur = stack.pop();
-        } while (cur != kSentinel && !done);
+        // the child boxes that can hold both classes
+        const bool done = walk_unordered(p, stack, in, boxes_ordered(p, in), pops,
+                                         [&](float lx, float ly, float lz, float hx, float hy, float hz) {
+            return sc_box(lx, ly, lz, hx, hy, hz, s, q, n);
+        }, [&](int32_t slot, float4 t0, float4 t1, float4 t2) {
+            V3 a, ab, ac;
+            pq_triangle(t0, t1, t2, s, a, ab, ac);
+            const float ha = sc_height(n, q, a), hb = sc_height(n, q, a + ab), hc = sc_height(n, q, a + ac);
+            const int above = (ha >= 0.0f) + (hb >= 0.0f) + (hc >= 0.0f), below = (ha < 0.0f) + (hb < 0.0f) + (hc < 0.0f);
+            // step 5: all three classified (a NaN height is neither), one ABOVE at least and one BELOW
+            return above + below == 3 && above > 0 && below > 0 && pair(k, slot);
+        });
         if (done) break;
     }
     return pops;
@@ -4418,8 +4410,7 @@ __global__ __launch_bounds__(kTriBlock, 8) void section_count_kernel(const SecPa
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const float* B = p.planes + (size_t)i * 6;
     int32_t total = 0;
     const int32_t pops = sc_trace(p, stack, v3(B[0], B[1], B[2]), v3(B[3], B[4], B[5]), [&](int32_t) { return true; },
@@ -4432,45 +4423,31 @@ __global__ __launch_bounds__(kTriBlock, 8) void section_count_kernel(const SecPa
     if (p.pops) p.pops[i] = pops;
 }
 
-// A room's entry while the heap is at work: the key (instance, triangle) as one number, as bx_key makes it, and the pair's record
-// slot, which travels with the key when segment or normal is wanted: they are computed from it once the room is sorted.  The slot
-// lives in the first word of the entry's segment (or, without segment, of its normal), inside the room.
+// A room's entry while the heap is at work: the key (instance, triangle) as one number and the pair's record slot, which travels
+// with the key when segment or normal is wanted: they are computed from it once the room is sorted.  The slot lives in the first
+// word of the entry's segment (or, without segment, of its normal), inside the room.
 struct ScItem { uint64_t key; int32_t slot; };
-__device__ __forceinline__ float* sc_aux(const SecParams& p, size_t q) { return p.segment ? p.segment + 6 * q : (p.normal ? p.normal + 3 * q : nullptr); }
-__device__ __forceinline__ ScItem sc_get(const SecParams& p, size_t q)
-{
-    ScItem it;
-    it.key = ((uint64_t)(uint32_t)p.instance[q] << 32) | (uint64_t)(uint32_t)p.triangle[q];
-    const float* aux = sc_aux(p, q);
-    it.slot = aux ? __float_as_int(*aux) : 0;
-    return it;
-}
-__device__ __forceinline__ void sc_put(const SecParams& p, size_t q, ScItem it)
-{
-    p.instance[q] = (int32_t)(it.key >> 32);
-    p.triangle[q] = (int32_t)(uint32_t)it.key;
-    float* aux = sc_aux(p, q);
-    if (aux) *aux = __int_as_float(it.slot);
-}
-// bx_sift_down with the slot travelling along
-__device__ __forceinline__ void sc_sift_down(const SecParams& p, size_t start, uint64_t size, uint64_t pos, ScItem it)
-{
-    for (;;) {
-        uint64_t child = 2 * pos + 1;
-        if (child >= size) break;
-        ScItem ci = sc_get(p, start + (size_t)child);
-        if (child + 1 < size) {
-            const ScItem c2 = sc_get(p, start + (size_t)child + 1);
-            if (c2.key > ci.key) { ci = c2; child++; }
-        }
-        if (ci.key <= it.key) break;
-        sc_put(p, start + (size_t)pos, ci);
-        pos = child;
+struct ScRoom {
+    const SecParams& p;
+    __device__ __forceinline__ float* aux(size_t q) const { return p.segment ? p.segment + 6 * q : (p.normal ? p.normal + 3 * q : nullptr); }
+    __device__ __forceinline__ ScItem get(size_t q) const
+    {
+        ScItem it;
+        it.key = pair_key(p.instance[q], p.triangle[q]);
+        const float* x = aux(q);
+        it.slot = x ? __float_as_int(*x) : 0;
+        return it;
     }
-    sc_put(p, start + (size_t)pos, it);
-}
+    __device__ __forceinline__ void put(size_t q, ScItem it) const
+    {
+        p.instance[q] = (int32_t)(it.key >> 32);
+        p.triangle[q] = (int32_t)(uint32_t)it.key;
+        float* x = aux(q);
+        if (x) *x = __int_as_float(it.slot);
+    }
+};
 
-// box_list_kernel's lane-private max-heap on (instance, triangle) and its early end for fixed rooms without count.  segment and normal
+// box_list_kernel's room heap on (instance, triangle) and its early end for fixed rooms without count.  segment and normal
 // depend on the plane, the instance and the record alone, and are written after the sort from the slot that travelled with each key:
 // the rooms are the same bits with and without count and whatever the tree.
 __global__ __launch_bounds__(kTriBlock, 8) void section_list_kernel(const SecParams p)
@@ -4479,8 +4456,7 @@ __global__ __launch_bounds__(kTriBlock, 8) void section_list_kernel(const SecPar
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const float* B = p.planes + (size_t)i * 6;
     const bool early = !p.offsets && !p.count;
     int32_t total = 0;
@@ -4494,37 +4470,18 @@ __global__ __launch_bounds__(kTriBlock, 8) void section_list_kernel(const SecPar
         uint64_t room;
         xl_room(p, i, start, room);                             // (read again per pair: not held across the traversal)
         if (room == 0) return false;
-        ScItem it;
-        it.key = ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)p.tri_id[slot];
-        it.slot = slot;
-        if (filled < room) {                                    // sift up from the new last slot
-            uint64_t pos = filled++;
-            while (pos > 0) {
-                const uint64_t parent = (pos - 1) / 2;
-                const ScItem pi = sc_get(p, start + (size_t)parent);
-                if (pi.key >= it.key) break;
-                sc_put(p, start + (size_t)pos, pi);
-                pos = parent;
-            }
-            sc_put(p, start + (size_t)pos, it);
-        } else if (it.key < sc_get(p, start).key) {             // full: the root leaves
-            sc_sift_down(p, start, room, 0, it);
-        }
+        room_insert(ScRoom{p}, start, room, filled, ScItem{pair_key(k, p.tri_id[slot]), slot});
         return false;
     });
     size_t start;
     uint64_t room;
     xl_room(p, i, start, room);
-    for (uint64_t end = filled; end > 1; end--) {               // heap -> ascending: the greatest key to the end, the rest a heap again
-        const ScItem last = sc_get(p, start + (size_t)(end - 1));
-        sc_put(p, start + (size_t)(end - 1), sc_get(p, start));
-        sc_sift_down(p, start, end - 1, 0, last);
-    }
+    room_sort(ScRoom{p}, start, filled);
     if (p.segment || p.normal) {
         const V3 P = v3(B[0], B[1], B[2]), N = v3(B[3], B[4], B[5]);
         for (uint64_t j = 0; j < filled; j++) {                 // the sorted entries: segment and normal from the slot
             const size_t q = start + (size_t)j;
-            const int32_t slot = sc_get(p, q).slot;
+            const int32_t slot = ScRoom{p}.get(q).slot;
             const DevInstance& in = p.instances[p.instance[q]];
             if (p.segment) {
                 const ScSeg sg = sc_segment(p.records, in, slot, P, N);
@@ -4721,8 +4678,7 @@ __global__ __launch_bounds__(kTriBlock, rg_waves(KT)) void region_count_kernel(c
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const float* R = p.regions + (size_t)i * (size_t)(6 * p.planes);
     int32_t total = 0, inside = 0;
     const int32_t pops = rg_trace<KT>(p, stack, R, [&](int32_t) { return true; }, [&](int32_t, int32_t, bool in) {
@@ -4740,40 +4696,26 @@ __global__ __launch_bounds__(kTriBlock, rg_waves(KT)) void region_count_kernel(c
 // the key in the entry's own inside slot when that field is wanted, and the pair's record slot, which travels in the entry's normal
 // (its first word) when normal is wanted, as section_list_kernel carries it.
 struct RgItem { uint64_t key; int32_t slot; uint8_t flag; };
-__device__ __forceinline__ RgItem rg_get(const RegParams& p, size_t q)
-{
-    RgItem it;
-    it.key = ((uint64_t)(uint32_t)p.instance[q] << 32) | (uint64_t)(uint32_t)p.triangle[q];
-    it.slot = p.normal ? __float_as_int(p.normal[3 * q]) : 0;
-    it.flag = p.flag ? p.flag[q] : 0;
-    return it;
-}
-__device__ __forceinline__ void rg_put(const RegParams& p, size_t q, RgItem it)
-{
-    p.instance[q] = (int32_t)(it.key >> 32);
-    p.triangle[q] = (int32_t)(uint32_t)it.key;
-    if (p.normal) p.normal[3 * q] = __int_as_float(it.slot);
-    if (p.flag) p.flag[q] = it.flag;
-}
-// bx_sift_down with the flag and the slot travelling along
-__device__ __forceinline__ void rg_sift_down(const RegParams& p, size_t start, uint64_t size, uint64_t pos, RgItem it)
-{
-    for (;;) {
-        uint64_t child = 2 * pos + 1;
-        if (child >= size) break;
-        RgItem ci = rg_get(p, start + (size_t)child);
-        if (child + 1 < size) {
-            const RgItem c2 = rg_get(p, start + (size_t)child + 1);
-            if (c2.key > ci.key) { ci = c2; child++; }
-        }
-        if (ci.key <= it.key) break;
-        rg_put(p, start + (size_t)pos, ci);
-        pos = child;
+struct RgRoom {
+    const RegParams& p;
+    __device__ __forceinline__ RgItem get(size_t q) const
+    {
+        RgItem it;
+        it.key = pair_key(p.instance[q], p.triangle[q]);
+        it.slot = p.normal ? __float_as_int(p.normal[3 * q]) : 0;
+        it.flag = p.flag ? p.flag[q] : 0;
+        return it;
     }
-    rg_put(p, start + (size_t)pos, it);
-}
+    __device__ __forceinline__ void put(size_t q, RgItem it) const
+    {
+        p.instance[q] = (int32_t)(it.key >> 32);
+        p.triangle[q] = (int32_t)(uint32_t)it.key;
+        if (p.normal) p.normal[3 * q] = __int_as_float(it.slot);
+        if (p.flag) p.flag[q] = it.flag;
+    }
+};
 
-// box_list_kernel's lane-private max-heap on (instance, triangle) and its early end for fixed rooms without count.  A pair's inside
+// box_list_kernel's room heap on (instance, triangle) and its early end for fixed rooms without count.  A pair's inside
 // flag depends on the region, the instance and the record alone and travels with its key; normal is written after the sort from the
 // slot that travelled with it: the rooms are the same bits with and without count and whatever the tree.
 template <int KT>
@@ -4783,8 +4725,7 @@ __global__ __launch_bounds__(kTriBlock, rg_waves(KT)) void region_list_kernel(co
     const int32_t i = (int32_t)blockIdx.x * kTriBlock + (int32_t)threadIdx.x;       // (< n <= INT32_MAX: no overflow)
     if (i >= p.n) return;
     int spill[kMaxStack - kLdsStack];
-    TriStack stack;
-    stack.lds = (lds_int*)lds_stack + threadIdx.x; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
+    TriStack stack = query_stack(lds_stack, spill, p.stack_depth);
     const float* R = p.regions + (size_t)i * (size_t)(6 * p.planes);
     const bool early = !p.offsets && !p.count;
     int32_t total = 0;
@@ -4798,37 +4739,17 @@ __global__ __launch_bounds__(kTriBlock, rg_waves(KT)) void region_list_kernel(co
         uint64_t room;
         xl_room(p, i, start, room);                             // (read again per pair: not held across the traversal)
         if (room == 0) return false;
-        RgItem it;
-        it.key = ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)p.tri_id[slot];
-        it.slot = slot;
-        it.flag = in ? 1 : 0;
-        if (filled < room) {                                    // sift up from the new last slot
-            uint64_t pos = filled++;
-            while (pos > 0) {
-                const uint64_t parent = (pos - 1) / 2;
-                const RgItem pi = rg_get(p, start + (size_t)parent);
-                if (pi.key >= it.key) break;
-                rg_put(p, start + (size_t)pos, pi);
-                pos = parent;
-            }
-            rg_put(p, start + (size_t)pos, it);
-        } else if (it.key < rg_get(p, start).key) {             // full: the root leaves
-            rg_sift_down(p, start, room, 0, it);
-        }
+        room_insert(RgRoom{p}, start, room, filled, RgItem{pair_key(k, p.tri_id[slot]), slot, (uint8_t)(in ? 1 : 0)});
         return false;
     });
     size_t start;
     uint64_t room;
     xl_room(p, i, start, room);
-    for (uint64_t end = filled; end > 1; end--) {               // heap -> ascending: the greatest key to the end, the rest a heap again
-        const RgItem last = rg_get(p, start + (size_t)(end - 1));
-        rg_put(p, start + (size_t)(end - 1), rg_get(p, start));
-        rg_sift_down(p, start, end - 1, 0, last);
-    }
+    room_sort(RgRoom{p}, start, filled);
     if (p.normal) {
         for (uint64_t j = 0; j < filled; j++) {                 // the sorted entries: normal from the slot
             const size_t q = start + (size_t)j;
-            const V3 nn = pq_normal(p, p.instances[p.instance[q]], rg_get(p, q).slot);
+            const V3 nn = pq_normal(p, p.instances[p.instance[q]], RgRoom{p}.get(q).slot);
             p.normal[3 * q] = nn.x; p.normal[3 * q + 1] = nn.y; p.normal[3 * q + 2] = nn.z;
         }
     }

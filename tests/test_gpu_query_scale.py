@@ -439,8 +439,8 @@ def _csr_boxes():
 
 @pytest.mark.parametrize("base", [2 ** 31 + 5, 2 ** 32 + 5])
 def test_box_csr_rooms_beyond_32_bits(rt, stack, base):
-    """test_csr_rooms_beyond_32_bits for rt_list_in_boxes, whose rooms are max-heaps with 64-bit slot arithmetic of their own (bx_key,
-    bx_put, bx_sift_down, the final heap sort): 400 boxes on the quad stack with hand-made offsets base + cumsum(room), counted in
+    """test_csr_rooms_beyond_32_bits for rt_list_in_boxes, whose rooms are max-heaps with 64-bit slot arithmetic of their own (BxRoom's
+    get and put, room_insert, room_sift_down, room_sort): 400 boxes on the quad stack with hand-made offsets base + cumsum(room), counted in
     int32 slots, rooms below, at and above each count (two deep heaps at half their count, so most arrivals replace the root).  The
     lists run to 1200 keys.  Both key arrays' windows around the rooms equal the shim's rooms, guard words 64 either side included,
     and the first 4096 slots of each array (where a start cut to 32 bits would land) keep their guards.  count equals the shim's."""
@@ -580,8 +580,8 @@ def _csr_planes():
                                          (("segment",), -(-2 ** 32 // 6) + 5)],
                          ids=["keys-2^31", "keys-2^32", "normal-2^32/3", "segment-2^32/6"])
 def test_section_csr_rooms_at_large_slots(rt, stack, fields, base):
-    """test_box_csr_rooms_beyond_32_bits for rt_list_sections, whose heap has slot arithmetic of its own: sc_get, sc_put and
-    sc_sift_down index segment + 6 * q and normal + 3 * q, and the pair's record slot travels through the heap in the first word of
+    """test_box_csr_rooms_beyond_32_bits for rt_list_sections, whose heap has slot arithmetic of its own: ScRoom's get and put
+    (under room_insert, room_sift_down and room_sort) index segment + 6 * q and normal + 3 * q, and the pair's record slot travels through the heap in the first word of
     the entry's segment (of its normal when no segment is asked for).  400 planes on the quad stack with hand-made offsets base +
     cumsum(room), counted in slots, rooms below, at and above each count (two deep heaps of 400 pairs at half their count, so most
     arrivals replace the root and sift a long way with their slot); the lists run to 1200 entries.  With the keys alone the base is
@@ -590,7 +590,7 @@ def test_section_csr_rooms_at_large_slots(rt, stack, fields, base):
     around the rooms equals the shim's rooms, guard words of 64 slots either side included, and the first W * 4096 words (where a
     start cut to 32 bits, or a product 3 * q or 6 * q taken in 32 bits, would land: W * base mod 2^32 is 17 and 32) keep their
     guard.  Float fields are compared as int32 words.  count equals the shim's.  (Every quad has the normal (0, 0, 1), so the normal
-    case shows where the words go and no more; a slot that the sift-up or sc_sift_down leaves behind shows in the segment case, whose
+    case shows where the words go and no more; a slot that room_insert's sift-up or room_sift_down leaves behind shows in the segment case, whose
     segments differ from triangle to triangle.)"""
     import torch
     planes, rng = _csr_planes()

@@ -153,6 +153,28 @@ def _check(sp, so, regions, where="", ms=(1, 3, 64)):
     return ref
 
 
+def test_full_traversals_visit_the_same_nodes(rt, orc, scenes, blob5k):
+    """The count call, the CSR list call and the fixed-room list call with count all visit every pair of every instance, so their
+    pops are equal element-wise (one full wave and a single-lane wave)."""
+    desc = sd.multi_instance_scene(scenes, blob5k)
+    so = desc.build_oracle(orc)
+    sp = _product(rt, desc)
+    try:
+        rng = np.random.default_rng(65)
+        box8 = _flat(families(rt, rng, orc.oracle(), desc)[8])                 # (40 boxes cut by two more planes: some twice)
+        box8 = np.ascontiguousarray(box8[rng.choice(len(box8), 65, replace=len(box8) < 65)])
+        for K in (2, 4, 6, 8):                                  # every plane capacity of the kernels: a region's first K planes are a region
+            regions = np.ascontiguousarray(box8[:, :K])
+            c = sp.count_in_regions(regions, outputs=("count", "pops"))
+            assert (c["count"] > 3).any() and c["pops"].max() > 0, K
+            _eq(sp.list_in_regions(regions, outputs=FIELDS + ("pops",))["pops"], c["pops"], "K=%d pops(CSR list) == pops(count)" % K)
+            _eq(sp.list_in_regions(regions, max_hits=3, outputs=FIELDS + ("count", "pops"))["pops"], c["pops"],
+                "K=%d pops(M=3 with count) == pops(count)" % K)
+    finally:
+        sp.close()
+        so.close()
+
+
 @pytest.mark.parametrize("name", ["c1", "multi", "demo", "deep"])
 def test_library_scenes_equal_oracle(rt, orc, scenes, blob5k, demo_objs, name):
     desc, _cam = _library_scene(name, scenes, blob5k, demo_objs)

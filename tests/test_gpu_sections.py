@@ -114,6 +114,25 @@ def _check(sp, so, planes, where="", ks=(1, 3, 64)):
     return ref
 
 
+def test_full_traversals_visit_the_same_nodes(rt, orc, scenes, blob5k):
+    """The count call, the CSR list call and the fixed-room list call with count all visit every pair of every instance, so their
+    pops are equal element-wise (one full wave and a single-lane wave)."""
+    desc = sd.multi_instance_scene(scenes, blob5k)
+    so = desc.build_oracle(orc)
+    sp = _product(rt, desc)
+    try:
+        rng = np.random.default_rng(65)
+        planes = _flat(families(rng, orc.oracle(), desc))
+        planes = np.ascontiguousarray(planes[rng.choice(len(planes), 65, replace=False)])
+        c = sp.count_sections(planes, outputs=("count", "pops"))
+        assert (c["count"] > 3).any() and c["pops"].max() > 0
+        _eq(sp.list_sections(planes, outputs=FIELDS + ("pops",))["pops"], c["pops"], "pops(CSR list) == pops(count)")
+        _eq(sp.list_sections(planes, max_hits=3, outputs=FIELDS + ("count", "pops"))["pops"], c["pops"], "pops(K=3 with count) == pops(count)")
+    finally:
+        sp.close()
+        so.close()
+
+
 @pytest.mark.parametrize("name", ["c1", "multi", "demo", "deep"])
 def test_library_scenes_equal_oracle(rt, orc, scenes, blob5k, demo_objs, name):
     desc, _cam = _library_scene(name, scenes, blob5k, demo_objs)
