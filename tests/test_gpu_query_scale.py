@@ -1,15 +1,23 @@
 """What the query families share, at the sizes where it can go wrong (the arithmetic of each family is test_gpu_crossing_list.py's,
-test_gpu_nearby.py's, test_gpu_tri_intersect.py's, test_gpu_boxes.py's and test_gpu_sections.py's business): the CSR scan behind the
-five *_offsets calls (crossing, nearby, intersecting, box, section) at its block edges and on its three-level path, totals and room
-positions past 2^31 and 2^32, the box list's heap rooms at slots past 2^31 and 2^32, the section list's heap rooms where the slot
-times the width of a segment or a normal passes 2^32 and where the slot itself does, occupancy grids that need the grid kernel's
-second launch row and its limit of 2^24 cells on an axis, and every query kernel with a partly filled last workgroup on the deep
-scene.  The C-ABI is called directly on torch buffers: the Python wrappers would allocate `total` rows.
+test_gpu_nearby.py's, test_gpu_tri_intersect.py's, test_gpu_boxes.py's, test_gpu_sections.py's and test_gpu_regions.py's business): the
+CSR scan behind the six *_offsets calls (crossing, nearby, intersecting, box, section, region) at its block edges and on its three-level
+path, totals and room positions past 2^31 and 2^32, the box list's heap rooms at slots past 2^31 and 2^32, the section list's heap
+rooms where the slot times the width of a segment or a normal passes 2^32 and where the slot itself does, the region list's heap rooms
+where the slot -- which is also the byte index of the one-byte inside flag -- passes 2^31 and 2^32 and where 3 * slot passes 2^32,
+occupancy grids that need the grid kernel's second launch row and its limit of 2^24 cells on an axis, and every query kernel with a
+partly filled last workgroup on the deep scene.  The C-ABI is called directly on torch buffers: the Python wrappers would allocate
+`total` rows.
+
+The region family adds: rt_region_offsets, the only *_offsets call with an extra argument (planes_per_region) and a dispatch over four
+plane capacities in front of the scan, at K = 6 on the block edges and at K = 3 (the capacity-4 kernel with a plane unused) on the
+three-level path; and rt_list_in_regions' rooms on a quad stack with half of its quads' windings reversed, so that the inside flag and
+the sign of the normal both change from entry to entry along a list and a flag or a record slot that the heap leaves behind shows.
 
 Every offsets check compares with np.concatenate([[0], np.cumsum(counts)]) of the CPU shims' counts (crossing_oracle, nearby_oracle,
-tri_intersect_oracle, box_oracle, section_oracle), never with the library's own counts.  Every buffer a kernel may write is allocated at its full
-size; the large cases read back small windows only.  Totals beyond 2^32 are not repeated for boxes: the scan and its 64-bit sums are
-one piece of code for all five families, tested through rt_crossing_offsets below."""
+tri_intersect_oracle, box_oracle, section_oracle, region_oracle), never with the library's own counts.  Every buffer a kernel may write
+is allocated at its full size; the large cases read back small windows only.  Totals beyond 2^32 are not repeated for boxes: the scan
+and its 64-bit sums are one piece of code for all six families, tested through rt_crossing_offsets below.  The builders of the region
+inputs need no GPU: tests/test_query_scale_inputs_host.py holds them to the shim in every ordinary run."""
 import ctypes as C
 
 import numpy as np
@@ -22,6 +30,7 @@ import nearby_oracle as nb
 import point_oracle
 import query_points as qp
 import ray_oracle
+import region_oracle as ro
 import scene_defs as sd
 import section_oracle as sc
 import tri_intersect_oracle as ti
@@ -34,7 +43,7 @@ F32 = np.float32
 SCAN_BLOCK = 1024                                               # elements per block of the scan over n + 1 offsets (kScanBlock)
 GUARD = 0x5A
 GUARD64 = int.from_bytes(bytes([GUARD]) * 8, "little")
-FAMILIES = ("crossing", "nearby", "intersecting", "box", "section")
+FAMILIES = ("crossing", "nearby", "intersecting", "box", "section", "region")
 
 
 def _cumsum(counts):
@@ -48,14 +57,23 @@ def _block_totals(counts):
     return c.reshape(-1, SCAN_BLOCK).sum(axis=1)
 
 
-def _ws_bytes(h, family, n):
+def _planes_of(family, q):
+    """planes_per_region of a region pool, which carries its K in its shape [n, K, 2, 3]; None for every other family"""
+    return int(q[0].shape[1]) if family == "region" else None
+
+
+def _ws_bytes(h, family, n, planes_per_region=None):
+    """rt_<family>_offsets_workspace_bytes(n); a region's workspace holds one count per region whatever its planes_per_region"""
+    assert (planes_per_region is not None) == (family == "region")
     return int(getattr(h, "rt_%s_offsets_workspace_bytes" % family)(n))
 
 
-def _call_offsets(h, family, handle, q, n, off, ws, ws_bytes):
+def _call_offsets(h, family, handle, q, n, off, ws, ws_bytes, planes_per_region=None):
     """rt_<family>_offsets on device pointers, synchronous on the NULL stream; q: the family's two query arrays (the second may be
-    None)"""
+    None); planes_per_region: for the region family alone"""
     a, b = q[0].data_ptr(), None if q[1] is None else q[1].data_ptr()
+    if family == "region":
+        return h.rt_region_offsets(handle, a, n, planes_per_region, off, ws, ws_bytes, None, 1)
     if family == "crossing":
         return h.rt_crossing_offsets(handle, a, b, None, n, off, ws, ws_bytes, None, 1)
     if family == "nearby":
@@ -75,10 +93,10 @@ def _up(arrays):
 class _Offsets:
     """Guarded buffers for one n: offsets int64 [n + 1] with 8 guard words behind, the workspace with 256 guard bytes behind"""
 
-    def __init__(self, h, family, n):
+    def __init__(self, h, family, n, planes_per_region=None):
         import torch
-        self.h, self.family, self.n = h, family, n
-        self.ws_bytes = _ws_bytes(h, family, n)
+        self.h, self.family, self.n, self.planes = h, family, n, planes_per_region
+        self.ws_bytes = _ws_bytes(h, family, n, planes_per_region)
         self.off = torch.full((n + 1 + 8,), GUARD64, dtype=torch.int64, device="cuda")
         self.ws = torch.full((self.ws_bytes + 256,), GUARD, dtype=torch.uint8, device="cuda")
 
@@ -86,7 +104,8 @@ class _Offsets:
         """one call -> the offsets [n + 1]; the guards behind the offsets and behind the workspace are checked"""
         import torch
         torch.cuda.synchronize()
-        rc = _call_offsets(self.h, self.family, handle, q, self.n, self.off.data_ptr(), self.ws.data_ptr(), self.ws_bytes)
+        assert _planes_of(self.family, q) == self.planes
+        rc = _call_offsets(self.h, self.family, handle, q, self.n, self.off.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self.planes)
         assert rc == 0, (where, rc)
         got = self.off.cpu().numpy()
         assert (got[self.n + 1:] == GUARD64).all(), "%s: the words behind offsets[n] were written: %s" % (where, got[self.n + 1:])
@@ -135,20 +154,42 @@ def deep(rt, orc):
     p.close()
 
 
+def _stack_tris(o_, flipped=False):
+    """test_gpu_crossing_list.test_thousand_crossings_sorted's 1200 parallel quads as 2400 triangle records in shuffled order: quad j of
+    the list lies at z = zs[j].  flipped: a random half of the quads (drawn from a generator of its own: the order stays what it was)
+    have both triangles' windings reversed, so their normals point down; the vertices, and with them every count, are unchanged.
+    -> (records [2400, ...], zs [1200], down [1200] bool)"""
+    rng = np.random.default_rng(3)
+    zs = rng.permutation(1200).astype(F32) * F32(0.01)
+    down = np.random.default_rng(109).random(1200) < 0.5 if flipped else np.zeros(1200, bool)
+    tris = []
+    for z, rev in zip(zs, down):
+        for f in ((0, 1, 2), (0, 2, 3)):
+            v = np.array([(0, 0, z), (1, 0, z), (1, 1, z), (0, 1, z)], F32)[list(f[::-1] if rev else f)]
+            tris.append(np.asarray(o_.tri_from_vertices(v.ravel()), F32))
+    return np.stack(tris), zs, down
+
+
+def _stack_desc(o_, flipped=False):
+    """the quads as two coincident instances"""
+    inst = (0, 0, (0.0,) * 6, (1.0, 1.0, 1.0))
+    return sd.SceneDesc([((1.0, 1.0, 1.0), None)], [("tris", _stack_tris(o_, flipped)[0])], [inst, inst])
+
+
 @pytest.fixture(scope="module")
 def stack(rt, orc):
     """test_gpu_crossing_list.test_thousand_crossings_sorted's 1200 parallel quads (2400 triangles, in shuffled order), as two
     coincident instances: a ray along z crosses one triangle of every quad of both, about 2400 crossings"""
-    o_ = orc.oracle()
-    rng = np.random.default_rng(3)
-    zs = rng.permutation(1200).astype(F32) * F32(0.01)
-    tris = []
-    for z in zs:
-        for f in ((0, 1, 2), (0, 2, 3)):
-            v = np.array([(0, 0, z), (1, 0, z), (1, 1, z), (0, 1, z)], F32)[list(f)]
-            tris.append(np.asarray(o_.tri_from_vertices(v.ravel()), F32))
-    inst = (0, 0, (0.0,) * 6, (1.0, 1.0, 1.0))
-    p = _Pair(rt, orc, sd.SceneDesc([((1.0, 1.0, 1.0), None)], [("tris", np.stack(tris))], [inst, inst]))
+    p = _Pair(rt, orc, _stack_desc(orc.oracle()))
+    yield p
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def flipstack(rt, orc):
+    """the same stack with the winding of a random half of its quads reversed: the world normals are (0, 0, +-c) and the sign changes
+    about 300 times along a list of 1200 entries, so an entry that ends up with another entry's record slot shows in `normal`"""
+    p = _Pair(rt, orc, _stack_desc(orc.oracle(), flipped=True))
     yield p
     p.close()
 
@@ -157,8 +198,30 @@ def stack(rt, orc):
 POOL = 2049
 
 
+def _obb_regions(rt, rng, centres, size):
+    """K = 6 oriented boxes: random frames, edges of 0.4 to 1 times `size`"""
+    m = len(centres)
+    q = np.stack([np.linalg.qr(rng.normal(size=(3, 3)))[0] for _ in range(m)])
+    half = 0.5 * size[:, None] * rng.uniform(0.4, 1.0, (m, 3))
+    return rt.regions_from_obbs(np.ascontiguousarray(centres, F32), np.ascontiguousarray(q, F32), np.ascontiguousarray(half, F32))
+
+
+def _region_pool(rt, lo, hi):
+    """POOL K = 6 regions for a scene whose box is lo..hi: oriented boxes of 1e-3 to 0.6 of the diagonal in and around the box (the
+    large ones hold hundreds of pairs, most small ones none), a fifth of them far outside -> [POOL, 6, 2, 3] float32"""
+    rng = np.random.default_rng(107)
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    span, diag = np.maximum(hi - lo, 1e-3), float(np.linalg.norm(hi - lo))
+    c = lo + span * rng.uniform(-0.1, 1.1, (POOL, 3))
+    size = diag * 10.0 ** rng.uniform(-3, np.log10(0.6), POOL)
+    u = rng.normal(size=(POOL, 3))
+    far = rng.random(POOL) < 0.2
+    c[far] = ((lo + hi) / 2 + u / np.linalg.norm(u, axis=1, keepdims=True) * diag * rng.uniform(1.5, 4, (POOL, 1)))[far]
+    return np.ascontiguousarray(_obb_regions(rt, rng, c, size), F32)
+
+
 @pytest.fixture(scope="module")
-def pools(orc, multi):
+def pools(rt, orc, multi):
     """Per family: POOL queries on the multi-instance scene (hits and misses mixed) with the shim's counts, computed once, and the
     indices of the queries with a count above 0"""
     rng = np.random.default_rng(41)
@@ -185,7 +248,10 @@ def pools(orc, multi):
            "intersecting": ((tris, None), ti.count_intersecting(multi.so, tris)),
            "box": ((boxes, None), bo.count_in_boxes(multi.so, boxes)),
            "section": ((planes, None), sc.count_sections(multi.so, planes))}
+    regions = _region_pool(rt, lo, hi)
+    out["region"] = ((regions, None), ro.count_in_regions(multi.so, regions)["count"])
     assert out["section"][1].max() > 64, out["section"][1].max()
+    assert out["region"][1].max() > 64 and regions.shape == (POOL, 6, 2, 3), out["region"][1].max()
     for family, (_q, c) in out.items():
         assert (c > 0).sum() >= 16 and (c == 0).sum() >= 16, (family, int((c > 0).sum()))
     return out
@@ -213,7 +279,7 @@ def test_offsets_at_scan_block_edges(rt, multi, pools, family, n):
     ref = _cumsum(counts)
     last = (n - 1) // SCAN_BLOCK * SCAN_BLOCK                  # the last scan block that holds a count
     assert counts[-1] > 0 and counts[last:].sum() > 0 and ref[-1] > ref[last]
-    buf = _Offsets(h, family, n)
+    buf = _Offsets(h, family, n, _planes_of(family, q))
     got = buf.run(multi.handle, _up(q), "%s n=%d" % (family, n))
     _same_offsets(got, ref, "%s n=%d" % (family, n))
     rq = tuple(None if a is None else a[::-1].copy() for a in q)
@@ -223,6 +289,15 @@ def test_offsets_at_scan_block_edges(rt, multi, pools, family, n):
 
 # ---- B2: the three-level scan --------------------------------------------------------------------------------------------------
 DISTINCT = 4096
+
+
+def _cube_corners():
+    """DISTINCT distinct K = 3 regions around the unit cube: the corner of three random half-spaces through one point in or near the
+    cube -> [DISTINCT, 3, 2, 3] float32.  K = 3 runs the capacity-4 kernels with one plane unused."""
+    rng = np.random.default_rng(113)
+    p = rng.uniform(-0.5, 1.5, (DISTINCT, 1, 3))
+    u = rng.normal(size=(DISTINCT, 3, 3))
+    return np.ascontiguousarray(np.stack([np.broadcast_to(p, u.shape), u / np.linalg.norm(u, axis=2, keepdims=True)], axis=2), F32)
 
 
 @pytest.fixture(scope="module")
@@ -246,7 +321,8 @@ def cube_queries(cube):
             "nearby": ((pts, md), nb.count_nearby(cube.so, pts, md)),
             "intersecting": ((tris, None), ti.count_intersecting(cube.so, tris)),
             "box": ((boxes, None), bo.count_in_boxes(cube.so, boxes)),
-            "section": ((planes, None), sc.count_sections(cube.so, planes))}
+            "section": ((planes, None), sc.count_sections(cube.so, planes)),
+            "region": ((_cube_corners(), None), ro.count_in_regions(cube.so, _cube_corners())["count"])}
 
 
 def _tiled(pool, n):
@@ -264,7 +340,7 @@ def _three_levels(rt, cube, cube_queries, family, n):
     totals = _block_totals(counts)
     assert len(np.unique(totals[:-1])) >= 2 and len(totals) > SCAN_BLOCK, (family, np.unique(totals))
     ref = _cumsum(counts)
-    got = _Offsets(h, family, n).run(cube.handle, _up(q), "%s n=%d" % (family, n))
+    got = _Offsets(h, family, n, _planes_of(family, q)).run(cube.handle, _up(q), "%s n=%d" % (family, n))
     _same_offsets(got, ref, "%s n=%d" % (family, n))
 
 
@@ -284,10 +360,10 @@ def test_three_level_scan_crossing(rt, cube, cube_queries, n):
     _same_offsets(got, _cumsum(counts), "crossing n=%d" % n)
 
 
-@pytest.mark.parametrize("family", ["nearby", "intersecting", "box", "section"])
+@pytest.mark.parametrize("family", ["nearby", "intersecting", "box", "section", "region"])
 def test_three_level_scan_other_families(rt, cube, cube_queries, family):
-    """The same at n = 2^20 + 1 through rt_nearby_offsets, rt_intersecting_offsets, rt_box_offsets and rt_section_offsets: one scan, but
-    each family's own count launch"""
+    """The same at n = 2^20 + 1 through rt_nearby_offsets, rt_intersecting_offsets, rt_box_offsets, rt_section_offsets and
+    rt_region_offsets: one scan, but each family's own count launch (the regions' with K = 3 planes, one below its kernel's capacity)"""
     _three_levels(rt, cube, cube_queries, family, 2 ** 20 + 1)
 
 
@@ -696,6 +772,255 @@ def test_section_fixed_rooms_at_large_slots(rt, stack, fields, n):
                     room = bufs[k][i * w:(i + 1) * w].cpu().numpy()
                     assert (room == pad).all(), "%s of room %d (a plane without pairs), %s: %d words are not padding" % (
                         k, i, at, int((room != pad).sum()))
+            if with_count:
+                got = cnt.cpu().numpy()
+                _eq(got[-64:], c, "count of the last 64")
+                assert (got[:-64] == 0).all()
+    finally:
+        del bufs
+        torch.cuda.empty_cache()
+
+
+# ---- B4e: the region list's heap rooms where the slot (the flag's byte index) passes 2^31 and 2^32 and where 3 * slot passes 2^32 ------
+RG_WIDTH = dict(instance=1, triangle=1, inside=1, normal=3)     # elements per slot: int32 words, the flag's bytes
+RG_FILL = dict(instance=GUARD32, triangle=GUARD32, inside=GUARD, normal=GUARDF)
+RG_PAD = dict(instance=-1, triangle=-1, inside=0, normal=0)     # (as words: the floats' padding is 0.0)
+FAR_REGION = np.stack([FAR_PLANE, FAR_PLANE])
+
+
+def _wedge(a, m, b):
+    """the K = 2 region above _tilt(a, m) and below z = b * 0.01 + 0.005, half a spacing above quad b (a <= b, 1 <= m <= b - a + 1): it
+    touches the quads a..b, both triangles in both instances, and holds the quads a + m..b whole"""
+    assert 0 <= a <= b and 1 <= m <= b - a + 1
+    return np.stack([_tilt(a, m), np.array([[0.5, 0.5, b * 0.01 + 0.005], [0, 0, -1]], F32)])
+
+
+def _wedge_counts(a, m, b):
+    """-> (count, inside) of _wedge(a, m, b) on the stack, in closed form"""
+    return 4 * (b - a + 1), 4 * (b - a - m + 1)
+
+
+def _wedges(specs):
+    """(a, m, b) rows -> (regions [len, 2, 2, 3], count, inside)"""
+    c = np.array([_wedge_counts(*s) for s in specs], np.int32).reshape(-1, 2)
+    return np.stack([_wedge(*s) for s in specs]), c[:, 0], c[:, 1]
+
+
+def _csr_regions():
+    """400 K = 2 regions on the quad stack, shuffled: one wedge of 1200 pairs, two of 400, four of 100 (half of the pairs of the large
+    ones are whole inside, 60 of the 100), 150 without pairs (75 far off, 74 whose two half-spaces z >= z1 and z <= z0 < z1 face
+    apart, and the largest wedge with a zero normal in its second plane) and 243 thin wedges over one to three quads -> (regions,
+    count and inside in closed form, rng)"""
+    rng = np.random.default_rng(127)
+    big = [(100, 150, 399), (500, 50, 599), (700, 50, 799)] + [(a, 10, a + 24) for a in (0, 450, 900, 1175)]
+    thin = [(int(a), int(rng.integers(1, k + 1)), int(a + k - 1)) for k in rng.choice([1, 2, 3], 243, p=[0.6, 0.3, 0.1])
+            for a in [rng.integers(0, QUADS - k + 1)]]
+    regions, count, inside = _wedges(big + thin)
+    z = np.sort(rng.uniform(0.0, 12.0, (74, 2)), axis=1) + np.array([0.0, 0.001])
+    apart = np.stack([np.stack([_flat_plane(z1), np.array([[0.5, 0.5, z0], [0, 0, -1]], F32)]) for z0, z1 in z])
+    zero = _wedge(0, 600, 1199)
+    zero[1, 1] = 0
+    none = np.concatenate([np.tile(FAR_REGION, (75, 1, 1, 1)), apart, zero[None]])
+    order = rng.permutation(400)
+    regions = np.ascontiguousarray(np.concatenate([regions, none])[order], F32)
+    pad = np.zeros(150, np.int32)
+    return regions, np.concatenate([count, pad])[order], np.concatenate([inside, pad])[order], rng
+
+
+def _csr_region_rooms(count, rng):
+    """rooms below, at and above each count; the two wedges of 400 pairs get half their count (deep heaps: every pair of the second
+    instance, and most of the first's, meets a full room) -> int64 [n]"""
+    c = count.astype(np.int64)
+    room = np.maximum(c + rng.integers(-1, 3, len(c)), 0)
+    room[c == 400] = 200
+    return room
+
+
+def _mixed_flags(flags, c, room, offsets):
+    """every list of at least 100 pairs holds both values of the inside flag, each in at least a quarter of its entries -> the number
+    of such lists.  flags: the shim's flat `inside`; region i's entries lie at offsets[i] .. offsets[i] + min(room, count)."""
+    lists = 0
+    for i in np.flatnonzero(c >= 100):
+        f = flags[offsets[i]:offsets[i] + min(room[i], c[i])]
+        assert len(f) >= 99
+        assert set(np.unique(f)) == {0, 1} and 0.25 <= f.mean() <= 0.75, (i, c[i], room[i], f.mean())
+        lists += 1
+    return lists
+
+
+def _last64_regions():
+    """the fixed-room tests' last 64 regions, shuffled: 16 wedges over 25 to 124 quads, 32 over 520 to 1189, the whole stack, and 15
+    thin ones; each wedge's tilted plane spans half of its quads, so half of its pairs are whole inside -> (regions, count, inside)"""
+    rng = np.random.default_rng(131)
+    spans = np.concatenate([rng.integers(25, 125, 16), rng.integers(520, 1000, 16), rng.integers(1030, 1190, 16), rng.integers(1, 4, 15)])
+    specs = [(int(a), max(1, int(s) // 2), int(a + s - 1)) for s in spans for a in [rng.integers(0, QUADS - s + 1)]] + [(0, 600, 1199)]
+    regions, count, inside = _wedges(specs)
+    order = rng.permutation(64)
+    return np.ascontiguousarray(regions[order], F32), count[order], inside[order]
+
+
+def _last64_bands(c, K):
+    """what the fixed-room tests need of the last 64 counts"""
+    assert ((c >= 100) & (c < 500)).sum() == 16 and ((c >= K) & (c < 4 * QUADS)).sum() == 32 and (c == 4 * QUADS).sum() == 1, c
+    assert ((c > 0) & (c <= 12)).sum() == 15 and (c // 2 >= K).sum() >= 17
+
+
+def _rg_words(a, k):
+    """a shim field as the flat elements the buffers below hold: the flag's bytes, everything else as int32 words"""
+    a = np.ascontiguousarray(a)
+    return a.reshape(-1) if k == "inside" else a.view(np.int32).reshape(-1)
+
+
+def _rg_buffer(k, nslots):
+    import torch
+    return torch.empty(RG_WIDTH[k] * nslots, dtype=torch.uint8 if k == "inside" else torch.int32, device="cuda")
+
+
+def _rg_guard(k):
+    return GUARD if k == "inside" else GUARD32
+
+
+def _rg_bytes(given, nslots):
+    return nslots * sum(RG_WIDTH[k] * (1 if k == "inside" else 4) for k in given)
+
+
+def _region_list(rt, handle, regions, n, offsets_ptr, max_hits, bufs, cnt):
+    """rt_list_in_regions on device buffers (bufs: field -> elements, a missing field is not asked for), synchronous on the NULL
+    stream; planes_per_region from the regions' shape"""
+    import torch
+    lst = rt.RtRegionList(*[bufs[k].data_ptr() if k in bufs else None for k in ro.FIELDS], None if cnt is None else cnt.data_ptr(), None)
+    torch.cuda.synchronize()
+    return rt.libs()[0].rt_list_in_regions(handle, regions.data_ptr(), n, int(regions.shape[1]), offsets_ptr, max_hits, C.byref(lst), None, 1)
+
+
+@pytest.mark.parametrize("fields,base", [((), 2 ** 31 + 5), ((), 2 ** 32 + 5), (("inside",), 2 ** 31 + 5), (("inside",), 2 ** 32 + 5),
+                                         (("normal",), -(-2 ** 32 // 3) + 5), (("inside", "normal"), -(-2 ** 32 // 3) + 5)],
+                         ids=["keys-2^31", "keys-2^32", "inside-2^31", "inside-2^32", "normal-2^32/3", "inside+normal-2^32/3"])
+def test_region_csr_rooms_at_large_slots(rt, flipstack, fields, base):
+    """test_section_csr_rooms_at_large_slots for rt_list_in_regions, whose heap has slot arithmetic of its own: RgRoom's get and put
+    (under room_insert, room_sift_down and room_sort) index the one-byte flag[q], whose byte index is the slot itself, and
+    normal + 3 * q; the pair's record slot travels through the heap in the first word of the entry's normal, its inside flag in its own
+    byte.  400 K = 2 wedges on the quad stack with half of its windings reversed, with hand-made offsets base + cumsum(room), counted
+    in slots, rooms below, at and above each count (two deep heaps of 400 pairs at half their count, so most arrivals replace the
+    root and sift a long way with their flag and slot); the lists run to 1200 entries.  With the keys alone, and with the flag, the
+    base is 2^31 + 5 and 2^32 + 5 (xl_room's start, the key index and the flag's byte index); with the normal it is
+    ceil(2^32 / 3) + 5, so that 3 * q passes 2^32 where q stays below 2^31, alone and with the flag beside it.  The shim's count and
+    inside of every region equal their closed forms before anything is allocated.  In every given field of W elements per slot the
+    window around the rooms equals the shim's rooms, guards of 64 slots either side included, and the first W * 4096 elements (where a
+    start cut to 32 bits, or a product 3 * q taken in 32 bits, would land: 3 * base mod 2^32 is 17) keep their guard.  Floats are
+    compared as int32 words; the flag buffer is uint8.  count equals the shim's.  Along every list of at least 100 entries both flag
+    values hold at least a quarter each and, the quads being shuffled in z, alternate; the normals are (0, 0, +-c) by the quad's
+    winding: an entry left with another's flag or record slot by room_insert's sift-up, room_sift_down or room_sort differs."""
+    import torch
+    regions, want_c, want_in, rng = _csr_regions()
+    n = len(regions)
+    given = ("instance", "triangle") + fields
+    shim = ro.count_in_regions(flipstack.so, regions)
+    _eq(shim["count"], want_c, "the shim's count against 4 * (b - a + 1)")
+    _eq(shim["inside"], want_in, "the shim's inside against 4 * (b - a - m + 1)")
+    c = want_c.astype(np.int64)
+    assert c.max() == 1200 and (c == 400).sum() == 2 and (c == 100).sum() == 4 and (c == 0).sum() == 150, np.unique(c, return_counts=True)
+    assert set(np.unique(c)) == {0, 4, 8, 12, 100, 400, 1200}
+    room = _csr_region_rooms(want_c, rng)
+    assert (room < c).any() and (room > c).any() and (room == c).any() and (room == 0).any() and (room[c == 400] == 200).all()
+    assert all((room[c == v] < v).any() and (room[c == v] > v).any() for v in (4, 8))       # (thin rooms of either kind)
+    rooms = int(room.sum())
+    assert rooms + 5 + 64 <= 4096                               # (offsets mod 2^32 fall inside the head window)
+    for k in given:                                             # (an element index cut to 32 bits falls inside the head window)
+        W = RG_WIDTH[k]
+        assert W * base < 2 ** 32 or (W * base) % 2 ** 32 + W * (rooms + 64) <= W * 4096, (k, base)
+    if "normal" in fields:                                      # (the product passes 2^32, the slot not 2^31)
+        assert base + rooms + 64 < 2 ** 31 and 3 * base > 2 ** 32
+    else:                                                       # (the slot, and with it the flag's byte index, passes the boundary)
+        assert base > 2 ** 31
+    offsets = (base + _cumsum(room)).astype(np.int64)
+    nslots = base + rooms + 64
+    _need_memory(_rg_bytes(given, nslots))
+    lo, hi = base - 64, base + rooms + 64
+    ref = ro.rooms(flipstack.so, regions, offsets=offsets - lo, slots=hi - lo, fill=RG_FILL)
+    _eq(ref["count"], want_c, "the shim's count beside its rooms")
+    assert _mixed_flags(ref["inside"], c, room, offsets - lo) == 7
+    bufs = None
+    try:
+        bufs = {k: _rg_buffer(k, nslots) for k in given}
+        for k, b in bufs.items():
+            b[RG_WIDTH[k] * lo:RG_WIDTH[k] * hi].fill_(_rg_guard(k))
+            b[:RG_WIDTH[k] * 4096].fill_(_rg_guard(k))
+        cnt = torch.full((n,), -9, dtype=torch.int32, device="cuda")
+        doff = torch.from_numpy(offsets).cuda()
+        bt, = _up((regions,))
+        assert _region_list(rt, flipstack.handle, bt, n, doff.data_ptr(), 0, bufs, cnt) == 0
+        for k in given:
+            W = RG_WIDTH[k]
+            window, head = bufs[k][W * lo:W * hi].cpu().numpy(), bufs[k][:W * 4096].cpu().numpy()
+            assert (head == _rg_guard(k)).all(), "%s: %d of the array's first %d elements were written" % (
+                k, int((head != _rg_guard(k)).sum()), W * 4096)
+            _eq(window, _rg_words(ref[k], k), "%s rooms at slot %d" % (k, base))
+        _eq(cnt.cpu().numpy(), ref["count"], "count")
+    finally:
+        del bufs
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("fields,n", [(("inside",), 2 ** 20 + 64), (("normal",), 2 ** 19 + 2 ** 18 + 64)], ids=["inside", "normal"])
+def test_region_fixed_rooms_at_large_slots(rt, flipstack, fields, n):
+    """max_hits = 2049 on the quad stack with half of its windings reversed; every region but the last 64 lies far off.  With the keys
+    and the flag n = 2^20 + 64 and the last 64 rooms start beyond slot, and flag byte, 2^31; with the keys and the normal n = 2^19 +
+    2^18 + 64, they start at slot 1 611 399 168 < 2^31, and 3 * q there is about 4.83e9, above 2^32.  The last 64 rooms equal the
+    shim's fixed rooms in every given field, with count and without it.  Their counts lie below K (16 wedges over 25 to 124 quads,
+    and 15 thin ones), between K and the scene's 4800 (32 wedges), and at 4800; 17 of them fill their room from instance 0 alone, so
+    the run without count asks `go` before instance 1 with a full room and reads the room's root p.instance[i * K] at a large slot.
+    (That read cannot change a room: a full room's keys all come from earlier instances, so a correct read always ends the traversal,
+    and a wrong one that goes on finds only greater keys.  What the run shows is that the read stays inside the array and the rooms
+    are right, no more.)  The rooms of a sample of the other regions (the first, the last, and those around the slots where q -- the
+    flag's byte index -- and 3 * q pass 2^31 and 2^32, and those where the last rooms' 3 * q cut to 32 bits would land) are all
+    padding: keys of -1, flags of 0 and normal words of 0.0."""
+    import torch
+    K = 2049
+    last, want_c, want_in = _last64_regions()
+    regions = np.tile(FAR_REGION, (n, 1, 1, 1))
+    regions[-64:] = last
+    given = ("instance", "triangle") + fields
+    shim = ro.count_in_regions(flipstack.so, last)
+    _eq(shim["count"], want_c, "the shim's count of the last 64 regions against 4 * (b - a + 1)")
+    _eq(shim["inside"], want_in, "the shim's inside of the last 64 regions against 4 * (b - a - m + 1)")
+    _last64_bands(want_c, K)
+    if "normal" in fields:
+        assert n * K < 2 ** 31 and 3 * (n - 64) * K > 2 ** 32
+    else:
+        assert (n - 64) * K > 2 ** 31
+    assert (ro.count_in_regions(flipstack.so, regions[:64])["count"] == 0).all()
+    _need_memory(_rg_bytes(given, n * K))
+    ref = ro.rooms(flipstack.so, last, max_hits=K)
+    c = ref["count"]
+    _eq(c, want_c, "the shim's count beside its rooms")
+    assert _mixed_flags(ref["inside"], c.astype(np.int64), np.full(64, K), np.arange(64) * K) == 49
+    marks = [2 ** 31 // K, 2 ** 32 // K, 2 ** 31 // 3 // K, 2 ** 32 // 3 // K]
+    # (and the rooms where the last 64 rooms' q, or 3 * q, cut to 32 bits would land: a product taken in 32 bits on both sides of the
+    # heap is consistent with itself and leaves the last rooms right; what shows is the slot it wrote into another region's room)
+    cut = [(W * (n - 64) * K) % 2 ** 32 // (W * K) + j for W in (1, 3) for j in (0, 1, 32, 63)]
+    sample = sorted({i for i in [0, 1, 63, 64, n // 2, n - 66, n - 65] + cut + [m + j for m in marks for j in (-1, 0, 1)] if i < n - 64})
+    assert len(sample) >= 13 and ("normal" not in fields or len([i for i in cut[4:] if i in sample]) == 4)
+    bufs = None
+    try:
+        bufs = {k: _rg_buffer(k, n * K) for k in given}
+        bt, = _up((regions,))
+        for with_count in (True, False):
+            at = "with count" if with_count else "without count"
+            for k, b in bufs.items():
+                w = RG_WIDTH[k] * K
+                for i in sample:
+                    b[i * w:(i + 1) * w].fill_(_rg_guard(k))
+                b[(n - 64) * w:].fill_(_rg_guard(k))
+            cnt = torch.full((n,), -9, dtype=torch.int32, device="cuda") if with_count else None
+            assert _region_list(rt, flipstack.handle, bt, n, None, K, bufs, cnt) == 0
+            for k in given:
+                w = RG_WIDTH[k] * K
+                _eq(bufs[k][(n - 64) * w:].cpu().numpy(), _rg_words(ref[k], k), "%s of the last 64 rooms, %s" % (k, at))
+                for i in sample:
+                    room = bufs[k][i * w:(i + 1) * w].cpu().numpy()
+                    assert (room == RG_PAD[k]).all(), "%s of room %d (a region without pairs), %s: %d elements are not padding" % (
+                        k, i, at, int((room != RG_PAD[k]).sum()))
             if with_count:
                 got = cnt.cpu().numpy()
                 _eq(got[-64:], c, "count of the last 64")

@@ -1,6 +1,6 @@
 """The `stream` argument of the query wrappers on the torch path, in both forms the docstrings promise: a torch.cuda.Stream and the raw
 hipStream_t of one.  Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes and occupancy grids,
-plane sections) runs once with each on a stream that is not the current one, and both results equal the numpy path's for the same inputs bit for
+plane sections, regions, segments, triangle distances) runs once with each on a stream that is not the current one, and both results equal the numpy path's for the same inputs bit for
 bit (the numpy path is held to the oracles by the family's own tests: none is needed here)."""
 import numpy as np
 import pytest
@@ -19,6 +19,7 @@ def _queries(s, q, **kw):
     pairs = s.INTERSECT_LIST_OUTPUTS + ("count", "pops")
     boxed = s.BOX_LIST_OUTPUTS + ("count", "pops")
     cut = s.SECTION_LIST_OUTPUTS + ("count", "pops")
+    held = s.REGION_LIST_OUTPUTS + ("count", "pops")
     grid_kw = kw or dict(as_numpy=True)                         # (the grid takes no arrays: numpy results are asked for by name)
     return {
         "trace_rays": lambda: s.trace_rays(o, d, outputs=s.RAY_OUTPUTS, **kw),
@@ -41,13 +42,19 @@ def _queries(s, q, **kw):
         "count_sections": lambda: s.count_sections(q["planes"], outputs=s.SECTION_COUNT_OUTPUTS, **kw),
         "list_sections_csr": lambda: s.list_sections(q["planes"], outputs=cut, **kw),
         "list_sections_k2": lambda: s.list_sections(q["planes"], max_hits=2, outputs=cut, **kw),
+        "count_in_regions": lambda: s.count_in_regions(q["regions"], outputs=s.REGION_COUNT_OUTPUTS, **kw),
+        "list_in_regions_csr": lambda: s.list_in_regions(q["regions"], outputs=held, **kw),
+        "list_in_regions_k2": lambda: s.list_in_regions(q["regions"], max_hits=2, outputs=held, **kw),
+        "closest_to_segments": lambda: s.closest_to_segments(q["segs"], md, outputs=s.SEGMENT_OUTPUTS, **kw),
+        "closest_to_triangles": lambda: s.closest_to_triangles(tris, md, skip, outputs=s.TRIANGLE_HIT_OUTPUTS, **kw),
     }
 
 
 QUERIES = ("trace_rays", "occluded", "closest_points", "count_crossings", "winding_numbers", "signed_distance", "list_crossings_csr",
            "list_crossings_k2", "list_nearby_csr", "list_nearby_k2", "count_intersecting", "list_intersecting_csr", "list_intersecting_k2",
            "count_in_boxes", "list_in_boxes_csr", "list_in_boxes_k2", "occupancy_grid", "count_sections", "list_sections_csr",
-           "list_sections_k2")
+           "list_sections_k2", "count_in_regions", "list_in_regions_csr", "list_in_regions_k2", "closest_to_segments",
+           "closest_to_triangles")
 GRID = ((-1.3, -1.2, -1.1), (0.41, 0.43, 0.47), (7, 6, 5))      # origin, spacing, dims: a grid around the blob, partial bricks
 
 
@@ -67,6 +74,11 @@ def staged(rt, scenes, blob5k):
     edge = rng.uniform(0.05, 0.4, (N, 3))                       # boxes around the same points: some cut the surface, some do not
     q["boxes"] = np.stack([pts - edge / 2, pts + edge / 2], axis=1).astype(F32)
     q["planes"] = np.stack([pts, rng.normal(size=(N, 3))], axis=1).astype(F32)      # planes through the same points: most cut the blob
+    # regions (K = 6 boxes) and segments at the same points (drawn last: what is above stays what it was); the triangles above serve
+    # closest_to_triangles too
+    edge = rng.uniform(0.05, 0.4, (N, 3))
+    q["regions"] = rt.regions_from_boxes(np.stack([pts - edge / 2, pts + edge / 2], axis=1).astype(F32))
+    q["segs"] = np.stack([pts, pts + rng.uniform(-0.3, 0.3, (N, 3))], axis=1).astype(F32)
     q = {k: np.ascontiguousarray(v) for k, v in q.items()}
     dq = {k: torch.from_numpy(v).cuda() for k, v in q.items()}
     torch.cuda.synchronize()

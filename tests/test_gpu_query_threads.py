@@ -1,7 +1,7 @@
-"""Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes, plane sections) on ONE scene from eight host
-threads at once, beside renders, instance updates, refits and a device-resident rebuild ("Threads"): the entry points share scene_launch, which takes the scene's call lock for the launches of
-one call (two nested calls for rt_signed_distance, a count launch and the scan's launches for the *_offsets calls) and leaves it before
-any wait.  test_gpu_threads.test_four_threads_on_one_scene, whose phase scheme and helpers this reuses, predates the families and
+"""Every query family (rays, points, crossings, nearby lists, triangle intersections, boxes, plane sections, regions, segments, triangle
+distances) on ONE scene from ten host threads at once, beside renders, instance updates, refits and a device-resident rebuild ("Threads"): the entry points share scene_launch, which takes the scene's call lock for the launches of
+one call (two nested calls for rt_signed_distance, a count launch and the scan's launches for the *_offsets calls, the distance launch
+and the crossing or intersection launch of rt_closest_to_segments and rt_closest_to_triangles) and leaves it before any wait.  test_gpu_threads.test_four_threads_on_one_scene, whose phase scheme and helpers this reuses, predates the families and
 queries with rt_trace_rays and rt_occluded only.  Every result of every call is compared bit for bit with the CPU shims' result for the
 scene state of its phase, never with another GPU run.  Nothing retries; a thread still alive after its deadline fails the test."""
 import ctypes as C
@@ -17,11 +17,17 @@ import nearby_oracle as nb
 import point_oracle
 import query_points as qp
 import query_rays as qr
+import query_segments as qsg
+import query_triangles as qtr
+import region_oracle as ro
 import scene_defs as sd
 import section_oracle as sc
+import segment_oracle as sg
 import tri_intersect_oracle as ti
+import triangle_distance_oracle as tdo
 from test_gpu_boxes import families as box_families
 from test_gpu_crossings import _cam, _eq
+from test_gpu_regions import families as region_families
 from test_gpu_sections import families as section_families
 from test_gpu_threads import _Threads, _deformed, _host_arrays, _params, _render_batch_fn, _same_frame
 from test_gpu_tri_intersect import families as tri_families
@@ -34,14 +40,16 @@ XL_FIELDS = ("t", "instance", "triangle", "sign", "barycentric", "uv", "point")
 TI_FIELDS = ("instance", "triangle", "normal", "segment")
 BX_FIELDS = ("instance", "triangle")
 SC_FIELDS = ("instance", "triangle", "segment", "normal")
+RG_FIELDS = ("instance", "triangle", "inside", "normal")
 GRID_DIMS = (5, 3, 2)
-WORKERS = ("W1", "W2", "W3", "W4", "W5", "W6", "W7", "W8")
+WORKERS = ("W1", "W2", "W3", "W4", "W5", "W6", "W7", "W8", "W9", "W10")
 
 
 def _oracle_results(so, q, frames_of):
     """Everything the workers ask, from the shims, for the oracle scene's current state: name -> dict or array"""
     o, d, tmax, pts, md, radius, tris, skip = (q[k] for k in ("o", "d", "tmax", "pts", "md", "radius", "tris", "skip"))
     boxes, (origin, spacing), planes = q["boxes"], q["grid"], q["planes"]
+    regions, segs, seg_md, qtris, qtri_md, qtri_skip = (q[k] for k in ("regions", "segs", "seg_md", "qtris", "qtri_md", "qtri_skip"))
     return {
         "closest": point_oracle.closest_points(so, pts),
         "closest_md": point_oracle.closest_points(so, pts, md),
@@ -65,6 +73,11 @@ def _oracle_results(so, q, frames_of):
         "sc_count": sc.count_sections(so, planes),
         "sc_csr": sc.list_sections(so, planes),
         "sc_k4": sc.list_sections(so, planes, max_hits=4),
+        "rg_count": ro.count_in_regions(so, regions)["count"],
+        "rg_csr": ro.list_in_regions(so, regions),
+        "rg_k4": ro.list_in_regions(so, regions, max_hits=4),
+        "sg_md": sg.closest_to_segments(so, segs, seg_md),
+        "td_md_skip": tdo.closest_to_triangles(so, qtris, qtri_md, qtri_skip),
         "frames": frames_of(so),
     }
 
@@ -78,8 +91,8 @@ def _same(got, ref, keys, where):
         _eq(_np(got[k]), ref[k], "%s %s" % (where, k))
 
 
-def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
-    """Eight workers, each on its own torch stream with at least three calls per phase, and a mutator, through five phases that alternate
+def test_ten_query_threads_on_one_scene(rt, orc, scenes, blob5k):
+    """Ten workers, each on its own torch stream with at least three calls per phase, and a mutator, through five phases that alternate
     two known states (S0: as uploaded; S1: instance 2 moved with rt_scene_update_instance_async and mesh 1 refitted from host arrays,
     both on the mutator's stream; the last change back to S0 is rt_scene_rebuild_mesh_device of the refitted mesh to its rest shape).
     W1: closest_points with every output, signed_distance (a nested call under one hold of the lock), closest_points bounded.
@@ -95,6 +108,15 @@ def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     W8: count_sections for `any` alone (the kernel that stops at the first pair), list_sections CSR with all four fields (a count
     launch and the scan under one hold of the lock, then the fill, whose rooms are heaps that carry each pair's record slot),
     max_hits = 4 with the normal alone and without count (the slot travels in the normal, the rooms end the traversal early).
+    W9: count_in_regions on K = 6 regions for `any` alone (the kernel that stops at the first pair), list_in_regions CSR with all four
+    fields (a count launch and the scan under one hold of the lock, then the fill, whose rooms are heaps that carry each pair's inside
+    flag and record slot), max_hits = 4 with the normal alone and without count (the slot travels in the normal, the rooms end the
+    traversal early), max_hits = 4 with the inside flag alone.
+    W10: the calls of two launches under one hold of the lock, which must see one scene state: closest_to_segments with every exact
+    output, crossings, clearance and within among them, with a max_distance column (the distance launch, then the crossing launch
+    that patches clearance and within); closest_to_triangles with a max_distance and a skip_instance column and every exact output,
+    intersections, clearance and within among them; closest_to_segments for `within` alone (the kernel that ends at the first
+    triangle in reach).
     Between phases the state change is ordered after every worker's last call and before every worker's next by events.  Every
     result of every call equals the shims' for its phase's state, every frame the oracle's, and no call fails."""
     import torch
@@ -126,8 +148,18 @@ def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     # (a generator of their own: the draws below stay what they were before the boxes came)
     boxes = np.ascontiguousarray(np.concatenate([f[1] for f in box_families(np.random.default_rng(83), o_, desc, n=600)]), F32)
     planes = np.ascontiguousarray(np.concatenate([f[1] for f in section_families(np.random.default_rng(89), o_, desc, n=600)]), F32)
-    for name, a in (("rays", o), ("points", pts), ("triangles", tris), ("boxes", boxes), ("planes", planes)):
+    regions = np.ascontiguousarray(np.concatenate([f[1] for f in region_families(rt, np.random.default_rng(97), o_, desc, n=800)[6]]), F32)
+    segs = qsg.flatten(qsg.families(np.random.default_rng(101), o_, desc, so, cam, n=2600)[0])
+    qtris = qtr.flatten(qtr.families(np.random.default_rng(103), o_, desc, so, cam, n=1300)[0])
+    for name, a in (("rays", o), ("points", pts), ("triangles", tris), ("boxes", boxes), ("planes", planes), ("regions", regions),
+                    ("segments", segs)):
         assert 2000 <= len(a) <= 4000, (name, len(a))
+    assert 1000 <= len(qtris) <= 2000, len(qtris)               # (the shim of the triangle distances is the slowest of the set-up)
+    assert regions.shape[1:] == (6, 2, 3)
+    rng2 = np.random.default_rng(107)                           # (the new families' bounds: the draws below stay what they were)
+    seg_md = qp.special_bounds(rng2, sg.closest_to_segments(so, segs)["distance"])
+    qtri_md = qp.special_bounds(rng2, tdo.closest_to_triangles(so, qtris)["distance"])
+    qtri_skip = rng2.integers(-1, len(desc.instances), len(qtris)).astype(np.int32)
     dist = point_oracle.closest_points(so, pts)["distance"]
     lo, hi = qp.scene_box(o_, desc, desc.oracle_meshes)
     diag = F32(np.linalg.norm((hi - lo).astype(np.float64)))
@@ -139,7 +171,8 @@ def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     near = (dist * rng.uniform(1.0, 1.5, len(pts)) + diag * F32(1e-3)).astype(F32)
     q = dict(o=o, d=d, tmax=qr.special_tmax(rng, len(o)), pts=pts, md=qp.special_bounds(rng, dist),
              radius=np.ascontiguousarray(np.where(dist > F32(0.1) * diag, np.nextafter(dist, F32(np.inf)), near), F32), tris=tris,
-             skip=rng.integers(-1, len(desc.instances), len(tris)).astype(np.int32), boxes=boxes, grid=grid, planes=planes)
+             skip=rng.integers(-1, len(desc.instances), len(tris)).astype(np.int32), boxes=boxes, grid=grid, planes=planes,
+             regions=regions, segs=segs, seg_md=seg_md, qtris=qtris, qtri_md=qtri_md, qtri_skip=qtri_skip)
 
     def frames_of(scene):
         return [scene.render(W, H, K, D, p, threads=16, planes=False)["img"] for p in poses]
@@ -149,7 +182,7 @@ def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
     want[1] = _oracle_results(so, q, frames_of)
     so.close()
     for name, key in (("closest", "distance"), ("xl_csr", "offsets"), ("nb_csr", "offsets"), ("ti_csr", "offsets"),
-                      ("bx_csr", "offsets"), ("sc_csr", "offsets")):
+                      ("bx_csr", "offsets"), ("sc_csr", "offsets"), ("rg_csr", "offsets"), ("sg_md", "distance")):
         assert not np.array_equal(want[0][name][key], want[1][name][key]), name + ": the two states give one result"
     assert any(not np.array_equal(a, b) for a, b in zip(want[0]["frames"], want[1]["frames"]))
 
@@ -220,6 +253,17 @@ def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
                     sc_csr=sp.list_sections(dq["planes"], outputs=SC_FIELDS, stream=s),
                     sc_k4=sp.list_sections(dq["planes"], max_hits=4, outputs=("normal",), stream=s))
 
+    def w9(s, ph):
+        return dict(rg_any=sp.count_in_regions(dq["regions"], outputs=("any",), stream=s),
+                    rg_csr=sp.list_in_regions(dq["regions"], outputs=RG_FIELDS, stream=s),
+                    rg_k4_normal=sp.list_in_regions(dq["regions"], max_hits=4, outputs=("normal",), stream=s),
+                    rg_k4_inside=sp.list_in_regions(dq["regions"], max_hits=4, outputs=("inside",), stream=s))
+
+    def w10(s, ph):
+        return dict(sg_md=sp.closest_to_segments(dq["segs"], dq["seg_md"], outputs=sg.OUTPUTS, stream=s),
+                    td_md_skip=sp.closest_to_triangles(dq["qtris"], dq["qtri_md"], dq["qtri_skip"], outputs=tdo.OUTPUTS, stream=s),
+                    sg_within=sp.closest_to_segments(dq["segs"], dq["seg_md"], outputs=("within",), stream=s))
+
     def w6():
         for ph in range(len(phases)):
             results["W6"][ph] = dict(xl_csr=sp.list_crossings(q["o"], q["d"]),
@@ -229,7 +273,8 @@ def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
             next_phase.wait()
             ready[ph].synchronize()                             # (its launches go to the NULL stream, which no torch event orders)
 
-    for name, calls in (("W1", w1), ("W2", w2), ("W3", w3), ("W4", w4), ("W5", w5), ("W7", w7), ("W8", w8)):
+    for name, calls in (("W1", w1), ("W2", w2), ("W3", w3), ("W4", w4), ("W5", w5), ("W7", w7), ("W8", w8), ("W9", w9),
+                        ("W10", w10)):
         th.start(name, worker, name, calls)
     th.start("W6", w6)
     try:
@@ -298,6 +343,18 @@ def test_eight_query_threads_on_one_scene(rt, orc, scenes, blob5k):
         assert np.array_equal(_np(r["sc_any"]["any"]), ref["sc_count"] > 0), at + " count_sections any alone"
         _same(r["sc_csr"], ref["sc_csr"], SC_FIELDS + ("offsets", "query_index", "count"), at + " list_sections CSR")
         _same(r["sc_k4"], ref["sc_k4"], ("normal",), at + " list_sections K=4, the normal alone, without count")
+        r = results["W9"][ph]
+        assert set(r["rg_any"]) == {"any"} and set(r["rg_k4_normal"]) == {"normal"} and set(r["rg_k4_inside"]) == {"inside"}
+        assert np.array_equal(_np(r["rg_any"]["any"]), ref["rg_count"] > 0), at + " count_in_regions any alone"
+        _same(r["rg_csr"], ref["rg_csr"], RG_FIELDS + ("offsets", "query_index", "count"), at + " list_in_regions CSR")
+        _same(r["rg_k4_normal"], ref["rg_k4"], ("normal",), at + " list_in_regions K=4, the normal alone, without count")
+        _same(r["rg_k4_inside"], ref["rg_k4"], ("inside",), at + " list_in_regions K=4, the inside flag alone, without count")
+        r = results["W10"][ph]
+        assert set(r["sg_md"]) == set(sg.OUTPUTS) and set(r["td_md_skip"]) == set(tdo.OUTPUTS) and set(r["sg_within"]) == {"within"}
+        assert {"crossings", "clearance", "within"} <= set(sg.OUTPUTS) and {"intersections", "clearance", "within"} <= set(tdo.OUTPUTS)
+        _same(r["sg_md"], ref["sg_md"], sg.OUTPUTS, at + " closest_to_segments")
+        _same(r["td_md_skip"], ref["td_md_skip"], tdo.OUTPUTS, at + " closest_to_triangles")
+        _same(r["sg_within"], ref["sg_md"], ("within",), at + " closest_to_segments within alone")
     sp.close()
 
 
