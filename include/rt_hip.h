@@ -51,7 +51,25 @@ enum {
  * the TrianglePrimitive array (TrianglePrimitive.hpp:8-11) and BVHTree::compile_tree
  * (BVHTree.hpp:364-383) the d_BVHTree array (BVHTree.hpp:18-26) plus one index list per leaf
  * (BVHTree.hpp:97-111).  Here the same data arrives flattened; the library re-lays it out for
- * the GPU (see DESIGN.md "Data layout in HBM").  All pointers are HOST pointers. */
+ * the GPU (see DESIGN.md "Data layout in HBM").  All pointers are HOST pointers.
+ *
+ * The tree may be the caller's own.  What rt_scene_upload asks of it: node 0 is the root, the two children of an interior node are
+ * different nodes with higher indices than their parent, every node has one parent, leaf ranges lie inside leaf_indices and
+ * hold triangle indices of this mesh (anything else: RT_E_INVALID), and the tree has at most 64 levels, the root being level 1
+ * (deeper: RT_E_DEPTH).  Every box must contain the vertices of the triangles below its node; it may be looser than exact.
+ * Nodes may be numbered in any order that keeps children behind parents, children may stand in either slot, a leaf may hold any
+ * number of triangles (the root may be a leaf, a leaf may be empty), and an empty leaf may carry an inverted box (min > max):
+ * such a mesh is traversed without pruning (rt_scene_mesh_flags bit 0).  Query answers do not depend on the tree
+ * (tests/test_gpu_caller_trees.py) -- with the one condition the reference's cast brings along for rt_trace_rays, rt_occluded and
+ * the renders: it prunes a box by comparing the box's ray PARAMETER with the world DISTANCE of the closest hit so far, which is
+ * conservative for directions of length >= 1 only, and of equal distances the first visited wins; a ray with a shorter direction,
+ * or with two equal smallest distances, may find another triangle under another tree, as it may in the reference.
+ * Leaf ranges may overlap, and leaf_indices may name a triangle more than once.  A triangle is then reported once per leaf
+ * that references it: it counts that often in rt_count_in_boxes, rt_count_sections, rt_count_in_regions, rt_count_intersecting
+ * and rt_count_crossings (and its winding), and stands that often in their lists, in rt_list_nearby and in the cells of
+ * rt_occupancy_grid.  The minimum-type answers (rt_trace_rays, rt_occluded, rt_closest_points, rt_closest_to_segments,
+ * rt_closest_to_triangles: distance, instance, triangle, location) are those of the mesh without the repeats.  A refit moves
+ * every reference; rt_scene_rebuild_mesh_device replaces the tree by the library's own, which has none. */
 typedef struct RtMeshDesc {
     int32_t num_triangles;
     const float *vertices;          /* [num_triangles][3][3]  TrianglePrimitive::vertices      */

@@ -189,7 +189,9 @@ def test_tmax_at_counted_t(rt, orc, scenes, blob5k):
 
 def test_tree_independence(rt, orc, scenes, blob5k):
     """The host-built tree, a tree built on the device (num_nodes = 0) and the host trees of every mesh refitted to the same vertices
-    give identical counts, windings and signed distances."""
+    give identical counts, windings and signed distances.  The two builders make the same tree node for node
+    (test_gpu_bvh_build_matches_host_builder) and a refit to the same vertices changes no box, so these are three ways to one tree
+    on the device, not three trees: trees the library does not build are tests/test_gpu_caller_trees.py's."""
     desc = sd.multi_instance_scene(scenes, blob5k)
     so = desc.build_oracle(orc)
     a, b, c = _product(rt, desc), _product(rt, desc, for_device=True), _product(rt, desc)

@@ -133,7 +133,9 @@ def test_max_distance_boundary(rt, orc, scenes, blob5k):
 
 
 def test_tree_independence(rt, orc, scenes, blob5k):
-    """The same triangles under the host-built tree and under a tree built on the device (num_nodes = 0) give identical results."""
+    """The same triangles under the host-built tree and under a tree built on the device (num_nodes = 0) give identical results.
+    The two builders make the same tree node for node (test_gpu_bvh_build_matches_host_builder), so this compares the two ways of
+    getting one tree onto the device, not two trees: trees the library does not build are tests/test_gpu_caller_trees.py's."""
     desc = sd.multi_instance_scene(scenes, blob5k)
     so = desc.build_oracle(orc)
     a, b = _product(rt, desc), _product(rt, desc, for_device=True)

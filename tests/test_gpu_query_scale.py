@@ -1183,9 +1183,12 @@ def _hardest_last(pool, n, rng):
 
 @pytest.mark.parametrize("n", [1, 63, 65, 129])
 def test_partial_workgroup_on_the_deep_scene(deep, deep_queries, n):
-    """One call of each family with n one, one below and one above the workgroup of 64, and two groups plus one, on the scene whose
-    traversal stack outgrows its LDS rows; the deepest queries come last, in the partly filled group.  Every result equals the shim's
-    bit for bit."""
+    """One call of each family with n one, one below and one above the workgroup of 64, and two groups plus one, on the 28-level chain;
+    the queries that visit the most nodes come last, in the partly filled group.  Every result equals the shim's bit for bit.
+    What the asserts establish about depth: the tree has more than 16 levels (max_stack > 16, so the kernels run with their spill
+    arrays declared) and some pool ray visits more than 16 nodes on the oracle (pops.max() > 16 in the fixture).  Neither says that a
+    query's stack held more than its 17 LDS rows: test_gpu_caller_trees.py::test_the_stack_reaches_its_spill_array does that, on
+    chains whose boxes cannot prune."""
     sp, so = deep.sp, deep.so
     rng = np.random.default_rng(61 + n)
     o, d = _hardest_last(deep_queries["rays"], n, rng)
