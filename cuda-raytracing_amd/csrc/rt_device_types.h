@@ -68,6 +68,21 @@ constexpr int kExMaxGroup = 32;
 constexpr int kExPlanesA = 5, kExPlanesS = 7;
 
 constexpr int kMaxViewInstances = 8;    // scenes of more instances render without view records (RenderParams::view_inst_off)
+// Ray header of one (frame, instance) of a launch that renders through view records: what a wave of render_kernel<.., VIEW> needs
+// of the instance before its loop and what does not depend on the lane, in one 64-byte block that the wave fetches through the
+// scalar cache.  Written by view_records_kernel in front of the frame's view records (block i of the frame's view = instance i).
+struct RayHeader {
+    float ro[3];                // the frame's origin in the instance's mesh space: to_mesh_space(..).ro, the bits the view records hold
+    uint32_t flags;             // kRay* below
+    Q4 q_rot;                   // DevInstance::q_rot, inv_scale: the direction's transform stays per lane
+    float inv_scale[3];
+    int32_t root_ref;
+    float inv_pose_xyz[3];
+    uint32_t vdelta;            // view_base + frame * view_frame_stride + view_inst_off[i]
+};
+static_assert(sizeof(RayHeader) == 64, "one scalar fetch of sixteen words");
+constexpr uint32_t kRayOriginFinite = 1, kRayBoxUnordered = 2, kRayExactUv = 4, kRayUnitInv = 8;
+
 constexpr int kMaxBatch = 32;   // frames per launch (rt_render_batch); 32 x 96 B of per-frame parameters keep the kernel
                                 // arguments under the 4 KB limit
 
@@ -85,7 +100,7 @@ struct FrameParams {            // what differs between the frames of one batche
 
 struct RenderParams {
     int32_t width, height;
-    int32_t num_frames;         // grid.y
+    int32_t num_frames;         // grid.z of un-ordered primary launches; a factor of the ordered ones' grid.x
     FrameParams frames[kMaxBatch];
     const float4* records;      // interior-node and triangle records (64 B each), one index space
     const float* tri_uv;        // [slot][3][2]
@@ -133,7 +148,8 @@ struct RenderParams {
     int32_t gen_samples;        // primary launch: sample indices in this chunk
     int32_t gen_spw;            // primary launch: sample indices per workgroup (4, 2 or 1: one, two or four 8x8 quads)
     // render_kernel<.., VIEW>: the view record of interior record `e` of instance i in frame f is at byte offset
-    // view_base + f * view_frame_stride + view_inst_off[i] + e * 64 from `records` (32-bit arithmetic; RtScene::ViewPool)
+    // view_base + f * view_frame_stride + view_inst_off[i] + e * 64 from `records` (32-bit arithmetic; RtScene::ViewPool); the ray
+    // header of instance i in frame f is at view_base + f * view_frame_stride + i * 64
     uint32_t view_base, view_frame_stride;
     int32_t view_inst_off[kMaxViewInstances];
     unsigned long long* loop_stats;     // render_kernel<.., STATS> (rt_scene_loop_stats): RT_LOOP_WORDS counters, null in every other launch

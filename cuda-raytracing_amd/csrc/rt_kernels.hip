@@ -196,6 +196,43 @@ __device__ __forceinline__ MeshRay to_mesh_space(const DevInstance& in, V3 org, 
     return r;
 }
 
+// The ray header of (frame, instance) (RayHeader; view_records_kernel writes it): one fetch through the scalar cache, the words
+// staying in scalar registers.  `view_off` = byte offset of the frame's view from p.records.
+struct RayHeaderWords {
+    V3 ro; uint32_t flags; Q4 q_rot; V3 inv_scale; int32_t root_ref; V3 back; uint32_t vdelta;
+};
+static_assert(offsetof(RayHeader, flags) == 12 && offsetof(RayHeader, q_rot) == 16 && offsetof(RayHeader, inv_scale) == 32 &&
+              offsetof(RayHeader, root_ref) == 44 && offsetof(RayHeader, inv_pose_xyz) == 48 && offsetof(RayHeader, vdelta) == 60, "RayHeader layout");
+
+__device__ __forceinline__ RayHeaderWords ray_header(const RenderParams& p, uint32_t view_off, int inst_index)
+{
+    // (four quarters, not one sixteen-register value: the allocator keeps or drops a fetched value whole, and only the last quarter
+    // lives on into the loop)
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    f4v w0, w1, w2, w3;
+    const uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane((int)(view_off + (uint32_t)inst_index * (uint32_t)sizeof(RayHeader)));
+    asm volatile("s_load_dwordx4 %0, %4, %5\n\ts_load_dwordx4 %1, %4, %5 offset:16\n\ts_load_dwordx4 %2, %4, %5 offset:32\n\t"
+                 "s_load_dwordx4 %3, %4, %5 offset:48\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(w0), "=&s"(w1), "=&s"(w2), "=&s"(w3) : "s"(p.records), "s"(off));
+    RayHeaderWords h;
+    h.ro = v3(w0[0], w0[1], w0[2]); h.flags = __float_as_uint(w0[3]);
+    h.q_rot.x = w1[0]; h.q_rot.y = w1[1]; h.q_rot.z = w1[2]; h.q_rot.w = w1[3];
+    h.inv_scale = v3(w2[0], w2[1], w2[2]); h.root_ref = __float_as_int(w2[3]);
+    h.back = v3(w3[0], w3[1], w3[2]); h.vdelta = __float_as_uint(w3[3]);
+    return h;
+}
+
+// (the direction's half of to_mesh_space above, operation for operation; the origin is the header's)
+__device__ __forceinline__ MeshRay to_mesh_space(const RayHeaderWords& h, V3 dir)
+{
+    MeshRay r;
+    r.rd = apply_quat(h.q_rot, dir);
+    r.rd.x *= h.inv_scale.x; r.rd.y *= h.inv_scale.y; r.rd.z *= h.inv_scale.z;
+    r.ro = h.ro;
+    r.dinv = v3(1.0f / r.rd.x, 1.0f / r.rd.y, 1.0f / r.rd.z);
+    return r;
+}
+
 // One interior node (raycast.cu:66-79) from its already fetched 64-B record: tests both children, pushes the
 // far one if it passes `dist < hit.min`, and leaves in `cur` the entry the reference would pop next (the entry
 // pushed last never goes through the stack).  Returns false when nothing was pushed.
@@ -316,6 +353,10 @@ __device__ __forceinline__ bool triangle_test(const RenderParams& p, const DevIn
     }
     return accept;
 }
+
+// The workgroup's linear index in its grid -- (tiles_x, tiles_y, frames) for un-ordered primary launches: frame-major, then tile
+// rows -- which is the row of RenderParams::trace its waves write (render_kernel's stamps, trace_loop<.., PROF>'s phase sums).
+__device__ __forceinline__ size_t trace_workgroup() { return ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; }
 
 // One instance of raycast.cu:26-139.
 //
@@ -518,7 +559,7 @@ __device__ __forceinline__ void trace_loop(const RenderParams& p, const DevInsta
             for (int o = 32; o > 0; o >>= 1) { unsigned long long x = __shfl_xor(best, o); best = x > best ? x : best; }
             const unsigned long long owner = __ballot(n_it == best);
             if ((int)(threadIdx.x & 63) == __ffsll((long long)owner) - 1) {
-                unsigned long long* t = p.trace + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (kPrimBlock / 64) + (threadIdx.x >> 6)) * 16 + 4;
+                unsigned long long* t = p.trace + (trace_workgroup() * (kPrimBlock / 64) + (threadIdx.x >> 6)) * 16 + 4;
                 for (int k = 0; k < 10; k++) t[k] += v[k];
             }
         }
@@ -1063,22 +1104,28 @@ __device__ __forceinline__ void loop_stat(const RenderParams& p, int which, unsi
 }
 
 template <bool DEBUG, bool PROF, bool EX = false, bool COUNT = false, class STK = Stack, bool POPS = false, bool OCTANTS = true, bool ANYHIT = false,
-          bool VIEW = false, bool UNIFORM_ORG = !EX, bool STATS = false, bool SEC = false>
+          bool VIEW = false, bool UNIFORM_ORG = !EX, bool STATS = false, bool SEC = false, bool HDR = false>
 __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevInstance& in, int inst_index,
                                                V3 org, V3 dir, STK& stack, Hit& hit, Counters<DEBUG>& cnt, int* iters = nullptr,
                                                int* pops = nullptr, uint32_t view_off = 0, float tmax = FLT_MAX)
 {
-    const MeshRay r = to_mesh_space(in, org, dir);
-    const uint32_t vdelta = VIEW ? view_off + (uint32_t)p.view_inst_off[inst_index] : 0u;
+    // HDR (render_kernel<.., VIEW>): everything of the instance that is the same in every lane -- the origin in mesh space and whether
+    // it is finite, the mesh's flags, the root, the view delta -- comes from the (frame, instance) ray header the view pre-pass wrote, in
+    // one fetch through the scalar cache; the lane transforms its direction, with to_mesh_space's operations in their order.
+    static_assert(!HDR || (VIEW && UNIFORM_ORG && OCTANTS && !EX && !SEC && !PROF && !DEBUG), "ray headers: the timed primary kernels' view path");
+    const RayHeaderWords h = HDR ? ray_header(p, view_off, inst_index) : RayHeaderWords();
+    const MeshRay r = HDR ? to_mesh_space(h, dir) : to_mesh_space(in, org, dir);
+    const uint32_t vdelta = HDR ? h.vdelta : VIEW ? view_off + (uint32_t)p.view_inst_off[inst_index] : 0u;
     int oct = -1;
     if constexpr (!PROF && OCTANTS) {
         const float inf = __int_as_float(0x7f800000);
         const bool usable = fabsf(r.dinv.x) < inf && fabsf(r.dinv.y) < inf && fabsf(r.dinv.z) < inf &&
                             r.dinv.x != 0.0f && r.dinv.y != 0.0f && r.dinv.z != 0.0f &&
-                            fabsf(r.ro.x) < inf && fabsf(r.ro.y) < inf && fabsf(r.ro.z) < inf;
+                            (HDR || (fabsf(r.ro.x) < inf && fabsf(r.ro.y) < inf && fabsf(r.ro.z) < inf));    // (HDR: kRayOriginFinite)
         const int mine = (r.dinv.x < 0.0f ? 1 : 0) | (r.dinv.y < 0.0f ? 2 : 0) | (r.dinv.z < 0.0f ? 4 : 0);
         const int first = __builtin_amdgcn_readfirstlane(mine);
-        if ((p.mesh_flags[in.mesh_index] & 1) == 0 && __ballot(!usable || mine != first) == 0ull) oct = first;
+        if ((HDR ? (h.flags & (kRayOriginFinite | kRayBoxUnordered)) == kRayOriginFinite : (p.mesh_flags[in.mesh_index] & 1) == 0) &&
+            __ballot(!usable || mine != first) == 0ull) oct = first;
     }
     // SEC (round 6: a ray with an origin of its own per lane -- the ray queries' rays; an any-hit ray is done at its first hit -- on the
     // optimistic stack): the hand-written loop or nothing.  A wave it does not cover (mixed sign octants, an exact-uv mesh) leaves with sp != 0,
@@ -1088,11 +1135,11 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
     if constexpr (SEC) { if (!(oct >= 0 && in.exact_uv == 0)) { stack.sp = 1; return; } }
     if constexpr (OCTANTS && !DEBUG && !PROF && (UNIFORM_ORG || SEC) && (!EX || POPS) && !(POPS && COUNT) && (!ANYHIT || SEC) && !STK::kSpill) {
         // the hand-written loop (trace_loop_asm) for what it covers; everything else takes the C++ loops below
-        if (SEC || (oct >= 0 && in.exact_uv == 0)) {
-            if constexpr (STATS) { loop_stat(p, RT_LOOP_ASM); if (in.unit_inv == 0) loop_stat(p, RT_LOOP_ASM_POSED); }
+        if (SEC || (oct >= 0 && (HDR ? (h.flags & kRayExactUv) == 0 : in.exact_uv == 0))) {
+            if constexpr (STATS) { loop_stat(p, RT_LOOP_ASM); if (HDR ? (h.flags & kRayUnitInv) == 0 : in.unit_inv == 0) loop_stat(p, RT_LOOP_ASM_POSED); }
             stack.sp = 0;
             stack.push(kSentinel);
-            int32_t cur = in.root_ref, sp = stack.sp;
+            int32_t cur = HDR ? h.root_ref : in.root_ref, sp = stack.sp;
             int wave_iters = 0;
             static_assert(STK::kStride == 64 || STK::kStride == 256, "the stack column's row pitch as a shift");
             int no_pops = 0;
@@ -1102,8 +1149,8 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
             const int32_t instance_before = hit.instance;
             if constexpr (EX) hit.instance = -7;
             // (wave-uniform values read through the scalar cache: the instance record's address is uniform)
-            const V3 back = v3(in.inv_pose_xyz[0], in.inv_pose_xyz[1], in.inv_pose_xyz[2]);
-            const uintptr_t ia = in.unit_inv != 0 ? (uintptr_t)0 : (uintptr_t)&in;
+            const V3 back = HDR ? h.back : v3(in.inv_pose_xyz[0], in.inv_pose_xyz[1], in.inv_pose_xyz[2]);
+            const uintptr_t ia = (HDR ? (h.flags & kRayUnitInv) != 0 : in.unit_inv != 0) ? (uintptr_t)0 : (uintptr_t)&in;
             const DevInstance* general = (const DevInstance*)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ia >> 32)) << 32) |
                                                               (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ia));
 #define RT_TRACE_ASM(O) trace_loop_asm<O, COUNT, (STK::kStride == 64 ? 8 : 10), VIEW, POPS, EX, SEC, ANYHIT>(p, inst_index, r, org, stack.lds, stack.lds_depth, cur, sp, hit, wave_iters, vdelta, \
@@ -1228,7 +1275,7 @@ __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameP
         stack.lds = lds_column; stack.spill = nullptr; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
         int outgrown = 0;                                       // a loop left through the spare row ends with sp != 0
         for (int i = 0; i < p.num_instances; i++) {             // raycast.cu:26
-            trace_instance<DEBUG, PROF, false, COUNT, StackT<kPrimBlock, false, true>, false, true, false, VIEW, true, STATS>(p, p.instances[i], i, org, dir, stack, hit, cnt,
+            trace_instance<DEBUG, PROF, false, COUNT, StackT<kPrimBlock, false, true>, false, true, false, VIEW, true, STATS, false, VIEW>(p, p.instances[i], i, org, dir, stack, hit, cnt,
                                                                                                                          iters, nullptr, view_off);
             outgrown |= stack.sp;
         }
@@ -1247,7 +1294,7 @@ __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameP
         stack.lds = lds_column; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth); stack.sp = 0;
         if constexpr (STATS) loop_stat(p, RT_LOOP_WAVES);
         for (int i = 0; i < p.num_instances; i++)               // raycast.cu:26
-            trace_instance<DEBUG, PROF, false, COUNT, StackT<kPrimBlock, SPILL>, false, true, false, VIEW, true, STATS>(p, p.instances[i], i, org, dir, stack, hit, cnt, iters,
+            trace_instance<DEBUG, PROF, false, COUNT, StackT<kPrimBlock, SPILL>, false, true, false, VIEW, true, STATS, false, VIEW>(p, p.instances[i], i, org, dir, stack, hit, cnt, iters,
                                                                                                                nullptr, view_off);
     }
 
@@ -1288,10 +1335,11 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
 {
     extern __shared__ int lds_stack[];                          // [lds_block_rows(stack_depth)][kPrimBlock] (+ 2 ints when ORDERED)
 
-    // Workgroup b renders tile b (row-major).  Consecutive workgroups are dealt round-robin to the 8 XCDs, so every
+    // Workgroup (x, y) of frame z renders tile (x, y): row-major, as workgroups are dispatched -- the tile's coordinates need no
+    // division.  Consecutive workgroups are dealt round-robin to the 8 XCDs, so every
     // XCD sees tiles from the whole frame: measured faster than giving each XCD one contiguous band (better load
     // balance; the working set is L1/L2 resident either way).
-    int tile = (int)blockIdx.x, frame = (int)blockIdx.y;
+    int tile = (int)blockIdx.x, frame = ORDERED ? 0 : (int)blockIdx.z;
     int iters = 0;
     if constexpr (ORDERED) {
         // a one-dimensional grid: workgroup b renders frame b % F of the tile with rank b / F, so the costly tiles of ALL
@@ -1300,7 +1348,7 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
         tile = tile / p.num_frames;
         if (p.tile_order) tile = p.tile_order[tile];
     }
-    const int tx = tile % p.tiles_x, ty = tile / p.tiles_x;
+    const int tx = ORDERED ? tile % p.tiles_x : (int)blockIdx.x, ty = ORDERED ? tile / p.tiles_x : (int)blockIdx.y;
 
     unsigned long long t_start = 0;
     if (p.trace) t_start = wall_clock64();
@@ -1332,11 +1380,13 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
         }
     }
     if (p.trace && lane == 0) {                                 // diagnostic: per-wave lifetime (RT_TRACE_FILE)
-        unsigned long long* t = p.trace + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (kPrimBlock / 64) + wave) * 16;
+        // (the ordered grid is one-dimensional: its y and z are 0, and the two-term form keeps that kernel's code what it was)
+        const size_t wg = ORDERED ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : trace_workgroup();
+        unsigned long long* t = p.trace + (wg * (kPrimBlock / 64) + wave) * 16;
         t[0] = t_start; t[1] = wall_clock64();
         unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        t[2] = ((unsigned long long)xcc << 32) | hw; t[3] = (unsigned long long)tile;
+        t[2] = ((unsigned long long)xcc << 32) | hw; t[3] = (unsigned long long)(ORDERED ? tile : (int)(blockIdx.y * gridDim.x + blockIdx.x));
     }
 }
 
@@ -2127,6 +2177,8 @@ __global__ void set_instance_kernel(DevInstance* dst, const DevInstance value) {
 // instance, the instance's interior records with `box - origin` in place of the twelve box words -- origin = the frame's camera
 // position in the instance's mesh space, computed by the function the traversal uses (to_mesh_space), the subtraction being
 // the one box_differences does per visit: the same fp32 operation on the same operands, done once.  One thread per 16 bytes.
+// In front of a frame's view records stand its ray headers (RayHeader, rt_device_types.h), one 64-byte block per instance, written
+// by one thread each: that same origin and the instance fields a wave of render_kernel<.., VIEW> needs before its loop.
 struct ViewJob {
     int32_t n;                                  // instances
     int32_t first[kMaxViewInstances];           // first record of the instance's part of a frame's view
@@ -2140,16 +2192,33 @@ __global__ __launch_bounds__(256) void view_records_kernel(const RenderParams p,
     const int t = (int)(blockIdx.x * 256 + threadIdx.x), frame = (int)blockIdx.y;
     int rec = t >> 2;
     const int quarter = t & 3;
-    if (rec >= job.total) return;
+    const FrameParams& f = p.frames[frame];
+    char* view = (char*)p.records + p.view_base + (size_t)frame * p.view_frame_stride;
+    if (rec >= job.total) {
+        // the job.n threads behind the last record: the ray header of (frame, instance), see RayHeader
+        const int i = t - job.total * 4;
+        if (i >= job.n) return;
+        const DevInstance& in = p.instances[i];
+        const V3 o = to_mesh_space(in, v3(f.origin[0], f.origin[1], f.origin[2]), v3(0.0f, 0.0f, 1.0f)).ro;
+        const float inf = __int_as_float(0x7f800000);
+        const uint32_t flags = (fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf ? kRayOriginFinite : 0u) |
+                               ((p.mesh_flags[in.mesh_index] & kBoxUnordered) != 0 ? kRayBoxUnordered : 0u) |
+                               (in.exact_uv != 0 ? kRayExactUv : 0u) | (in.unit_inv != 0 ? kRayUnitInv : 0u);
+        const uint32_t vdelta = p.view_base + (uint32_t)frame * p.view_frame_stride + (uint32_t)p.view_inst_off[i];
+        float4* h = (float4*)view + (size_t)i * 4;
+        h[0] = make_float4(o.x, o.y, o.z, __uint_as_float(flags));
+        h[1] = make_float4(in.q_rot.x, in.q_rot.y, in.q_rot.z, in.q_rot.w);
+        h[2] = make_float4(in.inv_scale[0], in.inv_scale[1], in.inv_scale[2], __int_as_float(in.root_ref));
+        h[3] = make_float4(in.inv_pose_xyz[0], in.inv_pose_xyz[1], in.inv_pose_xyz[2], __uint_as_float(vdelta));
+        return;
+    }
     int i = 0;
     while (i + 1 < job.n && rec >= job.count[i]) { rec -= job.count[i]; i++; }
-    const FrameParams& f = p.frames[frame];
     const V3 o = to_mesh_space(p.instances[i], v3(f.origin[0], f.origin[1], f.origin[2]), v3(0.0f, 0.0f, 1.0f)).ro;
     float4 v = p.records[(size_t)(job.node_base[i] + rec) * 4 + quarter];
     if (quarter == 0) v = make_float4(v.x - o.x, v.y - o.y, v.z - o.z, v.w - o.x);          // the operand order of box_differences
     else if (quarter == 1) v = make_float4(v.x - o.y, v.y - o.z, v.z - o.x, v.w - o.y);
     else if (quarter == 2) v = make_float4(v.x - o.z, v.y - o.x, v.z - o.y, v.w - o.z);
-    char* view = (char*)p.records + p.view_base + (size_t)frame * p.view_frame_stride;
     ((float4*)view)[(size_t)(job.first[i] + rec) * 4 + quarter] = v;
 }
 
@@ -4960,9 +5029,12 @@ void view_decide(RtScene* s)
     int32_t cap = 0;
     for (const auto& rf : s->mesh_refit) cap = std::max(cap, rf.int_cap);
     // (an instance may be given another mesh later, rt_scene_update_instance: every instance gets room for the largest)
-    v.frame_records = cap * (int32_t)s->instances.size();
+    // ... behind the frame's ray headers, one 64-byte block per instance (view_records_kernel): they count as records of the view,
+    // so every size derived from frame_records (view_resize, rt_scene_reserve_views, rt_scene_memory) carries them
+    const int32_t headers = (int32_t)s->instances.size();
+    v.frame_records = headers + cap * (int32_t)s->instances.size();
     v.inst_first.resize(s->instances.size());
-    for (size_t i = 0; i < s->instances.size(); i++) v.inst_first[i] = (int32_t)i * cap;
+    for (size_t i = 0; i < s->instances.size(); i++) v.inst_first[i] = headers + (int32_t)i * cap;
     v.usable = cap > 0 && s->records_bytes > 0 && !s->instances.empty() && s->instances.size() <= (size_t)kMaxViewInstances &&
                s->records_bytes + (size_t)v.frame_records * 64 <= kViewMaxBytes;
 }
@@ -5051,7 +5123,7 @@ int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 
     p.view_base = (uint32_t)(v.base_bytes + (size_t)use * v.slot_frames * frame_bytes);
     p.view_frame_stride = (uint32_t)frame_bytes;
     for (int i = 0; i < job.n; i++) p.view_inst_off[i] = (int32_t)(((int64_t)job.first[i] - job.node_base[i]) * 64);
-    hipLaunchKernelGGL(view_records_kernel, dim3((unsigned)(((size_t)job.total * 4 + 255) / 256), (unsigned)p.num_frames), dim3(256), 0, stream, p, job);
+    hipLaunchKernelGGL(view_records_kernel, dim3((unsigned)(((size_t)job.total * 4 + (size_t)job.n + 255) / 256), (unsigned)p.num_frames), dim3(256), 0, stream, p, job);
     if (hipGetLastError() != hipSuccess) { count(&RtScene::ViewPool::fallbacks); return -1; }
     return use;
 }
@@ -5167,7 +5239,9 @@ int launch(RenderParams& p, bool debug, hipStream_t stream, int synchronize, RtS
     p.tiles_y = (p.local_rows + kPrimTile - 1) / kPrimTile;
     // (one size for whichever kernel is launched below: the spare row of the optimistic stack costs the instrumented kernels nothing)
     const size_t lds = (size_t)(lds_stack_suffices(p) ? lds_rows(p.stack_depth) : lds_block_rows<false, false, true>(p.stack_depth)) * kPrimBlock * sizeof(int);
-    dim3 grid((unsigned)(p.tiles_x * p.tiles_y), (unsigned)p.num_frames), block(kPrimBlock);
+    // tile (x, y) of frame z: the kernel takes its tile's coordinates from the workgroup's
+    const size_t ntiles = (size_t)p.tiles_x * p.tiles_y, nframes = (size_t)p.num_frames;
+    dim3 grid((unsigned)p.tiles_x, (unsigned)p.tiles_y, (unsigned)p.num_frames), block(kPrimBlock);
     const char* trace_file = getenv("RT_TRACE_FILE");                               // diagnostics only
     // Heavy-first dispatch (RT_TILE_ORDER=0 turns it off): for one frame per launch with enough tiles to have a tail worth
     // hiding.  Batches do not use it: the tail of one frame already overlaps the bulk of the next, and measured with the
@@ -5180,22 +5254,23 @@ int launch(RenderParams& p, bool debug, hipStream_t stream, int synchronize, RtS
         RtScene* s; int slot; hipStream_t stream;
         ~ViewDone() { view_done(s, slot, stream); }
     } view_guard{scene, view_slot, stream};
-    if (scene && !debug && (!trace_file || trace_ordered) && !p.hit_instance && !p.hit_triangle && grid.x >= 1024 && (size_t)grid.x * grid.y <= ((size_t)1 << 30)) {
+    if (scene && !debug && (!trace_file || trace_ordered) && !p.hit_instance && !p.hit_triangle && ntiles >= 1024 && ntiles * nframes <= ((size_t)1 << 30)) {
         static const bool enabled = [] { const char* e = getenv("RT_TILE_ORDER"); return !(e && e[0] == '0'); }();
         // ... and (round 6) a rank's STRIPES of a few frames: at eight ranks a group of 20 frames is two and a half frames' worth of
         // work per launch and ends, like a single frame, in a tail of a few long waves (RT_TILE_ORDER_STRIPES=0 turns this part off)
         static const bool stripes_too = [] { const char* e = getenv("RT_TILE_ORDER_STRIPES"); return !(e && e[0] == '0'); }();
-        const bool thin_stripes = stripes_too && p.num_ranks > 1 && p.num_frames > 1 && (size_t)grid.x * grid.y < (size_t)4 * 32768;
-        if (enabled && !stats && ((p.num_frames == 1 && grid.x >= 8192) || thin_stripes)) {   // (8x8-pixel tiles: half a million pixels)
+        const bool thin_stripes = stripes_too && p.num_ranks > 1 && p.num_frames > 1 && ntiles * nframes < (size_t)4 * 32768;
+        if (enabled && !stats && ((p.num_frames == 1 && ntiles >= 8192) || thin_stripes)) {   // (8x8-pixel tiles: half a million pixels)
             if (!trace_ordered) return launch_ordered(scene, p, stream, synchronize, view_slot >= 0);
-            const size_t n = (size_t)grid.x * (kPrimBlock / 64) * 16;
+            const size_t n = ntiles * nframes * (kPrimBlock / 64) * 16;
             RT_HIP(trace_begin(p, n));
             const int rc = launch_ordered(scene, p, stream, 1, false);
             const hipError_t e = trace_end(p, n, trace_file, stream);
             return rc ? rc : (int)e;
         }
     }
-    const size_t trace_n = (size_t)grid.x * grid.y * (kPrimBlock / 64) * 16;
+    if (p.tiles_y > 65535) return RT_E_INVALID;                 // (a grid's y and z end at 65 535: frames of more than 524 280 rows; the ordered grid above is one-dimensional)
+    const size_t trace_n = ntiles * nframes * (kPrimBlock / 64) * 16;
     if (trace_file) RT_HIP(trace_begin(p, trace_n));
     if (trace_file && getenv("RT_TRACE_PROF")) hipLaunchKernelGGL((render_kernel<false, true>), grid, block, lds, stream, p);
     else if (debug) hipLaunchKernelGGL((render_kernel<true, false>), grid, block, lds, stream, p);

@@ -103,8 +103,9 @@ struct RtScene {
     struct ViewPool {
         std::mutex m;                            // (statistics only: the pool itself is protected by RtScene::call_mu)
         bool decided = false, usable = false;    // static eligibility of the scene (instances, sizes), decided at the first launch
-        int32_t frame_records = 0;               // interior-record capacity of all instances = records of one frame's view
-        std::vector<int32_t> inst_first;         // per instance: first view record within a frame's view
+        int32_t frame_records = 0;               // 64-byte blocks of one frame's view: a ray header per instance (RayHeader), then
+                                                 // the interior-record capacity of all instances
+        std::vector<int32_t> inst_first;         // per instance: first view record within a frame's view (behind the headers)
         size_t base_bytes = 0;                   // byte offset of the pool from d_records
         int32_t slot_frames = 0;                 // frames a slot holds (0 = no pool yet)
         int32_t slots = 0;                       // slots of the pool (1..3)
