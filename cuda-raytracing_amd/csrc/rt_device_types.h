@@ -63,10 +63,6 @@ struct DevMaterial {            // Material.hpp:6-16
     float roughness, metallic;  // read only by the extension kernel (dead in the reference)
 };
 
-// wavefront path queues (ex_wave_kernel): a segment = the 64 slots one wave may push to, a group = exq_k segments
-constexpr int kExMaxGroup = 32;
-constexpr int kExPlanesA = 5, kExPlanesS = 7;
-
 constexpr int kMaxViewInstances = 8;    // scenes of more instances render without view records (RenderParams::view_inst_off)
 // Ray header of one (frame, instance) of a launch that renders through view records: what a wave of render_kernel<.., VIEW> needs
 // of the instance before its loop and what does not depend on the lane, in one 64-byte block that the wave fetches through the
@@ -129,24 +125,6 @@ struct RenderParams {
     int32_t px_n, px_count;     // sample slots per pixel in a wave (4..64, a power of two), samples of this launch (<= px_n)
     int32_t px_pw, px_ph;       // pixels of a wave; a workgroup is 2 x 2 waves
     int32_t px_first, px_last;  // first / last chunk of the frame's samples (running sums wait in ex_acc in between)
-    // render_ex_kernel<.., PHASE 1 / 2>: the camera ray's hit per lane, two planes of ex_rec_lanes float4 -- (slot, instance, u, v) and
-    // (location, pops) -- for the workgroups wg_base .. wg_base + gridDim.x of the frame's grid
-    float4* ex_rec;
-    uint32_t ex_rec_lanes;
-    int32_t wg_base;
-    // wavefront form of the extension renderer (ex_wave_kernel): path queues between casts, see rt_kernels.hip
-    float4* exq_s;              // shadow-ray items: kExPlanesS planes of exq_nseg * 64 float4
-    float4* exq_a[3];           // bounce-ray items: kExPlanesA planes each; three arrays in rotation (exq_in1 / in2 / out)
-    int32_t* exq_cnt_s;         // [segment] items in the segment (0..64)
-    int32_t* exq_cnt_a[3];
-    int32_t exq_nseg;           // segments per queue array = waves of the primary launch
-    int32_t exq_k;              // segments per group (<= 32): a group's paths stay in the group through every stage
-    int32_t exq_in1, exq_in2;   // A(depth) = the segments of exq_a[in1] (pushed by the cast launch of depth - 1) then those of exq_a[in2]
-                                // (pushed by its shadow launch; -1 = none)
-    int32_t exq_out;            // the exq_a array this launch pushes A(depth + 1) items to
-    int32_t depth;              // depth of the rays this launch casts
-    int32_t gen_samples;        // primary launch: sample indices in this chunk
-    int32_t gen_spw;            // primary launch: sample indices per workgroup (4, 2 or 1: one, two or four 8x8 quads)
     // render_kernel<.., VIEW>: the view record of interior record `e` of instance i in frame f is at byte offset
     // view_base + f * view_frame_stride + view_inst_off[i] + e * 64 from `records` (32-bit arithmetic; RtScene::ViewPool); the ray
     // header of instance i in frame f is at view_base + f * view_frame_stride + i * 64

@@ -12,9 +12,6 @@
  * Environment (diagnostics and tests only): RT_TRACE_FILE=<path> makes every render launch synchronise and write
  * per-wave start / end stamps there (tools/trace_one.py), with RT_TRACE_PROF=1 through a stamped copy of the kernel;
  * RT_EX_SCRATCH_BYTES=<n> overrides the scratch budget of rt_render_ex (forces the chunked path);
- * RT_EX_SPLIT=1 renders the camera ray of a path with bounces or lighting in a launch of its own (bit-identical, measured slower);
- * RT_EX_WAVEFRONT=1 renders bounces / lighting with one cast per launch and path queues in between (bit-identical, slower
- * on the measured workloads: DESIGN.md section 3), RT_EX_GROUP=<4..32> sets its queue group size;
  * RT_TILE_ORDER=0 turns the heavy-first dispatch order of single-frame launches off; RT_BVH_LIBRARY_SCAN=1 makes
  * rt_bvh_build use the partition path of meshes above 1 M triangles; RT_BVH_DEBUG=1 prints its phase timings;
  * RT_BVH_SMALL=k (0..64) lowers the size of the subtrees one wave finishes on its own (0: level loop only; tests);
@@ -25,7 +22,7 @@
  * RT_E_NOMEM before it touches anything (tests of the callers' error paths).
  * Round 6: RT_OVERLAP_PRIORITY=0 gives rt_render_overlapped two streams of equal priority (see there); RT_TILE_ORDER_STRIPES=0 keeps a
  * rank's thin striped batches in natural tile order; RT_VIEW_MAX_BYTES=<n> bounds a scene's view pool (default 1 GiB, see
- * rt_scene_reserve_views); RT_EX_SPLIT_BYTES=<n> bounds the records of the two-launch bounce form (tests: forces chunks).
+ * rt_scene_reserve_views).
  */
 #ifndef RT_HIP_H
 #define RT_HIP_H

@@ -1283,8 +1283,11 @@ def test_ex_modes_match_oracle(rt, orc, scenes, blob5k, spp, bounces, lighting):
 
 def test_ex_samples_in_chunks(rt, orc, scenes, blob5k, monkeypatch):
     """A frame whose sample data exceeds the scratch budget is rendered in chunks of sample indices (running sums kept
-    between chunks): forced here with a budget of 3 samples for 10 spp -> chunks of 3, 3, 3, 1; same frame, same pops."""
+    between chunks): forced here with a budget of 3 samples for 10 spp -> chunks of 3, 3, 3, 1; same frame, same pops.
+    Chunks of sample indices belong to the mapping with one sample index per launch row (RT_EX_PIXEL_WAVES=0): from 4 samples on the
+    default mapping returns before it reads the budget."""
     m = sd.SHINY_CAMERA
+    monkeypatch.setenv("RT_EX_PIXEL_WAVES", "0")
     monkeypatch.setenv("RT_EX_SCRATCH_BYTES", str(3 * m["width"] * m["height"] * 16))
     _compare_ex(rt, orc, sd.shiny_scene(scenes, blob5k), m["width"], m["height"], scenes.scaled_K(m["width"]), m["pose"], 10, 3, 1)
     monkeypatch.setenv("RT_EX_SCRATCH_BYTES", "1")                      # degenerate budget: one sample per chunk
@@ -1294,12 +1297,11 @@ def test_ex_samples_in_chunks(rt, orc, scenes, blob5k, monkeypatch):
 @pytest.mark.parametrize("spp,bounces,lighting,size", [(3, 2, 1, (200, 120)), (2, 5, 0, (203, 117)), (5, 0, 1, (64, 48)), (6, 4, 1, (333, 190)),
                                                        (16, 0, 0, (131, 77)), (33, 1, 1, (97, 61)), (70, 2, 1, (64, 48)), (130, 0, 0, (45, 31))])
 def test_ex_forms_are_bit_identical(rt, orc, scenes, blob5k, monkeypatch, spp, bounces, lighting, size):
-    """The three ways the extension renderer maps (pixel, sample) pairs to lanes -- a pixel's samples in one wave with the sum
-    taken there (the default from 4 samples on; more than 64 samples take several launches), one sample index per launch row with
-    sample planes and a resolve pass (RT_EX_PIXEL_WAVES=0), and the wavefront form (RT_EX_WAVEFRONT=1: one cast per launch, live
-    paths compacted between launches) -- give the same frame and the same
-    node-pop totals, and both equal the oracle -- also with small queue groups (4 segments), with the samples in chunks
-    of 2 and of 1 (the primary launch's workgroup then covers 2 or 4 pixel quads), and for a rank's stripes."""
+    """The two ways the extension renderer maps (pixel, sample) pairs to lanes -- a pixel's samples in one wave with the sum
+    taken there (the default from 4 samples on; more than 64 samples take several launches), and one sample index per launch row
+    with sample planes and a resolve pass (RT_EX_PIXEL_WAVES=0; what ships below 4 samples) -- give the same frame and the same
+    node-pop totals, and both equal the oracle -- also with the samples in chunks of 3 and of 1, and for a rank's stripes
+    through either mapping."""
     W, H = size
     desc = sd.shiny_scene(scenes, blob5k)
     K, pose = scenes.scaled_K(W), sd.SHINY_CAMERA["pose"]
@@ -1310,13 +1312,9 @@ def test_ex_forms_are_bit_identical(rt, orc, scenes, blob5k, monkeypatch, spp, b
     cam.set_pose(pose)
     cam.set_options(spp, bounces, lighting)
     # (the default from 4 samples on: a pixel's samples share a wave and are summed there; RT_EX_PIXEL_WAVES=0: one sample index per
-    # launch row, sample planes and a resolve pass)
-    # (round 6: RT_EX_SPLIT=1 renders the camera ray of a path with bounces or lighting in a launch of its own, render_ex_kernel<..,
-    # PHASE 1 / 2>; RT_EX_SPLIT_BYTES forces that form into chunks of 4 and of 12 workgroups)
-    variants = [{"RT_EX_SPLIT": "1"}, {"RT_EX_SPLIT": "1", "RT_EX_SPLIT_BYTES": "8192"}, {"RT_EX_SPLIT": "1", "RT_EX_SPLIT_BYTES": str(12 * 2048)},
-                {"RT_EX_PIXEL_WAVES": "0"}, {"RT_EX_PIXEL_WAVES": "0", "RT_EX_SCRATCH_BYTES": str(3 * W * H * 16)}, {"RT_EX_WAVEFRONT": "1"}, {"RT_EX_WAVEFRONT": "1", "RT_EX_GROUP": "4"},
-                {"RT_EX_WAVEFRONT": "1", "RT_EX_SCRATCH_BYTES": str(2 * (W + 16) * (H + 16) * 380)},
-                {"RT_EX_WAVEFRONT": "1", "RT_EX_SCRATCH_BYTES": "1"}]
+    # launch row, sample planes and a resolve pass -- whole, in chunks of 3 sample indices and with one sample index per chunk)
+    variants = [{"RT_EX_PIXEL_WAVES": "0"}, {"RT_EX_PIXEL_WAVES": "0", "RT_EX_SCRATCH_BYTES": str(3 * W * H * 16)},
+                {"RT_EX_PIXEL_WAVES": "0", "RT_EX_SCRATCH_BYTES": "1"}]
     for env in variants:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -1325,21 +1323,25 @@ def test_ex_forms_are_bit_identical(rt, orc, scenes, blob5k, monkeypatch, spp, b
             monkeypatch.delenv(k)
         assert np.array_equal(other["img"], got["img"]), env
         assert np.array_equal(other["total_pops"], got["total_pops"]), env
-    # a rank's stripes through the wavefront form
-    monkeypatch.setenv("RT_EX_WAVEFRONT", "1")
+    # a rank's stripes through the default mapping, then through the other one
     import importlib
     tiling = importlib.import_module("cuda-raytracing_amd.tiling")
     h = rt.libs()[0]
     world, stripe = 3, 16
     pitch = W * 3
     max_rows = max(tiling.stripe_rows(H, stripe, r, world) for r in range(world))
-    gathered = rt.DeviceBuffer(nbytes=world * max_rows * pitch)
-    for r in range(world):
-        cam.render_scene_stripes(sp, gathered.ptr.value + r * max_rows * pitch, pitch, stripe, r, world, synchronize=True)
-    out = rt.DeviceBuffer(width_bytes=W * 3, height=H)
-    rt.check(h.rt_unstripe(gathered.ptr, pitch, max_rows * pitch, out.ptr, out.pitch, W, H, stripe, world, None))
-    rt.check(h.rt_device_synchronize())
-    assert np.array_equal(out.to_host().reshape(H, W, 3), ref["img"])
+    for env in ({}, {"RT_EX_PIXEL_WAVES": "0"}):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        gathered = rt.DeviceBuffer(nbytes=world * max_rows * pitch)
+        for r in range(world):
+            cam.render_scene_stripes(sp, gathered.ptr.value + r * max_rows * pitch, pitch, stripe, r, world, synchronize=True)
+        out = rt.DeviceBuffer(width_bytes=W * 3, height=H)
+        rt.check(h.rt_unstripe(gathered.ptr, pitch, max_rows * pitch, out.ptr, out.pitch, W, H, stripe, world, None))
+        rt.check(h.rt_device_synchronize())
+        for k in env:
+            monkeypatch.delenv(k)
+        assert np.array_equal(out.to_host().reshape(H, W, 3), ref["img"]), env
 
 
 def test_c3_bunny_64spp_8bounces(rt, orc, scenes, blob70k):
@@ -1569,7 +1571,7 @@ def test_fuzz_random_scenes(rt, orc, scenes, blob5k, seed):
 @pytest.mark.parametrize("seed", range(_FUZZ_FIRST, _FUZZ_FIRST + max(4, int(os.environ.get("RT_FUZZ_SEEDS", 4)) // 3)))
 def test_fuzz_extension_modes(rt, orc, scenes, blob5k, seed, monkeypatch):
     """Random spp / bounces / lighting, random metallic / roughness, rotated and scaled instances: extension kernel vs oracle,
-    and its wavefront form (RT_EX_WAVEFRONT=1) vs both."""
+    in the default mapping and with one sample index per launch row (RT_EX_PIXEL_WAVES=0)."""
     rng = np.random.default_rng(7000 + seed)
     mats = [(tuple(rng.uniform(0.1, 1, 3)), sd.checker_texture(16, 12, seed=seed) if rng.random() < 0.5 else None,
              dict(roughness=float(rng.choice([0.0, 0.05, 0.3])), metallic=float(rng.choice([0.0, 0.3, 0.8])))) for _ in range(3)]
@@ -1580,10 +1582,7 @@ def test_fuzz_extension_modes(rt, orc, scenes, blob5k, seed, monkeypatch):
     opts = (int(rng.integers(1, 9)), int(rng.integers(0, 5)), int(rng.integers(0, 2)))
     desc = sd.SceneDesc(mats, meshes, inst)
     _compare_ex(rt, orc, desc, W, H, scenes.scaled_K(W), (0.2, -3.5, 0.5, 0.05, -0.1, 0.02), *opts)
-    monkeypatch.setenv("RT_EX_SPLIT", "1")                                 # (the two-launch form of the bounce kernel)
-    _compare_ex(rt, orc, desc, W, H, scenes.scaled_K(W), (0.2, -3.5, 0.5, 0.05, -0.1, 0.02), *opts)
-    monkeypatch.delenv("RT_EX_SPLIT")
-    monkeypatch.setenv("RT_EX_WAVEFRONT", "1")
+    monkeypatch.setenv("RT_EX_PIXEL_WAVES", "0")
     _compare_ex(rt, orc, desc, W, H, scenes.scaled_K(W), (0.2, -3.5, 0.5, 0.05, -0.1, 0.02), *opts)
 
 
@@ -1607,14 +1606,14 @@ def test_fuzz_adversarial_scenes(rt, orc, scenes, seed):
 def test_fuzz_adversarial_extension_modes(rt, orc, scenes, seed, monkeypatch):
     """The same awkward scenes through the extension kernel (random spp / bounces / lighting, rough and metallic materials): secondary rays
     that start at hits on zero-area triangles (NaN normals), mirrored and extreme scales, origins on the lattice.  Semantics are this
-    project's own: image and total pops against its oracle -- the default form, then one of the two opt-in forms
-    (two launches, RT_EX_SPLIT=1, on even seeds; the wavefront form, RT_EX_WAVEFRONT=1, on odd ones)."""
+    project's own: image and total pops against its oracle -- the default mapping, then the one with one
+    sample index per launch row (RT_EX_PIXEL_WAVES=0), on every seed."""
     rng = np.random.default_rng(47000 + seed)
     desc, W, H, K, cam_pose, info = _adversarial_scene(scenes, rng, shiny=True)
     opts = (int(rng.integers(1, 9)), int(rng.integers(0, 5)), int(rng.integers(0, 2)))
     print("seed", seed, info, "spp / bounces / lighting", opts)
     _compare_ex(rt, orc, desc, W, H, K, cam_pose, *opts, threads=4)
-    monkeypatch.setenv("RT_EX_SPLIT" if seed % 2 == 0 else "RT_EX_WAVEFRONT", "1")
+    monkeypatch.setenv("RT_EX_PIXEL_WAVES", "0")
     _compare_ex(rt, orc, desc, W, H, K, cam_pose, *opts, threads=4)
 
 

@@ -40,7 +40,7 @@ render = {"campaign": "adversarial differential fuzz, HIP path vs CPU oracle: aw
                    "power-of-two, mirrored, 1e2..1e4, 1e-4..1e-2 scales) x cameras (any, axis-parallel central rays, on the lattice, inside)",
        "test_fuzz_adversarial_scenes": {"seeds": [first, first + n], "rng": "numpy.random.default_rng(31000 + seed)", "gpu_built_tree": "seed % 3 == 2",
                                         "checked": "RGB + hit ids of the production kernel, six planes of the instrumented kernel, a batch of four frames through view records"},
-       "test_fuzz_adversarial_extension_modes": {"seeds": [first, first + max(4, n // 3)], "rng": "numpy.random.default_rng(47000 + seed)", "checked": "RGB + total pops; the default form, then the two-launch form (even seeds) or the wavefront form (odd seeds)"},
+       "test_fuzz_adversarial_extension_modes": {"seeds": [first, first + max(4, n // 3)], "rng": "numpy.random.default_rng(47000 + seed)", "checked": "RGB + total pops; the default mapping, then one sample index per launch row (RT_EX_PIXEL_WAVES=0), every seed"},
        "test_fuzz_adversarial_refit_and_rebuild": {"seeds": [first, first + max(4, n // 3)], "rng": "numpy.random.default_rng(59000 + seed)",
                                                    "checked": "all planes as uploaded, after a refit to another awkward mesh, after a device rebuild from a third"},
        "test_fuzz_adversarial_api_sequences": {"seeds": [first, first + max(4, n // 3)], "rng": "numpy.random.default_rng(67000 + seed)",

@@ -13,7 +13,7 @@ for d in sys.argv[1:]:
         k = int(r["Dispatch_Id"])
         e = disp.setdefault(k, {"kernel": r["Kernel_Name"], "grid": int(r["Grid_Size"]), "c": collections.defaultdict(float)})
         e["c"][r["Counter_Name"]] += float(r["Counter_Value"])
-    seq = [e for e in disp.values() if "ex_wave" in e["kernel"] or "render_ex" in e["kernel"] or "resolve" in e["kernel"]]
+    seq = [e for e in disp.values() if "render_ex" in e["kernel"] or "resolve" in e["kernel"]]
     # the last frame = after the last-but-one resolve ... keep it simple: index launches from the end
     for i, e in enumerate(reversed(seq)):
         row = rows.setdefault(i, {"kernel": e["kernel"], "grid": e["grid"]})
