@@ -71,6 +71,8 @@ _REGION_COUNT_OUTPUTS = ("count", "inside", "any", "pops")
 _REGION_LIST_OUTPUTS = ("instance", "triangle", "inside", "normal")
 _SEGMENT_OUTPUTS = ("distance", "instance", "triangle", "parameter", "segment_point", "point", "normal", "barycentric", "uv", "crossings",
                     "clearance", "within", "pops")
+_SWEEP_OUTPUTS = ("time", "distance", "instance", "triangle", "centre", "point", "normal", "contact_normal", "barycentric", "uv", "hit",
+                  "pops")
 _TRIANGLE_HIT_OUTPUTS = ("distance", "instance", "triangle", "query_barycentric", "query_point", "point", "normal", "barycentric", "uv",
                          "intersections", "clearance", "within", "pops")
 
@@ -131,6 +133,10 @@ class RtSegmentHits(C.Structure):           # include/rt_hip.h (device pointers,
     _fields_ = [(n, _vp) for n in _SEGMENT_OUTPUTS]
 
 
+class RtSweepHits(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL, at least one given)
+    _fields_ = [(n, _vp) for n in _SWEEP_OUTPUTS]
+
+
 class RtTriangleHits(C.Structure):          # include/rt_hip.h (device pointers, any may be NULL, at least one given)
     _fields_ = [(n, _vp) for n in _TRIANGLE_HIT_OUTPUTS]
 
@@ -154,7 +160,7 @@ RT_HIP_SYMBOLS = [
     "rt_count_intersecting", "rt_intersecting_offsets_workspace_bytes", "rt_intersecting_offsets", "rt_list_intersecting",
     "rt_count_in_boxes", "rt_box_offsets_workspace_bytes", "rt_box_offsets", "rt_list_in_boxes", "rt_occupancy_grid",
     "rt_count_sections", "rt_section_offsets_workspace_bytes", "rt_section_offsets", "rt_list_sections",
-    "rt_closest_to_segments", "rt_closest_to_triangles",
+    "rt_closest_to_segments", "rt_closest_to_triangles", "rt_sweep_spheres",
     "rt_count_in_regions", "rt_region_offsets_workspace_bytes", "rt_region_offsets", "rt_list_in_regions"]
 RT_HOST_SYMBOLS = [
     "rth_obj_load", "rth_obj_parse", "rth_scan_float", "rth_obj_load_for_device", "rth_mesh_from_triangles_for_device", "rth_obj_load_lenient", "rth_obj_load_gpu", "rth_mesh_from_triangles", "rth_mesh_from_triangles_gpu", "rth_mesh_single_triangle", "rth_mesh_free", "rth_mesh_num_triangles",
@@ -319,6 +325,7 @@ def _declare(h, s):
     h.rt_region_offsets.argtypes = [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     h.rt_list_in_regions.argtypes = [_vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.POINTER(RtRegionList), _vp, C.c_int]
     h.rt_closest_to_segments.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtSegmentHits), _vp, C.c_int]
+    h.rt_sweep_spheres.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtSweepHits), _vp, C.c_int]
     h.rt_closest_to_triangles.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(RtTriangleHits), _vp, C.c_int]
     h.rt_occupancy_grid.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_int]
     h.rt_camera_rays.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
@@ -894,6 +901,30 @@ class Scene:
             check(h.rt_closest_to_segments(handle, ins[0], ins[1], n, C.byref(hits), st, sync), "rt_closest_to_segments")
         return _device_query(self, [("segments", segments), ("max_distance", max_distance)], outputs, call, stream, **_SEGMENT_INPUTS)
 
+    SWEEP_OUTPUTS = _SWEEP_OUTPUTS                                      # the fields of RtSweepHits
+
+    def sweep_spheres(self, segments, radius, outputs=("time", "instance", "triangle"), stream=None):
+        """The first contact of a sphere whose centre moves from P0 to P1 with the scene: how far it can go, and what it touches there
+        (rt_sweep_spheres; the rule, bit for bit a brute-force loop over every instance and triangle, is rule 16 of include/rt_hip.h):
+        dict of the wanted SWEEP_OUTPUTS of the segments' leading shape -- time (float32 in [0, 1]: the centre stops at
+        P0 + time * (P1 - P0); 0 where the sphere starts in contact; FLT_MAX on a miss), distance (float32: the centre's distance from
+        the contact point, the radius up to rounding, less where it starts in contact; FLT_MAX on a miss), instance / triangle (int32,
+        -1 on a miss), centre / point ([3] float32, world: the sphere's centre at contact and the contact point), normal ([3]: the
+        face normal as closest_points gives it), contact_normal ([3]: the unit vector from point towards centre), barycentric / uv
+        ([2]) of the contact point, hit (int32 0 / 1; wanted alone or with pops, the traversal stops at the first contact found), pops
+        (int32, interior nodes visited).  A sphere that starts in contact reports the nearest triangle to P0, as
+        closest_points(P0, max_distance=radius) does.  segments: float32 [..., 2, 3] world positions of the centre, contiguous.
+        radius: float32 of the leading shape, required (inclusive; NaN or negative = no contact).  torch tensors: asynchronous on
+        `stream` (default the current stream); numpy arrays: copied to the device and back, the call synchronises."""
+        outputs = _check_outputs(outputs, self.SWEEP_OUTPUTS)
+        if radius is None:
+            raise ValueError("radius is required: float32 of the segments' leading shape")
+
+        def call(h, handle, ins, ptr, n, st, sync):
+            hits = RtSweepHits(*[ptr.get(k) for k in _SWEEP_OUTPUTS])
+            check(h.rt_sweep_spheres(handle, ins[0], ins[1], n, C.byref(hits), st, sync), "rt_sweep_spheres")
+        return _device_query(self, [("segments", segments), ("radius", radius)], outputs, call, stream, **_SEGMENT_INPUTS)
+
     TRIANGLE_HIT_OUTPUTS = _TRIANGLE_HIT_OUTPUTS                        # the fields of RtTriangleHits
 
     def closest_to_triangles(self, triangles, max_distance=None, skip_instance=None, outputs=("distance", "instance", "triangle"),
@@ -1232,7 +1263,8 @@ _FIELDS = dict(
     any=((), np.bool_), occupied=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
     point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32), parameter=((), np.float32),
     segment_point=((3,), np.float32), crossings=((), np.int32), clearance=((), np.float32), within=((), np.int32),
-    query_barycentric=((2,), np.float32), query_point=((3,), np.float32), intersections=((), np.int32), inside=((), np.int32))
+    query_barycentric=((2,), np.float32), query_point=((3,), np.float32), intersections=((), np.int32), inside=((), np.int32),
+    time=((), np.float32), centre=((3,), np.float32), contact_normal=((3,), np.float32), hit=((), np.int32))
 
 
 def _check_outputs(outputs, allowed, extras=()):

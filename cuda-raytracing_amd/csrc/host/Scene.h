@@ -27,6 +27,7 @@ struct RtSectionCounts;
 struct RtSectionList;
 struct RtSegmentHits;
 struct RtTriangleHits;
+struct RtSweepHits;
 struct RtRegionCounts;
 struct RtRegionList;
 
@@ -126,6 +127,10 @@ public:
     // Returns the status.
     int closest_to_triangles(const float* d_triangles, const float* d_max_distance, const int32_t* d_skip_instance, int32_t n,
                              const RtTriangleHits& out, void* stream = nullptr, bool synchronize = false);
+    // Sphere sweeps on the device scene: rt_sweep_spheres of include/rt_hip.h (rule 16), where the semantics are.  Segments
+    // ([n][2][3] world, the centre's P0 then P1), radii ([n], required) and outputs are DEVICE arrays.  Returns the status.
+    int sweep_spheres(const float* d_segments, const float* d_radius, int32_t n, const RtSweepHits& out, void* stream = nullptr,
+                      bool synchronize = false);
     // Region queries on the device scene: rt_count_in_regions / rt_region_offsets / rt_list_in_regions of include/rt_hip.h (rule 15,
     // rooms), where the semantics are.  Regions ([n][planes_per_region][2][3] world, point then inward normal), offsets, workspace
     // and outputs are DEVICE arrays.  Return the status.

@@ -764,6 +764,12 @@ int Scene::closest_to_triangles(const float* d_triangles, const float* d_max_dis
     return last_error;
 }
 
+int Scene::sweep_spheres(const float* d_segments, const float* d_radius, int32_t n, const RtSweepHits& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_sweep_spheres(d_scene, d_segments, d_radius, n, &out, stream, synchronize ? 1 : 0) : RT_E_INVALID;
+    return last_error;
+}
+
 int Scene::count_in_regions(const float* d_regions, int32_t n, int32_t planes_per_region, const RtRegionCounts& out, void* stream,
                             bool synchronize)
 {

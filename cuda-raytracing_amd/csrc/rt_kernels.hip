@@ -2865,6 +2865,247 @@ __global__ __launch_bounds__(kPointBlock, 8) void triangle_closest_kernel(const 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Sphere sweeps (rt_sweep_spheres): the first contact of a sphere of radius r whose centre moves from P0 to P1, equal bit for bit to
+// a brute-force loop over every (instance, triangle) -- rule 16 of include/rt_hip.h, the pruning argument in DESIGN.md section 22.
+// segment_closest_kernel's shape: one wave per workgroup, one sweep per lane, the general stack, instances in ascending order.  The
+// lower bound is between the child's box and the box of the path up to the best time so far, which shrinks as the winner improves;
+// the children are visited nearer-to-Q0 first.  The leaf (eight candidate times, each priced by pq_weights) is one out-of-line
+// routine that maps the ends itself, as td_triangle does: the node loop holds the path's box, Q0 and the bound, nothing else.
+// ---------------------------------------------------------------------------------------------------------
+struct SweepParams {
+    const float4* records;
+    const float* tri_uv;
+    const int32_t* tri_id;
+    const int32_t* leaf_count;
+    const int32_t* mesh_flags;
+    const DevInstance* instances;
+    int32_t num_instances;
+    int32_t stack_depth;
+    const float* segs;          // [n][2][3] world positions of the centre: P0 then P1
+    const float* radius;        // [n]
+    int32_t n;
+    float *time, *distance;     // outputs, each optional (null = not wanted)
+    int32_t *instance, *triangle;
+    float *centre, *point, *normal, *contact_normal, *barycentric, *uv;
+    int32_t *hit, *pops;
+};
+
+// rule 16 step 3's constants: reach = (r + r * kSweepKR) + M * kSweepKM (DESIGN.md section 22 has the measurement that fixes them)
+constexpr float kSweepKR = 0x1p-20f, kSweepKM = 0x1p-20f;
+
+__device__ __forceinline__ float sw_absmax(float m, float x) { const float a = fabsf(x); return a > m ? a : m; }      // (a NaN is passed over)
+__device__ __forceinline__ float sw_reach2(float r, V3 q0, V3 q1)
+{
+    float m = 0.0f;
+    m = sw_absmax(m, q0.x); m = sw_absmax(m, q0.y); m = sw_absmax(m, q0.z);
+    m = sw_absmax(m, q1.x); m = sw_absmax(m, q1.y); m = sw_absmax(m, q1.z);
+    const float rw = (r + r * kSweepKR) + m * kSweepKM;
+    return rw * rw;
+}
+// the ends g = (P0, P1) in instance `in`'s scaled mesh space (read again wherever they are needed: not held across the traversal)
+__device__ __forceinline__ void sw_ends(const float* g, const DevInstance& in, V3& q0, V3& q1)
+{
+    q0 = apply_quat(in.q_pose, v3(g[0] - in.pose_xyz[0], g[1] - in.pose_xyz[1], g[2] - in.pose_xyz[2]));
+    q1 = apply_quat(in.q_pose, v3(g[3] - in.pose_xyz[0], g[4] - in.pose_xyz[1], g[5] - in.pose_xyz[2]));
+}
+__device__ __forceinline__ V3 sw_along(V3 p, float s, V3 d) { return v3(p.x + s * d.x, p.y + s * d.y, p.z + s * d.z); }
+__device__ __forceinline__ V3 sw_off(V3 p, float s, V3 d) { return v3(p.x - s * d.x, p.y - s * d.y, p.z - s * d.z); }
+
+// rule 16 steps 2-3 on one scene triangle: (s, b1, b2, d2) of its candidate, s = -1 when it has none.  lim: the lane's best time so
+// far (1 without one); a candidate time above it cannot win and is not priced.  Out of line and not unrolled: one pq_weights in the
+// code whichever candidate is priced.
+__device__ __noinline__ float4 sw_triangle(const float* g, float r, const DevInstance& in, V3 a, V3 ab, V3 ac, float lim)
+{
+    V3 q0, q1;
+    sw_ends(g, in, q0, q1);
+    const float reach2 = sw_reach2(r, q0, q1), r2 = r * r;
+    const V3 d = q1 - q0;
+    const float aa = dot(d, d);
+    float4 best = make_float4(-1.0f, 0.0f, 0.0f, 0.0f);
+    const int count = aa > 0.0f ? 8 : 1;                        // (a zero-length sweep has the start alone)
+#pragma unroll 1
+    for (int k = 0; k < count; k++) {
+        float s = __int_as_float(0x7fc00000);                   // (no root: fails the compares below)
+        if (k == 0) {
+            s = 0.0f;
+        } else if (k == 1) {                                    // the face: the plane offset by r on Q0's side, approached
+            const V3 n = v3(ab.y * ac.z - ab.z * ac.y, ab.z * ac.x - ab.x * ac.z, ab.x * ac.y - ab.y * ac.x);
+            const float m = sw_absmax(sw_absmax(sw_absmax(0.0f, n.x), n.y), n.z);
+            if (m > 0.0f) {
+                const V3 u = v3(n.x / m, n.y / m, n.z / m);
+                const float lu = sqrtf(pq_d2(u)), h0 = dot(u, q0 - a), vn = dot(u, d);
+                float gap = 0.0f, v = 0.0f;
+                if (h0 >= 0.0f) { gap = h0 - r * lu; v = -vn; }
+                else if (h0 < 0.0f) { gap = -h0 - r * lu; v = vn; }
+                if (v > 0.0f) s = gap / v;
+            }
+        } else if (k < 5) {                                     // an edge's line: the cylinder of radius r about it, entry root
+            const V3 e0 = k == 4 ? a + ab : a, f = k == 2 ? ab : (k == 3 ? ac : ac - ab);
+            const float ff = dot(f, f);
+            if (ff > 0.0f) {
+                const V3 w = q0 - e0;
+                const float td = dot(d, f) / ff, tw = dot(w, f) / ff;
+                const V3 dp = sw_off(d, td, f), wp = sw_off(w, tw, f);
+                const float ap = dot(dp, dp);
+                if (ap > 0.0f) {
+                    const float smid = -dot(wp, dp) / ap, dp2 = pq_d2(sw_along(wp, smid, dp));
+                    if (dp2 <= r2) s = smid - sqrtf((r2 - dp2) / ap);
+                }
+            }
+        } else {                                                // a vertex: the sphere of radius r about it, entry root
+            const V3 w = q0 - (k == 5 ? a : (k == 6 ? a + ab : a + ac));
+            const float smid = -dot(w, d) / aa, dp2 = pq_d2(sw_along(w, smid, d));
+            if (dp2 <= r2) s = smid - sqrtf((r2 - dp2) / aa);
+        }
+        if (!(s >= 0.0f && s <= lim)) continue;                 // (lim <= 1; a NaN fails)
+        if (best.x >= 0.0f && !(s < best.x)) continue;          // (the first of equals stays)
+        const V3 x = sw_along(q0, s, d);
+        const float2 bw = pq_weights(x, a, ab, ac);
+        const float d2 = pq_d2(x - pq_combine(a, ab, ac, bw.x, bw.y));
+        if (d2 <= reach2) {                                     // step 3: valid (a NaN fails)
+            best = make_float4(s, bw.x, bw.y, d2);
+            if (k == 0) break;                                  // (nothing is earlier than the start)
+        }
+    }
+    return best;
+}
+
+// the box of the path from Q0 to the end of what can still win -- Q1 without a winner, else E = Q0 + s_lim * D as rule 16 computes an
+// X (every X with s <= s_lim lies between Q0 and E per axis: rounding is monotone) -- widened as sq_interval does it; Q0; step 3's bound
+__device__ __forceinline__ void sw_path(const float* g, const DevInstance& in, float r, bool got, float s_lim, V3& slo, V3& shi, V3& q0,
+                                        float& reach2)
+{
+    V3 q1;
+    sw_ends(g, in, q0, q1);
+    reach2 = sw_reach2(r, q0, q1);
+    if (got) q1 = sw_along(q0, s_lim, q1 - q0);
+    sq_interval(q0.x, q1.x, slo.x, shi.x); sq_interval(q0.y, q1.y, slo.y, shi.y); sq_interval(q0.z, q1.z, slo.z, shi.z);
+}
+
+// ANY: only hit and / or pops are wanted: the traversal ends at the first valid candidate, across instances too
+template <bool ANY>
+__global__ __launch_bounds__(kPointBlock, 8) void sweep_kernel(const SweepParams p)
+{
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth)][kPointBlock]
+    const int32_t i = (int32_t)blockIdx.x * kPointBlock + (int32_t)threadIdx.x;     // (< n <= INT32_MAX: no overflow)
+    if (i >= p.n) return;
+    const size_t i3 = (size_t)i * 3;
+    const float* g = p.segs + (size_t)i * 6;
+    const float r = p.radius[i];
+    int spill[kMaxStack - kLdsStack];
+    PointStack stack = query_stack(lds_stack, spill, p.stack_depth);
+    // the best candidate so far by (s, d2, instance, tri_id); best_inst < 0 = none yet
+    float bs = 1.0f, best = 0.0f, b1 = 0.0f, b2 = 0.0f;
+    int32_t best_inst = -1, best_slot = 0, best_tid = 0, pops = 0;
+    for (int32_t k = 0; k < p.num_instances && r >= 0.0f && !(ANY && best_inst >= 0); k++) {       // (a NaN or negative radius: no contact)
+        const DevInstance& in = p.instances[k];
+        V3 slo, shi, q0;
+        float reach2;
+        sw_path(g, in, r, best_inst >= 0, bs, slo, shi, q0, reach2);
+        const V3 s = v3(in.scale[0], in.scale[1], in.scale[2]);
+        const bool prune = (p.mesh_flags[in.mesh_index] & kBoxUnordered) == 0;      // (unordered / NaN boxes: no pruning in this mesh)
+        stack.sp = 0;
+        stack.push(kSentinel);
+        int32_t cur = in.root_ref, rem = -1;
+        do {
+            if (cur >= 0) {                                     // interior node: both child boxes, nearer to Q0 first
+                pops++;
+                const float4* rec = p.records + (size_t)cur * 4;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                const float la = sq_box_lb(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, slo, shi);
+                const float lb = sq_box_lb(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, slo, shi);
+                // a contact at time 0 is beaten only by a smaller d2 at time 0 (equal is kept); otherwise by anything valid in the box
+                const float lim = (best_inst >= 0 && bs == 0.0f) ? best : reach2;
+                const bool pa = !(prune && la > lim), pb = !(prune && lb > lim);
+                const int32_t ra = __float_as_int(r3.x), rb = __float_as_int(r3.y);
+                bool a_near = true;
+                if (pa && pb) {
+                    a_near = !(pq_box_lb(r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, s, q0) < pq_box_lb(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, s, q0));
+                    stack.push(a_near ? rb : ra);
+                }
+                cur = (pa && pb) ? (a_near ? ra : rb) : (pa ? ra : (pb ? rb : kNeedPop));
+            } else {                                            // one triangle of a leaf per iteration
+                const int32_t slot = cur & kSlotMask;
+                if (rem < 0) {
+                    rem = (cur >> kSlotBits) & 31;
+                    if (rem == 31) rem = p.leaf_count[slot];    // (leaves of more than 30 triangles)
+                }
+                if (rem > 0) {
+                    const float4* rec = p.records + (size_t)slot * 4;
+                    const float4 t0 = rec[0], t1 = rec[1], t2 = rec[2];
+                    V3 a, ab, ac;
+                    pq_triangle(t0, t1, t2, s, a, ab, ac);
+                    const float4 c = sw_triangle(g, r, in, a, ab, ac, bs);
+                    if (c.x >= 0.0f) {                          // a valid candidate at a time <= bs
+                        const int32_t tid = p.tri_id[slot];
+                        const bool sooner = best_inst < 0 || c.x < bs;
+                        if (sooner || c.w < best || (c.w == best && best_inst == k && tid < best_tid)) {
+                            bs = c.x; best = c.w; b1 = c.y; b2 = c.z; best_inst = k; best_slot = slot; best_tid = tid;
+                            if (sooner && !ANY) sw_path(g, in, r, true, bs, slo, shi, q0, reach2);  // the path's box shrinks
+                        }
+                    }
+                }
+                rem--;
+                cur = rem > 0 ? cur + 1 : kNeedPop;
+                rem = rem > 0 ? rem : -1;
+            }
+            if (cur == kNeedPop) cur = stack.pop();
+        } while (cur != kSentinel && !(ANY && best_inst >= 0));
+    }
+    const bool got = best_inst >= 0;
+    if (p.pops) p.pops[i] = pops;
+    if (p.hit) p.hit[i] = got ? 1 : 0;
+    if constexpr (ANY) return;
+    if (p.time) p.time[i] = got ? bs : FLT_MAX;
+    if (p.distance) p.distance[i] = got ? sqrtf(best) : FLT_MAX;
+    if (p.instance) p.instance[i] = got ? best_inst : -1;
+    if (p.triangle) p.triangle[i] = got ? best_tid : -1;
+    if (p.barycentric) { p.barycentric[(size_t)i * 2] = got ? b1 : 0.0f; p.barycentric[(size_t)i * 2 + 1] = got ? b2 : 0.0f; }
+    if (!got) {
+        if (p.centre) { p.centre[i3] = 0.0f; p.centre[i3 + 1] = 0.0f; p.centre[i3 + 2] = 0.0f; }
+        if (p.point) { p.point[i3] = 0.0f; p.point[i3 + 1] = 0.0f; p.point[i3 + 2] = 0.0f; }
+        if (p.normal) { p.normal[i3] = 0.0f; p.normal[i3 + 1] = 0.0f; p.normal[i3 + 2] = 0.0f; }
+        if (p.contact_normal) { p.contact_normal[i3] = 0.0f; p.contact_normal[i3 + 1] = 0.0f; p.contact_normal[i3 + 2] = 0.0f; }
+        if (p.uv) { p.uv[(size_t)i * 2] = 0.0f; p.uv[(size_t)i * 2 + 1] = 0.0f; }
+        return;
+    }
+    const DevInstance& in = p.instances[best_inst];
+    V3 fn = v3(0.0f, 0.0f, 0.0f);
+    if (p.normal || p.contact_normal) fn = pq_normal(p, in, best_slot);
+    if (p.normal) { p.normal[i3] = fn.x; p.normal[i3 + 1] = fn.y; p.normal[i3 + 2] = fn.z; }
+    if (p.centre || p.point || p.contact_normal) {              // the winner's X and c again (the same sequences)
+        V3 q0, q1, a, ab, ac;
+        sw_ends(g, in, q0, q1);
+        const V3 x = sw_along(q0, bs, q1 - q0);
+        const float4* rec = p.records + (size_t)best_slot * 4;
+        pq_triangle(rec[0], rec[1], rec[2], v3(in.scale[0], in.scale[1], in.scale[2]), a, ab, ac);
+        const V3 c = pq_combine(a, ab, ac, b1, b2);
+        if (p.centre) {                                         // to world: apply_lre(inv_pose, X), segment_point's map
+            const V3 o = apply_quat(in.q_inv_pose, v3(x.x - in.inv_pose_xyz[0], x.y - in.inv_pose_xyz[1], x.z - in.inv_pose_xyz[2]));
+            p.centre[i3] = o.x; p.centre[i3 + 1] = o.y; p.centre[i3 + 2] = o.z;
+        }
+        if (p.point) {
+            const V3 o = apply_quat(in.q_inv_pose, v3(c.x - in.inv_pose_xyz[0], c.y - in.inv_pose_xyz[1], c.z - in.inv_pose_xyz[2]));
+            p.point[i3] = o.x; p.point[i3 + 1] = o.y; p.point[i3 + 2] = o.z;
+        }
+        if (p.contact_normal) {                                 // (X - c) / sqrtf(d2) rotated to world; the face normal where d2 is not > 0
+            if (best > 0.0f) {
+                const float len = sqrtf(best);
+                const V3 e = x - c;
+                fn = apply_quat(in.q_inv_rot, v3(e.x / len, e.y / len, e.z / len));
+            }
+            p.contact_normal[i3] = fn.x; p.contact_normal[i3 + 1] = fn.y; p.contact_normal[i3 + 2] = fn.z;
+        }
+    }
+    if (p.uv) {                                                 // w = (1 - b2) - b1, uv = (w uv0 + b1 uv1) + b2 uv2 (closest_point_kernel's)
+        const float* t = p.tri_uv + (size_t)best_slot * 6;
+        const float u0 = (1.0f - b2) - b1;
+        p.uv[(size_t)i * 2] = (u0 * t[0] + b1 * t[2]) + b2 * t[4];
+        p.uv[(size_t)i * 2 + 1] = (u0 * t[1] + b1 * t[3]) + b2 * t[5];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Ray crossing counts and winding numbers (rt_count_crossings / rt_winding_numbers / rt_signed_distance): every triangle a ray
 // crosses within (0, tmax], both faces, with the sign of the crossing -- equal to a brute-force count over every (instance,
 // triangle); the rule is in include/rt_hip.h, the pruning argument in DESIGN.md section 12.  One wave per workgroup, one ray (or
@@ -6073,6 +6314,30 @@ int rt_closest_to_segments(RtScene* s, const float* d_segments, const float* d_m
             const QueryShape c = query_shape(n, kCrossBlock, p.stack_depth);
             hipLaunchKernelGGL(segment_crossing_kernel, c.groups, dim3(kCrossBlock), c.lds, st, p);
         }
+        return RT_OK;
+    });
+}
+
+// ---- sphere sweeps ----------------------------------------------------------------------------------------------------------
+int rt_sweep_spheres(RtScene* s, const float* d_segments, const float* d_radius, int32_t n, const RtSweepHits* out, void* stream,
+                     int synchronize)
+{
+    if (!s || n < 0 || (n > 0 && (!d_segments || !d_radius || !out))) return RT_E_INVALID;
+    if (n == 0) return RT_OK;                                    // nothing launched
+    // what only the full traversal gives; hit and pops alone end at the first valid candidate
+    const bool full = out->time || out->distance || out->instance || out->triangle || out->centre || out->point || out->normal ||
+                      out->contact_normal || out->barycentric || out->uv;
+    if (!full && !out->hit && !out->pops) return RT_E_INVALID;
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        SweepParams p = scene_params<SweepParams>(s);
+        p.tri_uv = s->d_tri_uv; p.tri_id = s->d_tri_id;
+        p.segs = d_segments; p.radius = d_radius; p.n = n;
+        p.time = out->time; p.distance = out->distance; p.instance = out->instance; p.triangle = out->triangle; p.centre = out->centre;
+        p.point = out->point; p.normal = out->normal; p.contact_normal = out->contact_normal; p.barycentric = out->barycentric;
+        p.uv = out->uv; p.hit = out->hit; p.pops = out->pops;
+        const QueryShape k = query_shape(n, kPointBlock, p.stack_depth);
+        if (full) hipLaunchKernelGGL(sweep_kernel<false>, k.groups, dim3(kPointBlock), k.lds, st, p);
+        else hipLaunchKernelGGL(sweep_kernel<true>, k.groups, dim3(kPointBlock), k.lds, st, p);
         return RT_OK;
     });
 }

@@ -942,6 +942,72 @@ typedef struct RtTriangleHits { /* every pointer optional (NULL = not wanted), a
 int rt_closest_to_triangles(RtScene *scene, const float *d_triangles, const float *d_max_distance, const int32_t *d_skip_instance,
                             int32_t n, const RtTriangleHits *out, void *stream, int synchronize);
 
+/* ---- sphere sweeps: the FIRST CONTACT of a sphere of radius r whose centre moves from P0 to P1 -- how far a
+ *      character, a camera boom, a robot link or a tool can go before it touches the scene, and where it touches.  The moving form
+ *      of rt_closest_to_segments' capsule test: the result equals a brute-force loop over every (instance, triangle) bit for bit,
+ *      whatever the tree (host-built, device-built, refitted) and whatever the traversal order.
+ *      16. For query j with the world positions P0, P1 of the centre (fp32), the radius r = radius[j] and instance i; every operation
+ *          fp32 in one fixed sequence, no contraction; dot and d2 = (x*x + y*y) + z*z as in rule 13.  The radius is inclusive; a NaN or
+ *          negative radius gives no contact (-0 counts as 0).
+ *          1. Map: Q0, Q1 and D = Q1 - Q0 by rule 13 step 1.  The map is rigid, so r and the path parameter s mean the same in every
+ *             instance and results compare across instances.  a = dot(D, D), r2 = r*r.
+ *             M = the largest of |Q0.x|, |Q0.y|, |Q0.z|, |Q1.x|, |Q1.y|, |Q1.z| (taken by compares from 0: a NaN is passed over);
+ *             reach = (r + r*2^-20) + M*2^-20;  reach2 = reach*reach.
+ *          2. Scene triangle: A, AB, AC of rule 2; its edges (E0, F) are rule 13's in rule 13's order, its vertices A, A + AB, A + AC
+ *             (fp32 sums).  Eight candidate TIMES s per triangle, in this order; a candidate counts only when 0 <= s <= 1 by compares:
+ *             (0) the start: s = 0.
+ *             (1) the face: N = (AB.y*AC.z - AB.z*AC.y, AB.z*AC.x - AB.x*AC.z, AB.x*AC.y - AB.y*AC.x); m = the largest |N_k| (as M
+ *                 above); only when m > 0: U = N / m per component, lu = sqrtf(d2(U)), h0 = dot(U, Q0 - A), vn = dot(U, D);
+ *                 h0 >= 0: g = h0 - r*lu, v = -vn;  h0 < 0: g = -h0 - r*lu, v = vn;  (neither: no candidate);  only when v > 0: s = g / v.
+ *                 (The centre reaches the plane offset by r on Q0's side, moving towards it.  U keeps the squares in range for
+ *                 coordinates from 1e-10 to 1e10.)
+ *             (2-4) the edges' lines: only when ff = dot(F, F) > 0: w = Q0 - E0, tD = dot(D, F) / ff, tw = dot(w, F) / ff,
+ *                 D' = D - tD*F, w' = w - tw*F per component (the product rounded, then the difference), a' = dot(D', D'); only when
+ *                 a' > 0: s_mid = -dot(w', D') / a', d'2 = d2(w' + s_mid*D'); only when d'2 <= r2: s = s_mid - sqrtf((r2 - d'2) / a').
+ *             (5-7) the vertices V: only when a > 0: w = Q0 - V, s_mid = -dot(w, D) / a, d'2 = d2(w + s_mid*D); only when d'2 <= r2:
+ *                 s = s_mid - sqrtf((r2 - d'2) / a).
+ *             (1-7) are taken only when a > 0: a sweep of zero length (or one whose squared length underflows) has the start alone.
+ *             The edge and vertex roots are the closest-approach form, not (-b - sqrt(b*b - a*c)) / a: s_mid is the parameter of the
+ *             line's nearest point to the feature and d'2 the squared distance there from the difference vector itself, so nothing
+ *             cancels when the sphere starts many radii away.  Nothing divides by a value that a compare has not shown to be > 0.
+ *          3. Verification: every candidate time is priced as rule 13 prices a candidate: X = Q0 + s*D per component (the product
+ *             rounded, then the sum), (b1, b2) = rule 2's weights for the point X, c = (A + b1*AB) + b2*AC, d2 = d2(X - c).  It is
+ *             VALID when d2 <= reach2 (a NaN fails).  No feature-region test is needed: a face root whose contact lies off the
+ *             triangle, or an edge root beyond the edge's ends, has the centre farther than r from the triangle and fails.  The
+ *             triangle's candidate is the valid one with the smallest s, the first of equals in the order above.
+ *          4. The winner is the triangle candidate with the smallest (s, d2, instance, triangle).  With s = 0 (a sphere that starts
+ *             in contact) the second component makes it the nearest triangle to P0: wherever rt_closest_points(P0, max_distance = r)
+ *             has a winner, the sweep reports time 0 with the same instance, triangle, barycentrics and point, bit for bit (the start
+ *             candidate is rule 2 on Q0, and reach2 is never below rule 4's bound for r).
+ *          5. NON-FINITE queries do not fault and do not change other queries' results; their own results are unspecified.
+ *          NOT PROMISED: the contact is decided in fp32.  The sphere's true distance at the reported time differs from r by a few
+ *          ulps of r + M (DESIGN.md section 22 has the measurement); a path that comes within that of a triangle without crossing
+ *          into it may be reported either way.  The constants are the smallest that lost no contact in that measurement.
+ *      d_segments is a DEVICE array [n][2][3], P0 then P1 (rt_closest_to_segments' shape); d_radius a DEVICE array [n], REQUIRED; outputs
+ *      are optional tight DEVICE arrays indexed like the queries.  One traversal; when hit and / or pops are the only outputs it ends
+ *      at the first valid candidate, across instances too (pops is then at most the full traversal's).  A long sweep past much
+ *      geometry prunes little until its first contact is found (the bound is a box against a box): split it on the host.
+ *      Asynchronous on `stream` unless synchronize != 0; no workspace, no scene scratch, no host synchronisation (calls may overlap each
+ *      other and renders on other streams; a scene change on another stream is not ordered against them); nothing is launched when n == 0.
+ *      RT_E_INVALID: NULL scene, n < 0, NULL segments, radius or out, or no output at all, with n > 0. --------------------------- */
+typedef struct RtSweepHits {    /* every pointer optional (NULL = not wanted), at least one given */
+    float   *time;              /* [n] the winner's s in [0, 1]: the centre stops at P0 + s*(P1 - P0); FLT_MAX on a miss         */
+    float   *distance;          /* [n] sqrtf(d2) at contact (r - distance is the penetration when time == 0); FLT_MAX on a miss  */
+    int32_t *instance;          /* [n] the winner's instance index, -1 on a miss                                             */
+    int32_t *triangle;          /* [n] the winner's triangle index as uploaded, -1 on a miss                                 */
+    float   *centre;            /* [n][3] world position of X: apply_lre(inv_pose_i, X), segment_point's sequence; 0 on a miss */
+    float   *point;             /* [n][3] world contact point c: apply_lre(inv_pose_i, c); 0 on a miss                       */
+    float   *normal;            /* [n][3] world face normal, as rt_closest_points gives it; 0 on a miss                      */
+    float   *contact_normal;    /* [n][3] from point towards centre: (X - c) / sqrtf(d2) per component, rotated to world by
+                                 *        inv_rotation_i; the face normal where d2 > 0 fails; 0 on a miss                    */
+    float   *barycentric;       /* [n][2] (b1, b2): the weights of v1 and v2 at the contact point; 0 on a miss               */
+    float   *uv;                /* [n][2] texture uv, rt_closest_points' sequence; 0 on a miss                               */
+    int32_t *hit;               /* [n] 1 when the sphere touches anything on its way, else 0                                 */
+    int32_t *pops;              /* [n] interior nodes visited (a statistic, not part of the exact contract)                  */
+} RtSweepHits;
+int rt_sweep_spheres(RtScene *scene, const float *d_segments, const float *d_radius, int32_t n, const RtSweepHits *out, void *stream,
+                     int synchronize);
+
 /* ---- region queries: every (instance, triangle) of the scene that lies in or touches a caller's convex REGION,
  *      the intersection of K half-spaces -- a view frustum, a selection pyramid, an oriented box, a wedge, a slab between two planes --
  *      and whether the triangle lies wholly inside.  Selection, culling, "what is in this workspace or sensor cone", clipping to a
