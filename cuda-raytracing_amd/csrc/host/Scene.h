@@ -50,6 +50,9 @@ public:
     void update_mesh_instance(int index, MeshInstance mesh_instance);   // rt_scene_update_instance (Scene.cpp:67-74)
     // the same, ordered on a stream instead of synchronising (rt_scene_update_instance_async): for per-frame animation
     void update_mesh_instance(int index, MeshInstance mesh_instance, void* stream);
+    // Direction tables of batched launches (rt_scene_dir_table_stats of include/rt_hip.h): launches that read one, view launches
+    // that did not, buffer growths, bytes held.  Returns the status (also in last_error).
+    int dir_table_stats(uint64_t out[4]);
     // A mesh deforms (same triangle count and order): host copy and device copy get the moved vertices and normals and refitted
     // bounds -- texture coordinates stay; no rebuild, no re-upload of anything else.  Ordered on `stream` like update_mesh_instance(.., stream).
     void refit_mesh(int mesh_index, std::vector<TrianglePrimitive> moved, void* stream = nullptr);

@@ -812,6 +812,11 @@ void Scene::update_mesh_instance(int index, MeshInstance mesh_instance, void* st
     last_error = d_scene ? rt_scene_update_instance_async(d_scene, index, &d, stream) : RT_E_INVALID;
 }
 
+int Scene::dir_table_stats(uint64_t out[4])
+{
+    return last_error = d_scene ? rt_scene_dir_table_stats(d_scene, out) : RT_E_INVALID;
+}
+
 // -------------------------------------------------------------------------------- Camera
 
 Camera::Camera(int width, int height, float3x3 K, float4 D) : width(width), height(height), K(K), D(D)

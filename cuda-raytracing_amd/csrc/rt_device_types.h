@@ -133,6 +133,11 @@ struct RenderParams {
     unsigned long long* loop_stats;     // render_kernel<.., STATS> (rt_scene_loop_stats): RT_LOOP_WORDS counters, null in every other launch
     // parity planes (tight [height][width], frame coordinates), any may be null
     int32_t *hit_instance, *hit_triangle, *node_pops, *aabb_tests, *tri_tests, *inside_hits;
+    // render_kernel<.., VIEW, ., TABLE>: the launch's camera-space ray directions (camera_space_direction of every pixel, the same in
+    // every frame because the frames share K_inv and D bit for bit), written by the view pre-pass into the view slot's own buffer.
+    // Tile-major: component c of lane l of 8x8 tile (tx, ty) is float ((ty * tiles_x + tx) * 3 + c) * 64 + l.  Null in every other launch.
+    // (The last field: no other field's offset in the kernel arguments moved when it was added.)
+    const float* dir_table;
 };
 
 static_assert(sizeof(RenderParams) <= 4096, "kernel arguments must fit in 4 KB");

@@ -98,8 +98,10 @@ __device__ __forceinline__ void box_differences(const W& w, V3 o, float4& q0, fl
     q2 = make_float4(w[8] - o.z, w[9] - o.x, w[10] - o.y, w[11] - o.z);
 }
 
-// Primary ray direction of pixel (x, y): raycast.cu:159-188
-__device__ __forceinline__ V3 camera_direction(const FrameParams& p, float fx, float fy)
+// Primary ray direction of pixel (x, y), raycast.cu:159-188, in two halves that every caller runs back to back.
+// camera_space_direction: raycast.cu:159-182, the part that depends on (K_inv, D, x, y) only -- the same in every frame of a launch
+// whose frames share their intrinsics, which is what the direction table holds (RenderParams::dir_table).
+__device__ __forceinline__ V3 camera_space_direction(const FrameParams& p, float fx, float fy)
 {
     // apply_matrix(K_inv, (x, y, 1)), utils.hpp:134-140
     float a = p.kinv[0] * fx + p.kinv[1] * fy + p.kinv[2] * 1.0f;
@@ -112,7 +114,12 @@ __device__ __forceinline__ V3 camera_direction(const FrameParams& p, float fx, f
                    + (double)(p.D[2] * theta * theta * theta) + (double)(p.D[3] * theta * theta * theta * theta)));
     float scale = thetad / radius;
     V3 d = normalize(v3(scale * a, scale * b, c));
-    d = v3(d.x, d.z, -d.y);                                     // raycast.cu:182
+    return v3(d.x, d.z, -d.y);                                  // raycast.cu:182
+}
+
+// ... and the frame's part: the camera's rotation and the final normalize
+__device__ __forceinline__ V3 world_direction(const FrameParams& p, V3 d)
+{
     d = apply_quat(p.q_cam, d);                                 // raycast.cu:185
     return normalize(d);                                        // raycast.cu:188
 }
@@ -1255,14 +1262,24 @@ template <bool DEBUG, bool PROF, bool SPILL>
 __host__ __device__ inline int lds_block_rows(int stack_depth) { return lds_rows(stack_depth) + (optimistic_stack<DEBUG, PROF, SPILL>() ? 1 : 0); }
 
 // One pixel: camera ray -> cast_ray over all instances -> flat shade -> store (raycast.cu:146-297).
-template <bool DEBUG, bool PROF, bool COUNT = false, bool SPILL = true, bool VIEW = false, bool STATS = false>
+// TABLE (with VIEW, the un-ordered grid, one rank): the lane's camera-space direction comes from the launch's direction table --
+// three coalesced 256-byte loads per wave, issued before anything else so that the ray header's scalar fetch runs beside them --
+// and holds the bits camera_space_direction would have computed here: the pre-pass wrote them with that function.
+template <bool DEBUG, bool PROF, bool COUNT = false, bool SPILL = true, bool VIEW = false, bool STATS = false, bool TABLE = false>
 __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameParams& f, int x0, int y0, lds_int* lds_base, lds_int*& lds_column,
                                              int* iters = nullptr, uint32_t view_off = 0)
 {
+    static_assert(!TABLE || (VIEW && !COUNT && !DEBUG && !PROF && kPrimBlock == 64), "direction table: the batched view kernels, one 8x8 tile per workgroup");
+    V3 cdir;
+    if constexpr (TABLE) {
+        const float* t = p.dir_table + ((size_t)(blockIdx.y * (unsigned)p.tiles_x + blockIdx.x) * (3 * 64) + (size_t)(lds_column - lds_base));
+        cdir = v3(t[0], t[64], t[128]);
+    }
     int x, ly, y;
     pixel_of(p, f, (int)(lds_column - lds_base), x0, y0, x, ly, y);
     const V3 org = v3(f.origin[0], f.origin[1], f.origin[2]);
-    const V3 dir = camera_direction(f, (float)x, (float)y);
+    if constexpr (!TABLE) cdir = camera_space_direction(f, (float)x, (float)y);
+    const V3 dir = world_direction(f, cdir);
 
     Hit hit;
     hit.min = FLT_MAX; hit.slot = -1; hit.instance = -1; hit.u = 0.0f; hit.v = 0.0f;
@@ -1330,9 +1347,10 @@ __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameP
 // otherwise idle chip; started first, those waves run beside the bulk of the frame instead of after it
 // (measured: -22 % / -12 % / 0 % frame time for the far / mid / near camera).  Which tile a workgroup renders does not
 // change what a pixel computes.
-template <bool DEBUG, bool PROF, bool ORDERED = false, bool SPILL = true, bool VIEW = false, bool STATS = false>
+template <bool DEBUG, bool PROF, bool ORDERED = false, bool SPILL = true, bool VIEW = false, bool STATS = false, bool TABLE = false>
 __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParams p)
 {
+    static_assert(!TABLE || (VIEW && !ORDERED), "direction table: its tile index is the un-ordered grid's");
     extern __shared__ int lds_stack[];                          // [lds_block_rows(stack_depth)][kPrimBlock] (+ 2 ints when ORDERED)
 
     // Workgroup (x, y) of frame z renders tile (x, y): row-major, as workgroups are dispatched -- the tile's coordinates need no
@@ -1358,7 +1376,7 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
         int x, ly, y;
         pixel_of(p, p.frames[frame], (int)threadIdx.x, tx * kPrimTile, ty * kPrimTile, x, ly, y);
         if (x < p.width && ly < p.frames[frame].local_rows)
-            render_pixel<DEBUG, PROF, ORDERED, SPILL, VIEW, STATS>(p, p.frames[frame], tx * kPrimTile, ty * kPrimTile, (lds_int*)lds_stack, column, &iters,
+            render_pixel<DEBUG, PROF, ORDERED, SPILL, VIEW, STATS, TABLE>(p, p.frames[frame], tx * kPrimTile, ty * kPrimTile, (lds_int*)lds_stack, column, &iters,
                                                             VIEW ? p.view_base + (uint32_t)frame * p.view_frame_stride : 0u);
     }
     asm volatile("" : "+v"(column));
@@ -1556,7 +1574,7 @@ __global__ __launch_bounds__(kExBlock, (SIMPLE ? 8 : kExBounceWaves)) void rende
         drawn = 2;
     }
     V3 org = v3(f.origin[0], f.origin[1], f.origin[2]);
-    V3 dir = camera_direction(f, px, py);
+    V3 dir = world_direction(f, camera_space_direction(f, px, py));
     V3 weight = v3(1.0f, 1.0f, 1.0f);
     if constexpr (SIMPLE) {                                     // the loop below for bounces = 0, lighting = 0, written out
         const Hit hit = cast_ray_ex<false, true, false, ExStack, true, VIEW, true>(p, org, dir, stack, pops);
@@ -1901,10 +1919,26 @@ struct ViewJob {
     int32_t node_base[kMaxViewInstances];       // first interior record of the instance's mesh
     int32_t count[kMaxViewInstances];           // interior-record capacity of that mesh
     int32_t total;                              // records to write per frame (sum of count)
+    // the launch's direction table (RenderParams::dir_table; 0 blocks = none): workgroups record_blocks .. of every row of the grid
+    // write it, `dir_blocks` per row, four 8x8 tiles each -- every row takes a share, so no row brings workgroups with nothing to do
+    uint32_t record_blocks, dir_blocks;
 };
 
 __global__ __launch_bounds__(256) void view_records_kernel(const RenderParams p, const ViewJob job)
 {
+    if (blockIdx.x >= job.record_blocks) {
+        // one thread per lane of a tile: the lane's camera_space_direction, from the intrinsics every frame of the launch shares.
+        // Lanes beyond a ragged edge write what they compute: the table has room for whole tiles and nothing reads those.
+        const size_t k = ((size_t)blockIdx.y * job.dir_blocks + (blockIdx.x - job.record_blocks)) * 256 + threadIdx.x;
+        const size_t tile = k >> 6, ntiles = (size_t)p.tiles_x * (size_t)p.tiles_y;
+        if (tile >= ntiles) return;
+        const int lane = (int)(k & 63);
+        const int x = (int)(tile % (size_t)p.tiles_x) * kPrimTile + (lane & 7), y = (int)(tile / (size_t)p.tiles_x) * kPrimTile + (lane >> 3);   // pixel_of
+        const V3 d = camera_space_direction(p.frames[0], (float)x, (float)y);
+        float* out = const_cast<float*>(p.dir_table) + tile * (3 * 64) + lane;
+        out[0] = d.x; out[64] = d.y; out[128] = d.z;
+        return;
+    }
     const int t = (int)(blockIdx.x * 256 + threadIdx.x), frame = (int)blockIdx.y;
     int rec = t >> 2;
     const int quarter = t & 3;
@@ -2097,7 +2131,7 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const FrameParams f, i
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= npix) return;
     const int x = (int)(k % (size_t)width), y = (int)(k / (size_t)width);
-    const V3 d = camera_direction(f, (float)x, (float)y);
+    const V3 d = world_direction(f, camera_space_direction(f, (float)x, (float)y));
     org[k * 3] = f.origin[0]; org[k * 3 + 1] = f.origin[1]; org[k * 3 + 2] = f.origin[2];
     dir[k * 3] = d.x; dir[k * 3 + 1] = d.y; dir[k * 3 + 2] = d.z;
 }
@@ -5023,11 +5057,47 @@ int view_resize(RtScene* s, int frames)
     return RT_OK;
 }
 
+// RT_DIR_TABLE=0: no launch reads camera-space directions from a table (read once; the A/B switch, and the tests')
+int dir_table_mode()
+{
+    static const int mode = [] { const char* e = getenv("RT_DIR_TABLE"); return e && e[0] == '0' ? 0 : 1; }();
+    return mode;
+}
+
+// The direction table of a launch that got view slot `sl` (RenderParams::dir_table): for a primary launch of one rank and at least two
+// frames -- never the ordered grid, then -- whose frames all carry the first frame's K_inv and D bit for bit.  Returns the slot's buffer,
+// grown first if this image needs more room, or null: the launch then renders as it did without tables.
+float* dir_table_prepare(RtScene* s, RtScene::ViewPool::Slot& sl, const RenderParams& p)
+{
+    RtScene::ViewPool& v = s->view;
+    const size_t ntiles = (size_t)p.tiles_x * (size_t)p.tiles_y;
+    if (!dir_table_mode() || p.num_ranks != 1 || p.num_frames < 2 || ntiles < 1 || ntiles > ((size_t)1 << 24)) return nullptr;
+    static_assert(offsetof(FrameParams, kinv) == 0 && offsetof(FrameParams, D) == sizeof(float) * 9, "K_inv and D lead the frame's parameters");
+    for (int k = 1; k < p.num_frames; k++)
+        if (memcmp(&p.frames[k], &p.frames[0], sizeof(float) * 13) != 0) return nullptr;
+    const size_t need = ntiles * 3 * 64 * sizeof(float);
+    if (sl.dirs_bytes < need) {
+        // whatever last read the old buffer was queued before the slot's event was recorded (a slot that was never used has neither)
+        if (sl.d_dirs && sl.done && hipEventSynchronize(sl.done) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        float* block = nullptr;
+        if (hipMalloc((void**)&block, need) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        (void)hipFree(sl.d_dirs);
+        // (not in s->device_bytes: rt_scene_info / rt_scene_memory promise records + pool + the scene's arrays, and applications size
+        // their budgets by that sum; the tables have a count of their own, rt_scene_dir_table_stats)
+        std::lock_guard<std::mutex> lock(v.m);
+        v.dir_bytes += need; v.dir_bytes -= sl.dirs_bytes;
+        if (sl.d_dirs) v.dir_grows++;                           // (a slot's first buffer is not a growth)
+        sl.d_dirs = block; sl.dirs_bytes = need;
+    }
+    return sl.d_dirs;
+}
+
 // Decides whether this launch renders through view records; if so: a slot of the pool (grown when needed and allowed), the launch's
 // view parameters in `p`, the pre-pass queued on `stream`.  Returns the slot (view_done records its event after the render kernel) or
 // -1: the launch then runs the kernels without views -- same pixels.  The caller holds call_mu from here to view_done.
 // `samples`: primary rays per pixel (the samples-only extension kernel: its jittered rays share the frame's origin too).
-int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 1)
+// `primary`: the caller is launch() with p.tiles_x / tiles_y set -- the launch may also get a direction table (dir_table_prepare).
+int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 1, bool primary = false)
 {
     if (!view_mode() || !s || p.num_instances < 1 || p.num_instances > kMaxViewInstances || p.num_ranks < 1) return -1;
     RtScene::ViewPool& v = s->view;
@@ -5080,8 +5150,13 @@ int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 
     p.view_base = (uint32_t)(v.base_bytes + (size_t)use * v.slot_frames * frame_bytes);
     p.view_frame_stride = (uint32_t)frame_bytes;
     for (int i = 0; i < job.n; i++) p.view_inst_off[i] = (int32_t)(((int64_t)job.first[i] - job.node_base[i]) * 64);
-    hipLaunchKernelGGL(view_records_kernel, dim3((unsigned)(((size_t)job.total * 4 + (size_t)job.n + 255) / 256), (unsigned)p.num_frames), dim3(256), 0, stream, p, job);
-    if (hipGetLastError() != hipSuccess) { count(&RtScene::ViewPool::fallbacks); return -1; }
+    job.record_blocks = (uint32_t)(((size_t)job.total * 4 + (size_t)job.n + 255) / 256);
+    p.dir_table = (primary && samples == 1) ? dir_table_prepare(s, v.slot[use], p) : nullptr;
+    // (four tiles per workgroup, the workgroups dealt to the rows of the grid)
+    job.dir_blocks = p.dir_table ? (uint32_t)((((size_t)p.tiles_x * (size_t)p.tiles_y + 3) / 4 + (size_t)p.num_frames - 1) / (size_t)p.num_frames) : 0u;
+    hipLaunchKernelGGL(view_records_kernel, dim3(job.record_blocks + job.dir_blocks, (unsigned)p.num_frames), dim3(256), 0, stream, p, job);
+    if (hipGetLastError() != hipSuccess) { p.dir_table = nullptr; count(&RtScene::ViewPool::fallbacks); return -1; }
+    count(p.dir_table ? &RtScene::ViewPool::dir_launches : &RtScene::ViewPool::dir_skipped);
     return use;
 }
 
@@ -5206,7 +5281,8 @@ int launch(RenderParams& p, bool debug, hipStream_t stream, int synchronize, RtS
     // (near), a rank's stripes of 32 frames -6 % on one stream but no better than the two alternating streams bench.py uses.
     // (RT_TRACE_ORDERED=1 with RT_TRACE_FILE: the stamps of the heavy-first launch itself, for tools/trace_one.py)
     const bool trace_ordered = trace_file && getenv("RT_TRACE_ORDERED");
-    const int view_slot = (scene && !debug && !trace_file) ? view_prepare(scene, p, stream) : -1;
+    const int view_slot = (scene && !debug && !trace_file) ? view_prepare(scene, p, stream, 1, true) : -1;
+    const bool table = view_slot >= 0 && p.dir_table != nullptr;     // (one rank, two frames or more: not a launch the ordered grid takes)
     struct ViewDone {                                           // (whichever way this function returns after the render kernel was queued)
         RtScene* s; int slot; hipStream_t stream;
         ~ViewDone() { view_done(s, slot, stream); }
@@ -5233,18 +5309,22 @@ int launch(RenderParams& p, bool debug, hipStream_t stream, int synchronize, RtS
     else if (debug) hipLaunchKernelGGL((render_kernel<true, false>), grid, block, lds, stream, p);
     else if (stats) {                                           // rt_scene_loop_stats: the same choices as below, the instrumented copies
         if (lds_stack_suffices(p)) {
-            if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, false, true, true>), grid, block, lds, stream, p);
+            if (table) hipLaunchKernelGGL((render_kernel<false, false, false, false, true, true, true>), grid, block, lds, stream, p);
+            else if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, false, true, true>), grid, block, lds, stream, p);
             else hipLaunchKernelGGL((render_kernel<false, false, false, false, false, true>), grid, block, lds, stream, p);
         } else {
-            if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, true, true, true>), grid, block, lds, stream, p);
+            if (table) hipLaunchKernelGGL((render_kernel<false, false, false, true, true, true, true>), grid, block, lds, stream, p);
+            else if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, true, true, true>), grid, block, lds, stream, p);
             else hipLaunchKernelGGL((render_kernel<false, false, false, true, false, true>), grid, block, lds, stream, p);
         }
     }
     else if (lds_stack_suffices(p)) {
-        if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, false, true>), grid, block, lds, stream, p);
+        if (table) hipLaunchKernelGGL((render_kernel<false, false, false, false, true, false, true>), grid, block, lds, stream, p);
+        else if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, false, true>), grid, block, lds, stream, p);
         else hipLaunchKernelGGL((render_kernel<false, false, false, false>), grid, block, lds, stream, p);
     } else {
-        if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, true, true>), grid, block, lds, stream, p);
+        if (table) hipLaunchKernelGGL((render_kernel<false, false, false, true, true, false, true>), grid, block, lds, stream, p);
+        else if (view_slot >= 0) hipLaunchKernelGGL((render_kernel<false, false, false, true, true>), grid, block, lds, stream, p);
         else hipLaunchKernelGGL((render_kernel<false, false>), grid, block, lds, stream, p);
     }
     RT_HIP(hipGetLastError());
@@ -5710,7 +5790,7 @@ int rt_scene_destroy(RtScene* s)
     if (s->refit_scratch_done) (void)hipEventDestroy(s->refit_scratch_done);
     (void)hipFree(s->d_refit_scratch);
     (void)hipFree(s->d_ex_scratch);
-    for (auto& sl : s->view.slot) if (sl.done) (void)hipEventDestroy(sl.done);
+    for (auto& sl : s->view.slot) { if (sl.done) (void)hipEventDestroy(sl.done); (void)hipFree(sl.d_dirs); }
     (void)hipFree(s->d_records); (void)hipFree(s->d_tri_uv); (void)hipFree(s->d_tri_id);
     (void)hipFree(s->d_leaf_count); (void)hipFree(s->d_mesh_flags); (void)hipFree(s->d_instances); (void)hipFree(s->d_materials);
     for (uint8_t* t : s->d_textures) (void)hipFree(t);
@@ -5734,6 +5814,15 @@ int rt_scene_view_stats(RtScene* s, uint64_t* launches, uint64_t* fallbacks, uin
     if (fallbacks) *fallbacks = s->view.fallbacks;
     if (grows) *grows = s->view.grows;
     if (slot_frames) *slot_frames = s->view.slot_frames;
+    return RT_OK;
+}
+
+int rt_scene_dir_table_stats(RtScene* s, uint64_t out[4])
+{
+    RT_SCENE_CALL(s);
+    if (!out) return RT_E_INVALID;
+    std::lock_guard<std::mutex> lock(s->view.m);
+    out[0] = s->view.dir_launches; out[1] = s->view.dir_skipped; out[2] = s->view.dir_grows; out[3] = s->view.dir_bytes;
     return RT_OK;
 }
 

@@ -110,8 +110,14 @@ struct RtScene {
         int32_t slot_frames = 0;                 // frames a slot holds (0 = no pool yet)
         int32_t slots = 0;                       // slots of the pool (1..3)
         bool reserved = false;                   // sized by rt_scene_reserve_views: launches never grow it
-        struct Slot { hipStream_t stream = nullptr; hipEvent_t done = nullptr; bool used = false; } slot[3];
+        // Direction table (render_kernel<.., TABLE>, RenderParams::dir_table): the camera-space ray direction of every pixel, one
+        // buffer per slot OUTSIDE the record allocation -- its size follows the image (12 bytes per pixel of whole 8x8 tiles), not the
+        // scene.  Written by the pre-pass of every launch that reads it and never kept for the next, so the slot's reuse rule (stream
+        // order, or its event completed) is all the ordering it needs.  It grows inside the launch that needs more room, after a wait
+        // for the slot's event, and is freed with the scene.  Its bytes are counted in dir_bytes, not in RtScene::device_bytes.
+        struct Slot { hipStream_t stream = nullptr; hipEvent_t done = nullptr; bool used = false; float* d_dirs = nullptr; size_t dirs_bytes = 0; } slot[3];
         uint64_t launches = 0, fallbacks = 0, grows = 0;
+        uint64_t dir_launches = 0, dir_skipped = 0, dir_grows = 0, dir_bytes = 0;   // rt_scene_dir_table_stats
     } view;
     size_t records_bytes = 0;                    // size of the record array proper (the head of the d_records allocation)
     size_t records_alloc_bytes = 0;              // size of the d_records allocation: records, padding, view pool

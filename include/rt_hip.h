@@ -261,6 +261,20 @@ int rt_scene_reserve_views(RtScene *scene, int32_t frames_per_launch);
 int rt_scene_memory(RtScene *scene, size_t *records_bytes, size_t *view_pool_bytes, size_t *device_bytes, int32_t *view_slots,
                     int32_t *view_slot_frames);
 int rt_scene_view_stats(RtScene *scene, uint64_t *launches, uint64_t *fallbacks, uint64_t *grows, int32_t *slot_frames);
+/* Direction tables (no counterpart in the reference, whose kernel derives every pixel's ray from K_inv and D in every frame,
+ * raycast.cu:159-182).  A primary launch that renders through view records, for one rank, of at least two frames whose K_inv and D
+ * are equal BIT FOR BIT in every frame (memcmp, so a NaN equals itself and -0 differs from 0), reads each pixel's camera-space
+ * direction -- the ray up to the camera's rotation -- from a table that the view pre-pass of that same launch wrote with the kernel's
+ * own function: the bits a lane would have computed, once per launch instead of once per frame.  Nothing is kept from one launch to
+ * the next.  Any other launch renders as before, same pixels; RT_DIR_TABLE=0 (read once per process) turns tables off.
+ * MEMORY AND BLOCKING.  Each of the pool's one to three slots owns one buffer outside the record allocation: 12 bytes per pixel of
+ * whole 8x8 tiles (24.9 MB at 1920x1080), freed with the scene.  They are reported HERE (out[3]) and not in rt_scene_memory's
+ * device_bytes, which stays the scene's arrays + records + view pool.  A slot's buffer grows
+ * inside the first launch that brings a larger image: that call waits on the host until the slot's previous launch has finished,
+ * allocates and frees -- once per slot and image size that exceeds every earlier one.  A launch that cannot allocate renders without.
+ * out[0] launches that read a table, out[1] launches that rendered through view records without one, out[2] how often a slot's
+ * buffer was replaced by a larger one, out[3] bytes the buffers hold now. */
+int rt_scene_dir_table_stats(RtScene *scene, uint64_t out[4]);
 /* Which traversal loop ran (round 6; diagnostics, no counterpart in the reference).  The primary kernel picks, per wave and
  * instance, the hand-written gfx950 loop (any instance without the exact-uv mode, when the wave's rays share a sign octant and
  * the mesh's boxes are ordered), the compiler's octant-specialised loop, or the compiler's generic loop; a tree deeper than the LDS
@@ -285,6 +299,10 @@ int rt_scene_loop_stats(RtScene *scene, const RtCameraParams *cams, uint8_t *con
  * stream rendered this way keeps the GPU full while the last long rays of one frame finish (the reference's own
  * loop issues two renders before it synchronises, kernel.cu:277-279).  Asynchronous on `stream`, with one exception: a launch of four
  * or more frames that has to grow the scene's view pool blocks until the device is idle (see rt_scene_reserve_views, which avoids it).
+ * MEMORY: when every frame of such a launch carries the same K_inv and D, the launch also keeps a direction table in its view slot --
+ * 12 bytes per pixel of whole 8x8 tiles per slot, up to three slots (24.9 MB each at 1920x1080), outside the view pool's budget; the
+ * first launch of a slot with a larger image than the slot has seen waits, on the host, for that slot's previous launch before it
+ * replaces the buffer (see rt_scene_dir_table_stats; RT_DIR_TABLE=0 renders without).
  * Host threads: calls on ONE scene are serialised while they prepare and queue their launch (a few microseconds; the GPU work of
  * different streams still overlaps); different scenes do not meet. */
 #define RT_MAX_BATCH 32
