@@ -81,6 +81,14 @@ class RtRayHits(C.Structure):               # include/rt_hip.h (device pointers,
     _fields_ = [(n, _vp) for n in _RAY_OUTPUTS]
 
 
+RT_MAX_BATCH = 32                                   # RT_MAX_BATCH of include/rt_hip.h: frames per batched launch
+_GBUFFER_OUTPUTS = ("t", "depth", "instance", "triangle", "location", "normal", "uv")
+
+
+class RtGBuffer(C.Structure):               # include/rt_hip.h (device planes [count][height][width](xk), any may be NULL)
+    _fields_ = [(n, _vp) for n in _GBUFFER_OUTPUTS]
+
+
 class RtPointHits(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL)
     _fields_ = [(n, _vp) for n in _POINT_OUTPUTS]
 
@@ -151,7 +159,7 @@ RT_HIP_SYMBOLS = [
     "rt_abi_version", "rt_build_info", "rt_device_count", "rt_set_device", "rt_malloc", "rt_malloc_pitch", "rt_free", "rt_memcpy_d2h",
     "rt_memcpy_h2d", "rt_memcpy2d_d2h", "rt_stream_synchronize", "rt_device_synchronize", "rt_error_string",
     "rt_bvh_build", "rt_scene_upload", "rt_scene_update_instance", "rt_scene_update_instance_async", "rt_scene_refit_mesh", "rt_scene_refit_mesh_device", "rt_scene_rebuild_mesh_device", "rt_scene_debug_read", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh_capacity", "rt_scene_mesh_flags", "rt_render", "rt_render_overlapped", "rt_render_overlapped_stats", "rt_scene_view_stats", "rt_scene_dir_table_stats", "rt_scene_reserve_views", "rt_scene_memory", "rt_scene_loop_stats", "rt_render_batch",
-    "rt_render_debug", "rt_render_ids", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
+    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
@@ -169,7 +177,7 @@ RT_HOST_SYMBOLS = [
     "rth_scene_set_material_params", "rth_scene_add_mesh", "rth_scene_add_mesh_instance", "rth_scene_upload_to_device", "rth_scene_update_mesh_instance", "rth_scene_update_mesh_instance_async", "rth_scene_refit_mesh", "rth_scene_rebuild_mesh",
     "rth_scene_num_mesh_instances", "rth_scene_device_handle", "rth_instance_build", "rth_camera_create", "rth_camera_free",
     "rth_camera_set_pose", "rth_camera_set_stream", "rth_camera_render_scene", "rth_camera_render_scene_stripes",
-    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
+    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
     "rth_camera_render_scene_ex", "rth_xorwow", "rth_save_png", "rth_write_png_bgr",
     "rth_read_image_bgr", "rth_zlib_inflate", "rth_overlay_text_bgr", "rth_display_image", "rth_on_mouse", "rth_on_key",
     "rth_camera_params", "rth_q_rsqrt", "rth_atanf", "rth_normalize", "rth_invert_lre", "rth_apply_lre", "rth_euler2quat",
@@ -268,6 +276,8 @@ def _declare(h, s):
     h.rt_scene_loop_stats.argtypes = [_vp, C.POINTER(RtCameraParams), C.POINTER(_vp), C.c_size_t, C.c_int32, _vp, C.POINTER(C.c_uint64)]
     h.rt_render_debug.argtypes = [_vp, C.POINTER(RtCameraParams), _vp, C.c_size_t, C.POINTER(RtDebugPlanes), _vp, C.c_int]
     h.rt_render_ids.argtypes = [_vp, C.POINTER(RtCameraParams), _vp, C.c_size_t, _vp, _vp, _vp, C.c_int]
+    h.rt_render_batch.argtypes = [_vp, C.POINTER(RtCameraParams), C.POINTER(_vp), C.c_size_t, C.c_int32, _vp, C.c_int]
+    h.rt_render_gbuffer.argtypes = [_vp, C.POINTER(RtCameraParams), C.c_int32, C.POINTER(_vp), C.c_size_t, C.POINTER(RtGBuffer), _vp, C.c_int]
     h.rt_stripe_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i]
     h.rt_render_stripes.argtypes = [_vp, C.POINTER(RtCameraParams), _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int]
     h.rt_unstripe.argtypes = [_vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
@@ -378,6 +388,7 @@ def _declare(h, s):
     s.rth_camera_render_scene_stripes.argtypes = [_vp, _vp, _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int]
     s.rth_camera_render_scene_tiled.argtypes = [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int]
     s.rth_camera_render_scene_batch.argtypes = [_vp, _vp, _f, C.POINTER(_vp), C.c_size_t, C.c_int32, C.c_int]
+    s.rth_camera_render_gbuffer.argtypes = [_vp, _vp, _f, C.c_int32, C.POINTER(RtGBuffer), C.POINTER(_vp), C.c_size_t, _vp, C.c_int]
     s.rth_camera_render_scene_stripes_batch.argtypes = [_vp, _vp, _f, C.POINTER(_vp), C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
                                                         C.c_int32, C.c_int]
     s.rth_camera_render_scene_stripes_batch_rotating.argtypes = [_vp, _vp, _f, C.POINTER(_vp), C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
@@ -1031,6 +1042,51 @@ class Camera:
             check(libs()[0].rt_camera_rays(C.byref(p), sg.ptr(o), sg.ptr(d), sg.stream, sg.sync), "rt_camera_rays")
             return sg.result(o), sg.result(d)
 
+    GBUFFER_OUTPUTS = _GBUFFER_OUTPUTS                                  # the fields of RtGBuffer
+
+    def render_gbuffer(self, scene, poses=None, outputs=("t", "instance", "triangle"), image=False, stream=None, as_numpy=False):
+        """G-buffer frames of this camera (rt_render_gbuffer; the rule is in include/rt_hip.h): what every pixel's primary ray hits, bit
+        for bit what Scene.trace_rays gives for Camera.rays(), rendered by the primary kernel in one launch per RT_MAX_BATCH frames.
+        poses: None = the camera's current pose (one frame), or a sequence of any length of (x, y, z, yaw, pitch, roll).  Returns a
+        dict of the wanted GBUFFER_OUTPUTS -- t, depth [count, h, w] float32 (world distance to the hit; apply_lre(pose, location).z;
+        FLT_MAX on a miss), instance, triangle [count, h, w] int32 (-1 on a miss), location, normal [count, h, w, 3] and uv
+        [count, h, w, 2] float32 (0 on a miss) -- plus "image" [count, h, w, 3] uint8, the frames of render_scene, with image=True
+        (`outputs` may then be empty).  torch tensors on the current device, allocated and enqueued on `stream` (a torch.cuda.Stream
+        or a raw hipStream_t; default the current torch stream) without a synchronise -- or numpy arrays with as_numpy=True."""
+        outputs = tuple(outputs)
+        if [o for o in outputs if o not in _GBUFFER_OUTPUTS] or len(set(outputs)) != len(outputs) or not (outputs or image):
+            raise ValueError("outputs must be a subset of %s (non-empty unless image=True), nothing twice, got %r" % (_GBUFFER_OUTPUTS, outputs))
+        if poses is None:
+            P = _fa(list(self.params().camera_pose)).reshape(1, 6)
+        else:
+            P = np.asarray(poses, np.float32)
+            if P.ndim != 2 or P.shape[1] != 6 or P.shape[0] < 1:
+                raise ValueError("poses must be None or a non-empty sequence of (x, y, z, yaw, pitch, roll), got shape %s" % (P.shape,))
+            P = _fa(P)
+        n, h, w = int(P.shape[0]), self.height, self.width
+        if n * h * w > 2 ** 31 - 1:
+            raise ValueError("at most 2^31 - 1 pixels per call, got %d frames of %d x %d" % (n, w, h))
+        host = libs()[1]
+        with _staging(not as_numpy, stream) as sg:
+            out = {k: sg.alloc((n, h, w) + _FIELDS[k][0], _FIELDS[k][1]) for k in outputs}
+            img = sg.alloc((n, h, w, 3), np.uint8) if image else None
+            for first in range(0, n, RT_MAX_BATCH):
+                m = min(RT_MAX_BATCH, n - first)
+                at = {k: sg.ptr(a) for k, a in out.items()}
+                at = {k: (v.value if isinstance(v, _vp) else int(v)) + first * h * w * math.prod(_FIELDS[k][0]) * 4 for k, v in at.items()}
+                planes = RtGBuffer(*[at.get(k) for k in _GBUFFER_OUTPUTS])
+                ptrs = None
+                if image:
+                    base = sg.ptr(img)
+                    base = base.value if isinstance(base, _vp) else int(base)
+                    ptrs = (_vp * m)(*[base + (first + i) * h * w * 3 for i in range(m)])
+                check(host.rth_camera_render_gbuffer(self.h, scene.h, _fp(P[first:first + m]), m, C.byref(planes), ptrs, w * 3, sg.stream, sg.sync),
+                      "Camera::render_gbuffer")
+            res = {k: sg.result(a) for k, a in out.items()}
+            if image:
+                res["image"] = sg.result(img)
+            return res
+
     def render_scene(self, scene, d_img, pitch, synchronize=False):
         check(libs()[1].rth_camera_render_scene(self.h, scene.h, d_img, pitch, 1 if synchronize else 0), "Camera::render_scene")
 
@@ -1266,7 +1322,7 @@ def _trace_workspace(binning):
 # name -> (trailing shape, dtype) of every field a query returns, per query or per list slot: the same in every struct that has it
 # (but `inside`: a region's number of wholly-inside pairs here, a pair's flag in the region lists, which say so in their _ListKind)
 _FIELDS = dict(
-    t=((), np.float32), distance=((), np.float32), sdf=((), np.float32), instance=((), np.int32), triangle=((), np.int32),
+    t=((), np.float32), depth=((), np.float32), distance=((), np.float32), sdf=((), np.float32), instance=((), np.int32), triangle=((), np.int32),
     count=((), np.int32), winding=((), np.int32), pops=((), np.int32), sign=((), np.int8), occluded=((), np.uint8),
     any=((), np.bool_), occupied=((), np.bool_), barycentric=((2,), np.float32), uv=((2,), np.float32), location=((3,), np.float32),
     point=((3,), np.float32), normal=((3,), np.float32), segment=((2, 3), np.float32), parameter=((), np.float32),

@@ -8,6 +8,7 @@
 using namespace transforms;
 
 struct RtComm;
+struct RtGBuffer;
 
 // Replacement for display_image()'s `cv::imwrite("out.png", ...)` (kernel.cu:30-43) without OpenCV: copies a pitched BGR
 // device image to the host and writes it as an 8-bit RGB PNG (stored, i.e. uncompressed, deflate blocks).
@@ -40,6 +41,9 @@ public:
     // `count` frames (<= RT_MAX_BATCH) along a camera path in one launch: frame i uses poses[i] (K, D, size from
     // this camera) and goes to img_ptrs[i]; see rt_render_batch in rt_hip.h
     void render_scene_batch(Scene& scene, const lre* poses, int count, uchar3* const* img_ptrs, size_t pitch, bool synchronize = false);
+    // G-buffer frames (rt_render_gbuffer in rt_hip.h): frame i is this camera at poses[i]; `out` holds the wanted DEVICE planes,
+    // frame-major; d_imgs null = no colour frames.  1..RT_MAX_BATCH poses per call.  Asynchronous on `stream`; returns last_error.
+    int render_gbuffer(Scene& scene, const std::vector<lre>& poses, const RtGBuffer& out, uint8_t* const* d_imgs = nullptr, size_t pitch = 0);
     // rotate_first >= 0: the stripe owner rotates with the frame index -- frame i renders the stripes of owner
     // (rank + rotate_first + i) % num_ranks, so that every rank's share of a group of frames is the same (rt_hip.h)
     void render_scene_stripes_batch(Scene& scene, const lre* poses, int count, uchar3* const* local_ptrs, size_t local_pitch,

@@ -886,6 +886,14 @@ void Camera::render_scene_batch(Scene& scene, const lre* poses, int count, uchar
     last_error = rt_render_batch(scene.d_scene, p, (uint8_t* const*)img_ptrs, pitch, count, stream, synchronize ? 1 : 0);
 }
 
+int Camera::render_gbuffer(Scene& scene, const std::vector<lre>& poses, const RtGBuffer& out, uint8_t* const* d_imgs, size_t pitch)
+{
+    if (poses.empty() || poses.size() > (size_t)RT_MAX_BATCH) return last_error = RT_E_INVALID;
+    RtCameraParams p[RT_MAX_BATCH];
+    for (size_t i = 0; i < poses.size(); i++) p[i] = camera_params(*this, poses[i]);
+    return last_error = rt_render_gbuffer(scene.d_scene, p, (int32_t)poses.size(), d_imgs, pitch, &out, stream, 0);
+}
+
 void Camera::render_scene_stripes_batch(Scene& scene, const lre* poses, int count, uchar3* const* local_ptrs, size_t local_pitch,
                                         int stripe_rows, int rank, int num_ranks, bool synchronize, int rotate_first)
 {

@@ -234,6 +234,19 @@ int rth_camera_render_scene_batch(RthCamera* c, RthScene* s, const float* poses6
     c->cam.render_scene_batch(s->scene, poses, count, (uchar3* const*)d_imgs, pitch, synchronize != 0);
     return c->cam.last_error;
 }
+int rth_camera_render_gbuffer(RthCamera* c, RthScene* s, const float* poses6, int32_t count, const void* gbuffer, void* const* d_imgs,
+                              size_t pitch, void* stream, int synchronize)
+{
+    if (!c || !s || !poses6 || !gbuffer || count < 1 || count > RT_MAX_BATCH) return RT_E_INVALID;
+    std::vector<lre> poses((size_t)count);
+    for (int i = 0; i < count; i++) poses[(size_t)i] = LRE(poses6 + 6 * i);
+    void* const own = c->cam.stream;
+    c->cam.stream = stream;
+    const int rc = c->cam.render_gbuffer(s->scene, poses, *(const RtGBuffer*)gbuffer, (uint8_t* const*)d_imgs, pitch);
+    c->cam.stream = own;
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
 int rth_camera_render_scene_stripes_batch(RthCamera* c, RthScene* s, const float* poses6, void* const* d_locals, size_t local_pitch,
                                           int32_t count, int32_t stripe_rows, int32_t rank, int32_t num_ranks, int synchronize)
 {

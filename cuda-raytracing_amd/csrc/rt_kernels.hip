@@ -1265,11 +1265,27 @@ __host__ __device__ inline int lds_block_rows(int stack_depth) { return lds_rows
 // TABLE (with VIEW, the un-ordered grid, one rank): the lane's camera-space direction comes from the launch's direction table --
 // three coalesced 256-byte loads per wave, issued before anything else so that the ray header's scalar fetch runs beside them --
 // and holds the bits camera_space_direction would have computed here: the pre-pass wrote them with that function.
-template <bool DEBUG, bool PROF, bool COUNT = false, bool SPILL = true, bool VIEW = false, bool STATS = false, bool TABLE = false>
+// GBUF (rt_render_gbuffer, gbuffer_kernel below): the traversal is the one of the timed kernels, untouched; the epilogue also stores the
+// G-buffer planes of `g`, frame-major (frame = blockIdx.z of the un-ordered grid), and shades only a frame that has an image.  The
+// planes beyond t and the ids are derived AFTER the traversal from what it leaves (hit.instance, hit.slot, hit.u, hit.v) and the
+// pixel's ray made again: the loop keeps no location -- three more live registers there cost every ray, the second evaluation of one
+// triangle costs a hit pixel a few dozen instructions once.
+struct GBufParams {
+    float* t;                   // every plane optional (null = not wanted), tight, [frame][height][width](xk): RtGBuffer of rt_hip.h
+    float* depth;
+    int32_t *instance, *triangle;
+    float *location, *normal, *uv;
+    Q4 q_pose[kMaxBatch];       // euler2quat(camera_pose ypr) of frame i: the rotation of apply_lre(camera_pose, .), for `depth`
+};
+static_assert(sizeof(RenderParams) + sizeof(GBufParams) <= 4096, "kernel arguments must fit in 4 KB");
+__device__ __forceinline__ V3 hit_normal(const RenderParams& p, const Hit& hit);
+
+template <bool DEBUG, bool PROF, bool COUNT = false, bool SPILL = true, bool VIEW = false, bool STATS = false, bool TABLE = false, bool GBUF = false>
 __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameParams& f, int x0, int y0, lds_int* lds_base, lds_int*& lds_column,
-                                             int* iters = nullptr, uint32_t view_off = 0)
+                                             int* iters = nullptr, uint32_t view_off = 0, const GBufParams* g = nullptr)
 {
     static_assert(!TABLE || (VIEW && !COUNT && !DEBUG && !PROF && kPrimBlock == 64), "direction table: the batched view kernels, one 8x8 tile per workgroup");
+    static_assert(!GBUF || (!COUNT && !DEBUG && !PROF && !STATS && kPrimBlock == 64), "G-buffer: the un-ordered production kernels");
     V3 cdir;
     if constexpr (TABLE) {
         const float* t = p.dir_table + ((size_t)(blockIdx.y * (unsigned)p.tiles_x + blockIdx.x) * (3 * 64) + (size_t)(lds_column - lds_base));
@@ -1321,9 +1337,68 @@ __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameP
     // recognise the recomputation and keep the first copies alive.)
     asm volatile("" : "+v"(lds_column));
     pixel_of(p, f, (int)(lds_column - lds_base), x0, y0, x, ly, y);
-    const uint32_t px = shade(p, hit);
-    uint8_t* out = f.img + (size_t)ly * p.pitch + 3 * (size_t)x;
-    out[0] = (uint8_t)px; out[1] = (uint8_t)(px >> 8); out[2] = (uint8_t)(px >> 16);
+    if (!GBUF || f.img) {                                       // (G-buffer frames without an image: no texture fetch, no store)
+        const uint32_t px = shade(p, hit);
+        uint8_t* out = f.img + (size_t)ly * p.pitch + 3 * (size_t)x;
+        out[0] = (uint8_t)px; out[1] = (uint8_t)(px >> 8); out[2] = (uint8_t)(px >> 16);
+    }
+    if constexpr (GBUF) {
+        // element of pixel (x, y) of this frame in a scalar plane; every offset in size_t
+        const size_t o = ((size_t)blockIdx.z * (size_t)p.height + (size_t)y) * (size_t)p.width + (size_t)x;
+        const bool got = hit.instance >= 0;
+        if (g->t) g->t[o] = hit.min;
+        if (g->instance) g->instance[o] = hit.instance;
+        if (g->triangle) g->triangle[o] = got ? p.tri_id[hit.slot] : -1;
+        if (g->location || g->depth) {
+            // The accepted candidate once more, as triangle_test<.., EX> evaluates it for query_kernel (raycast.cu:33-51, TrianglePrimitive.hpp:62-79,
+            // raycast.cu:98-104): the pixel's ray from the same table entry or the same intrinsics, to_mesh_space of the winning
+            // instance, the record of the winning slot, the transform always applied.  Same operations on the same inputs: the
+            // bits of rt_trace_rays' location.
+            V3 loc = v3(0.0f, 0.0f, 0.0f);
+            float depth = FLT_MAX;
+            if (got) {
+                V3 cd;
+                if constexpr (TABLE) {
+                    const float* t = p.dir_table + ((size_t)(blockIdx.y * (unsigned)p.tiles_x + blockIdx.x) * (3 * 64) + (size_t)(lds_column - lds_base));
+                    cd = v3(t[0], t[64], t[128]);
+                } else cd = camera_space_direction(f, (float)x, (float)y);
+                const V3 wd = world_direction(f, cd);
+                const V3 o3 = v3(f.origin[0], f.origin[1], f.origin[2]);
+                const DevInstance& in = p.instances[hit.instance];
+                const MeshRay r = to_mesh_space(in, o3, wd);
+                const float4* rec = p.records + (size_t)hit.slot * 4;
+                const float4 t0 = rec[0], t1 = rec[1];
+                const V3 v0 = v3(t0.x, t0.y, t0.z), nrm = v3(t0.w, t1.x, t1.y);
+                const float denom = dot(r.rd, nrm);
+                const float tt = dot(v0 - r.ro, nrm) / denom;
+                const V3 pt = r.ro + tt * r.rd;
+                loc = v3(pt.x * in.scale[0], pt.y * in.scale[1], pt.z * in.scale[2]);
+                loc = apply_quat(in.q_inv_pose, v3(loc.x - in.inv_pose_xyz[0], loc.y - in.inv_pose_xyz[1], loc.z - in.inv_pose_xyz[2]));
+                // depth (rt_hip.h, G-buffer rule 2): apply_lre(camera_pose, location).z
+                depth = apply_quat(g->q_pose[blockIdx.z], v3(loc.x - f.origin[0], loc.y - f.origin[1], loc.z - f.origin[2])).z;
+            }
+            if (g->location) { g->location[o * 3] = loc.x; g->location[o * 3 + 1] = loc.y; g->location[o * 3 + 2] = loc.z; }
+            if (g->depth) g->depth[o] = depth;
+        }
+        if (g->normal) {
+            const V3 n = got ? hit_normal(p, hit) : v3(0.0f, 0.0f, 0.0f);
+            g->normal[o * 3] = n.x; g->normal[o * 3 + 1] = n.y; g->normal[o * 3 + 2] = n.z;
+        }
+        if (g->uv) {
+            // query_kernel's uv: TrianglePrimitive::point_inside's interpolation (exact-uv meshes: the hit carries it)
+            float2 uv = make_float2(0.0f, 0.0f);
+            if (got) {
+                uv = make_float2(hit.u, hit.v);
+                if (!p.instances[hit.instance].exact_uv) {
+                    const float* q = p.tri_uv + (size_t)hit.slot * 6;
+                    const float w = 1.0f - hit.u - hit.v;
+                    uv.x = (w * q[0] + hit.v * q[2]) + hit.u * q[4];
+                    uv.y = (w * q[1] + hit.v * q[3]) + hit.u * q[5];
+                }
+            }
+            g->uv[o * 2] = uv.x; g->uv[o * 2 + 1] = uv.y;
+        }
+    }
 
     // hit-id planes: also available from the production kernel (rt_render_ids), so that the kernel that is timed is the
     // kernel whose hit ids are checked; a wave-uniform branch on a kernel argument, outside the traversal loop
@@ -1406,6 +1481,24 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
         unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         t[2] = ((unsigned long long)xcc << 32) | hw; t[3] = (unsigned long long)(ORDERED ? tile : (int)(blockIdx.y * gridDim.x + blockIdx.x));
     }
+}
+
+// rt_render_gbuffer: render_kernel's un-ordered form -- workgroup (x, y) of frame z renders tile (x, y), one wave per workgroup, the
+// same LDS block -- around render_pixel<.., GBUF>, with the planes as a second kernel argument (as query_kernel takes QueryParams):
+// a kernel of its own because the arguments of render_kernel's instantiations must stay what they are.  No heavy-first order, no
+// wave stamps: neither applies to this call.
+template <bool SPILL, bool VIEW, bool TABLE>
+__global__ __launch_bounds__(kPrimBlock, 8) void gbuffer_kernel(const RenderParams p, const GBufParams g)
+{
+    static_assert(!TABLE || VIEW, "direction table: written by the view pre-pass");
+    extern __shared__ int lds_stack[];                          // [lds_block_rows(stack_depth)][kPrimBlock]
+    const int frame = (int)blockIdx.z, x0 = (int)blockIdx.x * kPrimTile, y0 = (int)blockIdx.y * kPrimTile;
+    lds_int* column = (lds_int*)lds_stack + threadIdx.x;
+    int x, ly, y;
+    pixel_of(p, p.frames[frame], (int)threadIdx.x, x0, y0, x, ly, y);
+    if (x < p.width && ly < p.frames[frame].local_rows)
+        render_pixel<false, false, false, SPILL, VIEW, false, TABLE, true>(p, p.frames[frame], x0, y0, (lds_int*)lds_stack, column, nullptr,
+                                                                           VIEW ? p.view_base + (uint32_t)frame * p.view_frame_stride : 0u, &g);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -4900,18 +4993,19 @@ void fill_scene(RenderParams& p, const RtScene* s)
 }
 
 // count cameras (same width/height) -> the per-frame part of the launch parameters
-int fill_params(RenderParams& p, const RtScene* s, const RtCameraParams* cams, uint8_t* const* d_imgs, int count, size_t pitch)
+// (no_images: rt_render_gbuffer without colour frames -- d_imgs is null, every frame's img stays null and the pitch is not looked at)
+int fill_params(RenderParams& p, const RtScene* s, const RtCameraParams* cams, uint8_t* const* d_imgs, int count, size_t pitch, bool no_images = false)
 {
-    if (!s || !cams || !d_imgs || count < 1 || count > kMaxBatch || !camera_ok(&cams[0]) || pitch < (size_t)cams[0].width * 3) return RT_E_INVALID;
+    if (!s || !cams || (!d_imgs != no_images) || count < 1 || count > kMaxBatch || !camera_ok(&cams[0]) || (!no_images && pitch < (size_t)cams[0].width * 3)) return RT_E_INVALID;
     memset(&p, 0, sizeof p);
     p.width = cams[0].width; p.height = cams[0].height;
     p.num_frames = count;
     for (int i = 0; i < count; i++) {
         const RtCameraParams* cam = &cams[i];
-        if (cam->width != p.width || cam->height != p.height || !d_imgs[i]) return RT_E_INVALID;
+        if (cam->width != p.width || cam->height != p.height || (!no_images && !d_imgs[i])) return RT_E_INVALID;
         FrameParams& f = p.frames[i];
         fill_frame(f, cam);
-        f.img = d_imgs[i];
+        f.img = no_images ? nullptr : d_imgs[i];
         f.rank = 0; f.local_rows = p.height;
     }
     fill_scene(p, s);
@@ -5331,6 +5425,34 @@ int launch(RenderParams& p, bool debug, hipStream_t stream, int synchronize, RtS
     if (trace_file) RT_HIP(trace_end(p, trace_n, trace_file, stream));
     if (synchronize) RT_HIP(hipStreamSynchronize(stream));
     return RT_OK;
+}
+
+// rt_render_gbuffer's launch: the un-ordered grid and the batch launch's choices of launch() -- the stack form by the tree's depth; view
+// records when view_prepare grants a slot (four frames or more, at most kMaxViewInstances instances, ...), with the direction table
+// when the frames share K_inv and D; plain records otherwise -- each as the gbuffer_kernel instantiation of that form.
+int launch_gbuffer(RtScene* scene, RenderParams& p, const GBufParams& g, hipStream_t stream)
+{
+    if (p.width <= 0 || p.local_rows <= 0) return RT_E_INVALID;
+    p.tiles_x = (p.width + kPrimTile - 1) / kPrimTile;
+    p.tiles_y = (p.local_rows + kPrimTile - 1) / kPrimTile;
+    if (p.tiles_y > 65535) return RT_E_INVALID;                 // (a grid's y ends at 65 535, as in launch())
+    const bool shallow = lds_stack_suffices(p);
+    const size_t lds = (size_t)(shallow ? lds_rows(p.stack_depth) : lds_block_rows<false, false, true>(p.stack_depth)) * kPrimBlock * sizeof(int);
+    const dim3 grid((unsigned)p.tiles_x, (unsigned)p.tiles_y, (unsigned)p.num_frames), block(kPrimBlock);
+    const int view_slot = view_prepare(scene, p, stream, 1, true);
+    const bool table = view_slot >= 0 && p.dir_table != nullptr;
+    if (shallow) {
+        if (table) hipLaunchKernelGGL((gbuffer_kernel<false, true, true>), grid, block, lds, stream, p, g);
+        else if (view_slot >= 0) hipLaunchKernelGGL((gbuffer_kernel<false, true, false>), grid, block, lds, stream, p, g);
+        else hipLaunchKernelGGL((gbuffer_kernel<false, false, false>), grid, block, lds, stream, p, g);
+    } else {
+        if (table) hipLaunchKernelGGL((gbuffer_kernel<true, true, true>), grid, block, lds, stream, p, g);
+        else if (view_slot >= 0) hipLaunchKernelGGL((gbuffer_kernel<true, true, false>), grid, block, lds, stream, p, g);
+        else hipLaunchKernelGGL((gbuffer_kernel<true, false, false>), grid, block, lds, stream, p, g);
+    }
+    const hipError_t e = hipGetLastError();
+    view_done(scene, view_slot, stream);
+    return e == hipSuccess ? RT_OK : (int)e;
 }
 
 }  // namespace
@@ -5999,6 +6121,36 @@ int rt_render_ids(RtScene* s, const RtCameraParams* cam, uint8_t* d_img, size_t 
         if (rc) return rc;
         p.hit_instance = d_hit_instance; p.hit_triangle = d_hit_triangle;
         if ((rc = launch(p, false, (hipStream_t)stream, 0, s))) return rc;   // (with the scene: the kernel whose ids are checked is the one that is timed, views included)
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_render_gbuffer(RtScene* s, const RtCameraParams* cams, int32_t count, uint8_t* const* d_imgs, size_t pitch, const RtGBuffer* out,
+                      void* stream, int synchronize)
+{
+    // (every argument is judged before the scene is touched)
+    if (!s || !cams || !out || count < 1 || count > kMaxBatch || !camera_ok(&cams[0])) return RT_E_INVALID;
+    for (int i = 1; i < count; i++) if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) return RT_E_INVALID;
+    const bool planes = out->t || out->depth || out->instance || out->triangle || out->location || out->normal || out->uv;
+    if (!planes && !d_imgs) return RT_E_INVALID;
+    if (d_imgs) {
+        if (pitch < (size_t)cams[0].width * 3) return RT_E_INVALID;
+        for (int i = 0; i < count; i++) if (!d_imgs[i]) return RT_E_INVALID;
+    }
+    {
+        RT_SCENE_CALL(s);
+        RenderParams p;
+        int rc = fill_params(p, s, cams, d_imgs, count, pitch, d_imgs == nullptr);
+        if (rc) return rc;
+        GBufParams g;
+        g.t = out->t; g.depth = out->depth; g.instance = out->instance; g.triangle = out->triangle;
+        g.location = out->location; g.normal = out->normal; g.uv = out->uv;
+        for (int i = 0; i < kMaxBatch; i++) {
+            const RtCameraParams& c = cams[i < count ? i : 0];
+            g.q_pose[i] = euler2quat(v3(c.camera_pose[3], c.camera_pose[4], c.camera_pose[5]));
+        }
+        if ((rc = launch_gbuffer(s, p, g, (hipStream_t)stream))) return rc;
     }
     RT_WAIT_IF(synchronize, stream);
     return RT_OK;

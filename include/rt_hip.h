@@ -313,6 +313,43 @@ int rt_render_batch(RtScene *scene, const RtCameraParams *cams, uint8_t *const *
  * actually timed (rt_render_debug runs an instrumented copy). */
 int rt_render_ids(RtScene *scene, const RtCameraParams *cam, uint8_t *d_img, size_t pitch, int32_t *d_hit_instance,
                   int32_t *d_hit_triangle, void *stream, int synchronize);
+/* ---- G-buffer frames: what the primary ray of every pixel of `count` (1..RT_MAX_BATCH) cameras of one size
+ *      hits, as planes, in ONE launch of the primary kernel's G-buffer form -- the range, depth, position, normal, uv and ids a
+ *      depth camera, a range scanner or a dataset generator wants of a calibrated camera, without the detour through
+ *      rt_camera_rays + rt_trace_rays.  For pixel (x, y) of frame i:
+ *      1. Every plane but `depth` holds, bit for bit, what rt_trace_rays gives for ray y * width + x of rt_camera_rays(&cams[i]):
+ *         the reference's cast_ray on the reference's camera ray, quirks included (see "ray queries" below: t is a world
+ *         DISTANCE, back faces are never hit, of equal distances the first visited wins).
+ *      2. depth = apply_lre(camera_pose_i, location).z, one fixed fp32 sequence without contraction: with q = euler2quat(yaw,
+ *         pitch, roll of camera_pose_i) (transforms.hpp:148-163, on the host) and v = location - camera position per component,
+ *         apply_quat(q, v) of transforms.hpp:165-176 -- a = -v.x*q.y - v.y*q.z - v.z*q.w, b = v.x*q.x + v.y*q.w - v.z*q.z,
+ *         c = v.y*q.x + v.z*q.y - v.x*q.w, d = v.z*q.x + v.x*q.z - v.y*q.y, left to right -- and
+ *         depth = q.x*d - q.w*a - q.y*c + q.z*b, left to right (the quaternion is stored (w, x, y, z) in .x .y .z .w).
+ *         FLT_MAX on a miss.  It is the hit's coordinate along the z axis of the frame camera_pose defines, not a distance
+ *         (that is `t`) and not a coordinate along the viewing direction (raycast.cu:182 looks along that frame's +y).
+ *      3. Layout: tight DEVICE planes, frame-major; the element of pixel (x, y) of frame i is (i * height + y) * width + x, times
+ *         3 (location, normal) or 2 (uv) for the vector planes.  Every offset is computed in size_t.
+ *      d_imgs: NULL = no colour frames (the kernel then does not shade: no texture fetch, no store); otherwise d_imgs[i] gets
+ *      exactly rt_render's bytes for cams[i], rows `pitch` bytes apart.
+ *      Asynchronous on `stream` unless synchronize != 0, with rt_render_batch's launch decisions (stack form; view records and
+ *      the direction table for four frames or more), hence its view-pool behaviour -- a launch that has to grow the pool blocks
+ *      until the device is idle, rt_scene_reserve_views avoids it -- its direction-table memory and its serialisation of host
+ *      threads on one scene: see rt_render_batch above.  One rank only: no stripes; never the heavy-first tile order;
+ *      RT_TRACE_FILE does not apply.  Pixels whose ray has a non-finite component (a non-finite pose) do not fault and do
+ *      not change other frames; their own values are unspecified.
+ *      RT_E_INVALID: NULL scene, cams or out; count outside 1..RT_MAX_BATCH; frames of different sizes (or a size < 1); no
+ *      output at all (no plane and no d_imgs); a NULL entry in a non-NULL d_imgs; pitch < 3 * width with d_imgs. ------------- */
+typedef struct RtGBuffer {      /* every pointer optional (NULL = not wanted); DEVICE, tight, frame-major: [count][height][width](xk) */
+    float   *t;                 /* RtRayHits::t of the pixel's primary ray (HitInfo::min); FLT_MAX on a miss */
+    float   *depth;             /* camera-space z of the accepted hit: apply_lre(cam.camera_pose, location).z (rule 2); FLT_MAX on a miss */
+    int32_t *instance, *triangle;   /* rt_render_ids' planes; -1 on a miss */
+    float   *location;          /* [..][3] RtRayHits::location; 0 on a miss */
+    float   *normal;            /* [..][3] RtRayHits::normal;   0 on a miss */
+    float   *uv;                /* [..][2] RtRayHits::uv;       0 on a miss */
+} RtGBuffer;
+int rt_render_gbuffer(RtScene *scene, const RtCameraParams *cams, int32_t count /* 1..RT_MAX_BATCH */,
+                      uint8_t *const *d_imgs /* NULL = no colour frames */, size_t pitch,
+                      const RtGBuffer *out, void *stream, int synchronize);
 /* same frame plus the parity planes (instrumented copy of the kernel: counts every visit) */
 int rt_render_debug(RtScene *scene, const RtCameraParams *cam, uint8_t *d_img, size_t pitch,
                     const RtDebugPlanes *planes, void *stream, int synchronize);

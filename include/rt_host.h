@@ -94,6 +94,10 @@ int rth_camera_render_scene_tiled(RthCamera *c, RthScene *s, void *comm, void *d
                                   int32_t root, int synchronize);
 int rth_camera_render_scene_batch(RthCamera *c, RthScene *s, const float *poses6, void *const *d_imgs, size_t pitch,
                                   int32_t count, int synchronize);
+/* Camera::render_gbuffer: G-buffer frames of `count` (1..RT_MAX_BATCH) poses in one launch (rt_render_gbuffer in rt_hip.h);
+ * gbuffer = a const RtGBuffer * of device planes, d_imgs NULL = no colour frames; on `stream` (not the camera's own) */
+int rth_camera_render_gbuffer(RthCamera *c, RthScene *s, const float *poses6, int32_t count, const void *gbuffer,
+                              void *const *d_imgs, size_t pitch, void *stream, int synchronize);
 int rth_camera_render_scene_stripes_batch(RthCamera *c, RthScene *s, const float *poses6, void *const *d_locals,
                                           size_t local_pitch, int32_t count, int32_t stripe_rows, int32_t rank,
                                           int32_t num_ranks, int synchronize);
