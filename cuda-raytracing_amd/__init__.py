@@ -159,7 +159,7 @@ RT_HIP_SYMBOLS = [
     "rt_abi_version", "rt_build_info", "rt_device_count", "rt_set_device", "rt_malloc", "rt_malloc_pitch", "rt_free", "rt_memcpy_d2h",
     "rt_memcpy_h2d", "rt_memcpy2d_d2h", "rt_stream_synchronize", "rt_device_synchronize", "rt_error_string",
     "rt_bvh_build", "rt_scene_upload", "rt_scene_update_instance", "rt_scene_update_instance_async", "rt_scene_refit_mesh", "rt_scene_refit_mesh_device", "rt_scene_rebuild_mesh_device", "rt_scene_debug_read", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh_capacity", "rt_scene_mesh_flags", "rt_render", "rt_render_overlapped", "rt_render_overlapped_stats", "rt_scene_view_stats", "rt_scene_dir_table_stats", "rt_scene_reserve_views", "rt_scene_memory", "rt_scene_loop_stats", "rt_render_batch",
-    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
+    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
@@ -177,7 +177,7 @@ RT_HOST_SYMBOLS = [
     "rth_scene_set_material_params", "rth_scene_add_mesh", "rth_scene_add_mesh_instance", "rth_scene_upload_to_device", "rth_scene_update_mesh_instance", "rth_scene_update_mesh_instance_async", "rth_scene_refit_mesh", "rth_scene_rebuild_mesh",
     "rth_scene_num_mesh_instances", "rth_scene_device_handle", "rth_instance_build", "rth_camera_create", "rth_camera_free",
     "rth_camera_set_pose", "rth_camera_set_stream", "rth_camera_render_scene", "rth_camera_render_scene_stripes",
-    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
+    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_directions", "rth_sensor_create", "rth_sensor_destroy", "rth_sensor_set_pose", "rth_sensor_set_stream", "rth_sensor_rays", "rth_sensor_render_gbuffer", "rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
     "rth_camera_render_scene_ex", "rth_xorwow", "rth_save_png", "rth_write_png_bgr",
     "rth_read_image_bgr", "rth_zlib_inflate", "rth_overlay_text_bgr", "rth_display_image", "rth_on_mouse", "rth_on_key",
     "rth_camera_params", "rth_q_rsqrt", "rth_atanf", "rth_normalize", "rth_invert_lre", "rth_apply_lre", "rth_euler2quat",
@@ -278,6 +278,12 @@ def _declare(h, s):
     h.rt_render_ids.argtypes = [_vp, C.POINTER(RtCameraParams), _vp, C.c_size_t, _vp, _vp, _vp, C.c_int]
     h.rt_render_batch.argtypes = [_vp, C.POINTER(RtCameraParams), C.POINTER(_vp), C.c_size_t, C.c_int32, _vp, C.c_int]
     h.rt_render_gbuffer.argtypes = [_vp, C.POINTER(RtCameraParams), C.c_int32, C.POINTER(_vp), C.c_size_t, C.POINTER(RtGBuffer), _vp, C.c_int]
+    h.rt_render_gbuffer_table.argtypes = [_vp, _vp, C.POINTER(RtCameraParams), C.c_int32, C.POINTER(_vp), C.c_size_t, C.POINTER(RtGBuffer), _vp, C.c_int]
+    h.rt_ray_table_create.argtypes = [_vp, C.c_int32, C.c_int32, _vp, C.c_int, C.POINTER(_vp)]
+    h.rt_ray_table_info.argtypes = [_vp, _i, _i, C.POINTER(C.c_size_t)]
+    h.rt_ray_table_destroy.argtypes = [_vp]
+    h.rt_ray_table_rays.argtypes = [_vp, C.POINTER(RtCameraParams), _vp, _vp, _vp, C.c_int]
+    h.rt_camera_directions.argtypes = [C.POINTER(RtCameraParams), _vp, _vp, C.c_int]
     h.rt_stripe_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i]
     h.rt_render_stripes.argtypes = [_vp, C.POINTER(RtCameraParams), _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int]
     h.rt_unstripe.argtypes = [_vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
@@ -389,6 +395,16 @@ def _declare(h, s):
     s.rth_camera_render_scene_tiled.argtypes = [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int]
     s.rth_camera_render_scene_batch.argtypes = [_vp, _vp, _f, C.POINTER(_vp), C.c_size_t, C.c_int32, C.c_int]
     s.rth_camera_render_gbuffer.argtypes = [_vp, _vp, _f, C.c_int32, C.POINTER(RtGBuffer), C.POINTER(_vp), C.c_size_t, _vp, C.c_int]
+    s.rth_camera_directions.argtypes = [_vp, _vp, _vp, C.c_int]
+    s.rth_sensor_create.argtypes = [_f, C.c_int32, C.c_int32, C.POINTER(_vp)]
+    s.rth_sensor_destroy.argtypes = [_vp]
+    s.rth_sensor_destroy.restype = None
+    s.rth_sensor_set_pose.argtypes = [_vp, _f]
+    s.rth_sensor_set_pose.restype = None
+    s.rth_sensor_set_stream.argtypes = [_vp, _vp]
+    s.rth_sensor_set_stream.restype = None
+    s.rth_sensor_rays.argtypes = [_vp, _f, _vp, _vp, _vp, C.c_int]
+    s.rth_sensor_render_gbuffer.argtypes = [_vp, _vp, _f, C.c_int32, C.POINTER(RtGBuffer), C.POINTER(_vp), C.c_size_t, _vp, C.c_int]
     s.rth_camera_render_scene_stripes_batch.argtypes = [_vp, _vp, _f, C.POINTER(_vp), C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
                                                         C.c_int32, C.c_int]
     s.rth_camera_render_scene_stripes_batch_rotating.argtypes = [_vp, _vp, _f, C.POINTER(_vp), C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
@@ -1013,6 +1029,42 @@ class Scene:
             pass
 
 
+def _render_gbuffer(call, what, owner, scene, poses, outputs, image, stream, as_numpy):
+    """Camera.render_gbuffer and Sensor.render_gbuffer: the argument checks, the staging and the cut into launches of RT_MAX_BATCH
+    frames.  `call`: rth_camera_render_gbuffer or rth_sensor_render_gbuffer; owner: .h, .width, .height, .current_pose()."""
+    outputs = tuple(outputs)
+    if [o for o in outputs if o not in _GBUFFER_OUTPUTS] or len(set(outputs)) != len(outputs) or not (outputs or image):
+        raise ValueError("outputs must be a subset of %s (non-empty unless image=True), nothing twice, got %r" % (_GBUFFER_OUTPUTS, outputs))
+    if poses is None:
+        P = _fa(owner.current_pose()).reshape(1, 6)
+    else:
+        P = np.asarray(poses, np.float32)
+        if P.ndim != 2 or P.shape[1] != 6 or P.shape[0] < 1:
+            raise ValueError("poses must be None or a non-empty sequence of (x, y, z, yaw, pitch, roll), got shape %s" % (P.shape,))
+        P = _fa(P)
+    n, h, w = int(P.shape[0]), owner.height, owner.width
+    if n * h * w > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 pixels per call, got %d frames of %d x %d" % (n, w, h))
+    with _staging(not as_numpy, stream) as sg:
+        out = {k: sg.alloc((n, h, w) + _FIELDS[k][0], _FIELDS[k][1]) for k in outputs}
+        img = sg.alloc((n, h, w, 3), np.uint8) if image else None
+        for first in range(0, n, RT_MAX_BATCH):
+            m = min(RT_MAX_BATCH, n - first)
+            at = {k: sg.ptr(a) for k, a in out.items()}
+            at = {k: (v.value if isinstance(v, _vp) else int(v)) + first * h * w * math.prod(_FIELDS[k][0]) * 4 for k, v in at.items()}
+            planes = RtGBuffer(*[at.get(k) for k in _GBUFFER_OUTPUTS])
+            ptrs = None
+            if image:
+                base = sg.ptr(img)
+                base = base.value if isinstance(base, _vp) else int(base)
+                ptrs = (_vp * m)(*[base + (first + i) * h * w * 3 for i in range(m)])
+            check(call(owner.h, scene.h, _fp(P[first:first + m]), m, C.byref(planes), ptrs, w * 3, sg.stream, sg.sync), what)
+        res = {k: sg.result(a) for k, a in out.items()}
+        if image:
+            res["image"] = sg.result(img)
+        return res
+
+
 class Camera:
     def __init__(self, width, height, K, D):
         self.width, self.height = int(width), int(height)
@@ -1030,6 +1082,9 @@ class Camera:
         p = RtCameraParams()
         libs()[1].rth_camera_params(self.h, C.addressof(p))
         return p
+
+    def current_pose(self):
+        return list(self.params().camera_pose)
 
     def rays(self, as_numpy=False, stream=None):
         """(origins, directions) float32 [height, width, 3] of every pixel's primary ray, exactly as the render kernels make it
@@ -1053,39 +1108,15 @@ class Camera:
         [count, h, w, 2] float32 (0 on a miss) -- plus "image" [count, h, w, 3] uint8, the frames of render_scene, with image=True
         (`outputs` may then be empty).  torch tensors on the current device, allocated and enqueued on `stream` (a torch.cuda.Stream
         or a raw hipStream_t; default the current torch stream) without a synchronise -- or numpy arrays with as_numpy=True."""
-        outputs = tuple(outputs)
-        if [o for o in outputs if o not in _GBUFFER_OUTPUTS] or len(set(outputs)) != len(outputs) or not (outputs or image):
-            raise ValueError("outputs must be a subset of %s (non-empty unless image=True), nothing twice, got %r" % (_GBUFFER_OUTPUTS, outputs))
-        if poses is None:
-            P = _fa(list(self.params().camera_pose)).reshape(1, 6)
-        else:
-            P = np.asarray(poses, np.float32)
-            if P.ndim != 2 or P.shape[1] != 6 or P.shape[0] < 1:
-                raise ValueError("poses must be None or a non-empty sequence of (x, y, z, yaw, pitch, roll), got shape %s" % (P.shape,))
-            P = _fa(P)
-        n, h, w = int(P.shape[0]), self.height, self.width
-        if n * h * w > 2 ** 31 - 1:
-            raise ValueError("at most 2^31 - 1 pixels per call, got %d frames of %d x %d" % (n, w, h))
-        host = libs()[1]
+        return _render_gbuffer(libs()[1].rth_camera_render_gbuffer, "Camera::render_gbuffer", self, scene, poses, outputs, image, stream, as_numpy)
+
+    def directions(self, as_numpy=False, stream=None):
+        """float32 [height, width, 3]: the camera-space direction of every pixel (rt_camera_directions; +y the optical axis, +x image
+        right, +z image up).  Sensor(camera.directions()) reproduces this camera bit for bit.  torch or numpy as rays()."""
         with _staging(not as_numpy, stream) as sg:
-            out = {k: sg.alloc((n, h, w) + _FIELDS[k][0], _FIELDS[k][1]) for k in outputs}
-            img = sg.alloc((n, h, w, 3), np.uint8) if image else None
-            for first in range(0, n, RT_MAX_BATCH):
-                m = min(RT_MAX_BATCH, n - first)
-                at = {k: sg.ptr(a) for k, a in out.items()}
-                at = {k: (v.value if isinstance(v, _vp) else int(v)) + first * h * w * math.prod(_FIELDS[k][0]) * 4 for k, v in at.items()}
-                planes = RtGBuffer(*[at.get(k) for k in _GBUFFER_OUTPUTS])
-                ptrs = None
-                if image:
-                    base = sg.ptr(img)
-                    base = base.value if isinstance(base, _vp) else int(base)
-                    ptrs = (_vp * m)(*[base + (first + i) * h * w * 3 for i in range(m)])
-                check(host.rth_camera_render_gbuffer(self.h, scene.h, _fp(P[first:first + m]), m, C.byref(planes), ptrs, w * 3, sg.stream, sg.sync),
-                      "Camera::render_gbuffer")
-            res = {k: sg.result(a) for k, a in out.items()}
-            if image:
-                res["image"] = sg.result(img)
-            return res
+            d = sg.alloc((self.height, self.width, 3), np.float32)
+            check(libs()[1].rth_camera_directions(self.h, sg.ptr(d), sg.stream, sg.sync), "Camera::directions")
+            return sg.result(d)
 
     def render_scene(self, scene, d_img, pitch, synchronize=False):
         check(libs()[1].rth_camera_render_scene(self.h, scene.h, d_img, pitch, 1 if synchronize else 0), "Camera::render_scene")
@@ -1174,6 +1205,59 @@ class Camera:
     def close(self):
         if self.h:
             libs()[1].rth_camera_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Sensor:
+    """A sensor that is not the pinhole camera: one camera-space direction per pixel, [h, w, 3] float32, numpy or torch (+y the
+    optical axis, +x image right, +z image up; any length; see "sensor frames" in include/rt_hip.h and the generators in
+    sensors.py).  Holds a device-resident ray table; immutable, usable by any number of scenes, streams and threads."""
+
+    def __init__(self, directions):
+        d = directions.detach().cpu().numpy() if hasattr(directions, "detach") else np.asarray(directions)
+        if d.ndim != 3 or d.shape[2] != 3 or d.shape[0] < 1 or d.shape[1] < 1 or d.dtype != np.float32:
+            raise ValueError("directions must be float32 [height, width, 3], got %s %s" % (d.dtype, d.shape))
+        d = np.ascontiguousarray(d)
+        self.height, self.width = int(d.shape[0]), int(d.shape[1])
+        self._pose = [0.0] * 6
+        self.h = _vp()
+        check(libs()[1].rth_sensor_create(_fp(d), self.width, self.height, C.byref(self.h)), "Sensor")
+
+    def set_pose(self, pose):
+        self._pose = [float(v) for v in _fa(pose).reshape(6)]
+
+    def current_pose(self):
+        return list(self._pose)
+
+    def rays(self, pose=None, as_numpy=False, stream=None):
+        """(origins, directions) float32 [height, width, 3] of every pixel's ray under `pose` (default: the set pose), as
+        rt_ray_table_rays makes them: what render_gbuffer casts.  torch or numpy as Camera.rays()."""
+        P = _fa(self._pose if pose is None else pose)
+        if P.shape != (6,):
+            raise ValueError("pose must be (x, y, z, yaw, pitch, roll), got shape %s" % (P.shape,))
+        host = libs()[1]
+        shape = (self.height, self.width, 3)
+        with _staging(not as_numpy, stream) as sg:
+            o, d = sg.alloc(shape, np.float32), sg.alloc(shape, np.float32)
+            check(host.rth_sensor_rays(self.h, _fp(P), sg.ptr(o), sg.ptr(d), sg.stream, sg.sync), "Sensor::rays")
+            return sg.result(o), sg.result(d)
+
+    GBUFFER_OUTPUTS = _GBUFFER_OUTPUTS
+
+    def render_gbuffer(self, scene, poses=None, outputs=("t", "instance", "triangle"), image=False, stream=None, as_numpy=False):
+        """Camera.render_gbuffer for this sensor (rt_render_gbuffer_table): every plane but depth is, bit for bit, what
+        Scene.trace_rays gives for rays(pose); "image" is the flat shade of that hit, the sky colour on a miss."""
+        return _render_gbuffer(libs()[1].rth_sensor_render_gbuffer, "Sensor::render_gbuffer", self, scene, poses, outputs, image, stream, as_numpy)
+
+    def close(self):
+        if getattr(self, "h", None):
+            libs()[1].rth_sensor_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -44,6 +44,9 @@ public:
     // G-buffer frames (rt_render_gbuffer in rt_hip.h): frame i is this camera at poses[i]; `out` holds the wanted DEVICE planes,
     // frame-major; d_imgs null = no colour frames.  1..RT_MAX_BATCH poses per call.  Asynchronous on `stream`; returns last_error.
     int render_gbuffer(Scene& scene, const std::vector<lre>& poses, const RtGBuffer& out, uint8_t* const* d_imgs = nullptr, size_t pitch = 0);
+    // The camera-space direction of every pixel (rt_camera_directions in rt_hip.h): DEVICE [height * width][3], what a Sensor built
+    // from it reproduces this camera with, bit for bit.  Asynchronous on `stream`; returns last_error.
+    int directions(float* d_dirs);
     // rotate_first >= 0: the stripe owner rotates with the frame index -- frame i renders the stripes of owner
     // (rank + rotate_first + i) % num_ranks, so that every rank's share of a group of frames is the same (rt_hip.h)
     void render_scene_stripes_batch(Scene& scene, const lre* poses, int count, uchar3* const* local_ptrs, size_t local_pitch,

@@ -1,0 +1,48 @@
+// Sensor.h -- a sensor that is not the reference's pinhole camera (no counterpart in the reference): any ray pattern with one
+// centre of projection -- a spinning lidar, an equirectangular panorama, a fisheye, a Brown-Conrady camera -- given as one
+// camera-space direction per pixel (+y the optical axis, +x image right, +z image up: the frame after raycast.cu:182).  Owns an
+// RtRayTable (rt_hip.h, "sensor frames") and renders G-buffer and colour frames of a Scene from it.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+#include "Scene.h"
+#include "transforms.hpp"
+
+struct RtGBuffer;
+struct RtRayTable;
+
+class Sensor {
+public:
+    // dirs: HOST [height][width][3] floats, row-major; copied to the device and packed before the constructor returns.
+    // A sensor that could not be made (a bad size, no memory, no device) has last_error != 0 and refuses every call.
+    Sensor(const float* dirs, int width, int height);
+    ~Sensor();
+    Sensor(const Sensor&) = delete;
+    Sensor& operator=(const Sensor&) = delete;
+
+    transforms::lre pose;
+    int width;
+    int height;
+    void* stream = nullptr;                        // hipStream_t
+    int last_error = 0;
+
+    void set_pose(const transforms::lre& p) { pose = p; }
+    void set_stream(void* s) { stream = s; }
+    const RtRayTable* table() const { return d_table; }
+    // The rays of the current pose (rt_ray_table_rays): DEVICE origins and world directions [height * width][3].  Asynchronous on
+    // `stream`; returns last_error.
+    int rays(float* d_origins, float* d_directions);
+    // G-buffer frames (rt_render_gbuffer_table in rt_hip.h): frame i is this sensor at poses[i]; `out` holds the wanted DEVICE planes,
+    // frame-major; d_imgs null = no colour frames.  1..RT_MAX_BATCH poses per call.  Asynchronous on `stream`; returns last_error.
+    int render_gbuffer(Scene& scene, const std::vector<transforms::lre>& poses, const RtGBuffer& out, uint8_t* const* d_imgs = nullptr,
+                       size_t pitch = 0);
+    // The same two with the pose and the stream as arguments: they read the sensor and write nothing in it, so any number of host
+    // threads may call them on one sensor at once.  They return the error code and leave last_error alone.
+    int rays_on(void* on_stream, const transforms::lre& at, float* d_origins, float* d_directions) const;
+    int render_gbuffer_on(void* on_stream, Scene& scene, const std::vector<transforms::lre>& poses, const RtGBuffer& out,
+                          uint8_t* const* d_imgs = nullptr, size_t pitch = 0) const;
+
+private:
+    RtRayTable* d_table = nullptr;
+};

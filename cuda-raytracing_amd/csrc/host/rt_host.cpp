@@ -26,6 +26,7 @@
 #include "ImageIO.hpp"
 #include "OBJLoader.hpp"
 #include "Scene.h"
+#include "Sensor.h"
 
 // ------------------------------------------------------------------------------ BVHTree
 
@@ -892,6 +893,63 @@ int Camera::render_gbuffer(Scene& scene, const std::vector<lre>& poses, const Rt
     RtCameraParams p[RT_MAX_BATCH];
     for (size_t i = 0; i < poses.size(); i++) p[i] = camera_params(*this, poses[i]);
     return last_error = rt_render_gbuffer(scene.d_scene, p, (int32_t)poses.size(), d_imgs, pitch, &out, stream, 0);
+}
+
+int Camera::directions(float* d_dirs)
+{
+    RtCameraParams p = camera_params(*this, pose);
+    return last_error = rt_camera_directions(&p, d_dirs, stream, 0);
+}
+
+// -------------------------------------------------------------------------------- Sensor
+
+// the pose's part of RtCameraParams (Camera.cu:21); K_inv and D stay zero: the table calls do not read them
+static RtCameraParams sensor_params(const Sensor& s, const lre& pose)
+{
+    RtCameraParams p;
+    memset(&p, 0, sizeof p);
+    p.width = s.width; p.height = s.height;
+    lre inv = invert_lre(pose);
+    memcpy(p.camera_pose, &pose, sizeof p.camera_pose);
+    memcpy(p.inv_camera_pose, &inv, sizeof p.inv_camera_pose);
+    return p;
+}
+
+Sensor::Sensor(const float* dirs, int width, int height) : width(width), height(height)
+{
+    pose = lre();
+    if (!dirs || width < 1 || height < 1) { last_error = RT_E_INVALID; return; }
+    const size_t bytes = (size_t)width * (size_t)height * 3 * sizeof(float);
+    void* d = nullptr;
+    if ((last_error = rt_malloc(&d, bytes))) return;
+    if (!(last_error = rt_memcpy_h2d(d, dirs, bytes, nullptr)))
+        last_error = rt_ray_table_create((const float*)d, width, height, nullptr, 1, &d_table);
+    (void)rt_free(d);
+}
+
+Sensor::~Sensor() { (void)rt_ray_table_destroy(d_table); }
+
+int Sensor::rays_on(void* on_stream, const lre& at, float* d_origins, float* d_directions) const
+{
+    if (!d_table) return RT_E_INVALID;
+    RtCameraParams p = sensor_params(*this, at);
+    return rt_ray_table_rays(d_table, &p, d_origins, d_directions, on_stream, 0);
+}
+
+int Sensor::render_gbuffer_on(void* on_stream, Scene& scene, const std::vector<lre>& poses, const RtGBuffer& out, uint8_t* const* d_imgs,
+                              size_t pitch) const
+{
+    if (!d_table || !scene.d_scene || poses.empty() || poses.size() > (size_t)RT_MAX_BATCH) return RT_E_INVALID;
+    RtCameraParams p[RT_MAX_BATCH];
+    for (size_t i = 0; i < poses.size(); i++) p[i] = sensor_params(*this, poses[i]);
+    return rt_render_gbuffer_table(scene.d_scene, d_table, p, (int32_t)poses.size(), d_imgs, pitch, &out, on_stream, 0);
+}
+
+int Sensor::rays(float* d_origins, float* d_directions) { return last_error = rays_on(stream, pose, d_origins, d_directions); }
+
+int Sensor::render_gbuffer(Scene& scene, const std::vector<lre>& poses, const RtGBuffer& out, uint8_t* const* d_imgs, size_t pitch)
+{
+    return last_error = render_gbuffer_on(stream, scene, poses, out, d_imgs, pitch);
 }
 
 void Camera::render_scene_stripes_batch(Scene& scene, const lre* poses, int count, uchar3* const* local_ptrs, size_t local_pitch,

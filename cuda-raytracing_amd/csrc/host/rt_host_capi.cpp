@@ -9,10 +9,12 @@
 #include "ImageIO.hpp"
 #include "OBJLoader.hpp"
 #include "Scene.h"
+#include "Sensor.h"
 
 struct RthMesh { MeshPrimitive mesh; explicit RthMesh(MeshPrimitive m) : mesh(std::move(m)) {} };
 struct RthScene { Scene scene; };
 struct RthCamera { Camera cam; RthCamera(int w, int h, float3x3 K, float4 D) : cam(w, h, K, D) {} };
+struct RthSensor { Sensor sensor; RthSensor(const float* dirs, int w, int h) : sensor(dirs, w, h) {} };
 
 static thread_local std::string g_err;
 static float3 F3(const float* v) { return make_float3(v[0], v[1], v[2]); }
@@ -247,6 +249,49 @@ int rth_camera_render_gbuffer(RthCamera* c, RthScene* s, const float* poses6, in
     if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
     return rc;
 }
+int rth_camera_directions(RthCamera* c, float* d_dirs, void* stream, int synchronize)
+{
+    if (!c || !d_dirs) return RT_E_INVALID;
+    void* const own = c->cam.stream;
+    c->cam.stream = stream;
+    const int rc = c->cam.directions(d_dirs);
+    c->cam.stream = own;
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+
+int rth_sensor_create(const float* dirs, int32_t width, int32_t height, RthSensor** out)
+{
+    if (!dirs || !out || width < 1 || height < 1) return RT_E_INVALID;
+    RthSensor* s = nullptr;
+    try { s = new RthSensor(dirs, width, height); } catch (...) { return RT_E_NOMEM; }
+    const int rc = s->sensor.last_error;
+    if (rc) { delete s; return rc; }
+    *out = s;
+    return RT_OK;
+}
+void rth_sensor_destroy(RthSensor* s) { delete s; }
+void rth_sensor_set_pose(RthSensor* s, const float* pose6) { s->sensor.pose = LRE(pose6); }
+void rth_sensor_set_stream(RthSensor* s, void* stream) { s->sensor.stream = stream; }
+int rth_sensor_rays(RthSensor* s, const float* pose6, float* d_origins, float* d_directions, void* stream, int synchronize)
+{
+    if (!s) return RT_E_INVALID;
+    const int rc = s->sensor.rays_on(stream, pose6 ? LRE(pose6) : s->sensor.pose, d_origins, d_directions);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+int rth_sensor_render_gbuffer(RthSensor* n, RthScene* s, const float* poses6, int32_t count, const void* gbuffer, void* const* d_imgs,
+                              size_t pitch, void* stream, int synchronize)
+{
+    if (!n || !s || !poses6 || !gbuffer || count < 1 || count > RT_MAX_BATCH) return RT_E_INVALID;
+    std::vector<lre> poses((size_t)count);
+    for (int i = 0; i < count; i++) poses[(size_t)i] = LRE(poses6 + 6 * i);
+    // (nothing of the sensor is written: host threads may share one)
+    const int rc = n->sensor.render_gbuffer_on(stream, s->scene, poses, *(const RtGBuffer*)gbuffer, (uint8_t* const*)d_imgs, pitch);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+
 int rth_camera_render_scene_stripes_batch(RthCamera* c, RthScene* s, const float* poses6, void* const* d_locals, size_t local_pitch,
                                           int32_t count, int32_t stripe_rows, int32_t rank, int32_t num_ranks, int synchronize)
 {

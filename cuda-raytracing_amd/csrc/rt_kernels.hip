@@ -1284,7 +1284,8 @@ template <bool DEBUG, bool PROF, bool COUNT = false, bool SPILL = true, bool VIE
 __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameParams& f, int x0, int y0, lds_int* lds_base, lds_int*& lds_column,
                                              int* iters = nullptr, uint32_t view_off = 0, const GBufParams* g = nullptr)
 {
-    static_assert(!TABLE || (VIEW && !COUNT && !DEBUG && !PROF && kPrimBlock == 64), "direction table: the batched view kernels, one 8x8 tile per workgroup");
+    // (a caller's table -- RtRayTable, rt_render_gbuffer_table -- also serves a launch without view records: the G-buffer form only)
+    static_assert(!TABLE || ((VIEW || GBUF) && !COUNT && !DEBUG && !PROF && kPrimBlock == 64), "direction table: the batched view kernels and the G-buffer kernels, one 8x8 tile per workgroup");
     static_assert(!GBUF || (!COUNT && !DEBUG && !PROF && !STATS && kPrimBlock == 64), "G-buffer: the un-ordered production kernels");
     V3 cdir;
     if constexpr (TABLE) {
@@ -1486,11 +1487,11 @@ __global__ __launch_bounds__(kPrimBlock, 8) void render_kernel(const RenderParam
 // rt_render_gbuffer: render_kernel's un-ordered form -- workgroup (x, y) of frame z renders tile (x, y), one wave per workgroup, the
 // same LDS block -- around render_pixel<.., GBUF>, with the planes as a second kernel argument (as query_kernel takes QueryParams):
 // a kernel of its own because the arguments of render_kernel's instantiations must stay what they are.  No heavy-first order, no
-// wave stamps: neither applies to this call.
+// wave stamps: neither applies to this call.  TABLE without VIEW: the table is the caller's (rt_render_gbuffer_table), the launch got
+// no view slot.
 template <bool SPILL, bool VIEW, bool TABLE>
 __global__ __launch_bounds__(kPrimBlock, 8) void gbuffer_kernel(const RenderParams p, const GBufParams g)
 {
-    static_assert(!TABLE || VIEW, "direction table: written by the view pre-pass");
     extern __shared__ int lds_stack[];                          // [lds_block_rows(stack_depth)][kPrimBlock]
     const int frame = (int)blockIdx.z, x0 = (int)blockIdx.x * kPrimTile, y0 = (int)blockIdx.y * kPrimTile;
     lds_int* column = (lds_int*)lds_stack + threadIdx.x;
@@ -2225,6 +2226,46 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const FrameParams f, i
     if (k >= npix) return;
     const int x = (int)(k % (size_t)width), y = (int)(k / (size_t)width);
     const V3 d = world_direction(f, camera_space_direction(f, (float)x, (float)y));
+    org[k * 3] = f.origin[0]; org[k * 3 + 1] = f.origin[1]; org[k * 3 + 2] = f.origin[2];
+    dir[k * 3] = d.x; dir[k * 3 + 1] = d.y; dir[k * 3 + 2] = d.z;
+}
+
+// rt_camera_directions: camera_space_direction of every pixel, row-major -- what the view pre-pass fills a launch's table with
+__global__ __launch_bounds__(256) void camera_directions_kernel(const FrameParams f, int32_t width, size_t npix, float* dir)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= npix) return;
+    const int x = (int)(k % (size_t)width), y = (int)(k / (size_t)width);
+    const V3 d = camera_space_direction(f, (float)x, (float)y);
+    dir[k * 3] = d.x; dir[k * 3 + 1] = d.y; dir[k * 3 + 2] = d.z;
+}
+
+// rt_ray_table_create: the caller's row-major directions [height][width][3] into the tiled layout render_pixel<.., TABLE> reads
+// (tile ty * tiles_x + tx = 3 x 64 words, x / y / z planes 64 apart, lane (y & 7) * 8 + (x & 7)).  One thread per WORD OF THE TABLE,
+// in table order: a wave writes 256 consecutive bytes; the reads are the strided side (eight runs of eight pixels, 12 bytes apart).
+// The words are moved as integers: the table holds the caller's bits, whatever they are.  Lanes beyond a ragged edge get (0, 1, 0).
+__global__ __launch_bounds__(256) void ray_table_pack_kernel(const uint32_t* src, int32_t width, int32_t height, int32_t tiles_x, size_t nwords,
+                                                             uint32_t* table)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nwords) return;
+    const size_t tile = k / (3 * 64);
+    const int r = (int)(k % (3 * 64)), plane = r >> 6, lane = r & 63;
+    const int x = (int)(tile % (size_t)tiles_x) * kPrimTile + (lane & 7), y = (int)(tile / (size_t)tiles_x) * kPrimTile + (lane >> 3);
+    uint32_t w = plane == 1 ? 0x3f800000u : 0u;
+    if (x < width && y < height) w = src[((size_t)y * (size_t)width + (size_t)x) * 3 + (size_t)plane];
+    table[k] = w;
+}
+
+// rt_ray_table_rays: rt_camera_rays for a table -- world_direction of the entry, the frame's origin; row-major y * width + x
+__global__ __launch_bounds__(256) void ray_table_rays_kernel(const FrameParams f, const float* table, int32_t width, int32_t tiles_x, size_t npix,
+                                                             float* org, float* dir)
+{
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= npix) return;
+    const int x = (int)(k % (size_t)width), y = (int)(k / (size_t)width);
+    const float* t = table + ((size_t)(y / kPrimTile) * (size_t)tiles_x + (size_t)(x / kPrimTile)) * (3 * 64) + (size_t)((y & 7) * 8 + (x & 7));
+    const V3 d = world_direction(f, v3(t[0], t[64], t[128]));
     org[k * 3] = f.origin[0]; org[k * 3 + 1] = f.origin[1]; org[k * 3 + 2] = f.origin[2];
     dir[k * 3] = d.x; dir[k * 3 + 1] = d.y; dir[k * 3 + 2] = d.z;
 }
@@ -4925,6 +4966,14 @@ __global__ __launch_bounds__(kTriBlock, rg_waves(KT)) void region_list_kernel(co
 
 struct RtTimer { hipEvent_t start, stop; };
 
+// A caller's ray table (rt_ray_table_create): camera-space directions in the tiled layout of RenderParams::dir_table, whole tiles.
+// Immutable once created; owned by the caller, not by a scene.
+struct RtRayTable {
+    float* d_table;
+    int32_t width, height, tiles_x, tiles_y;
+    size_t bytes;
+};
+
 #define RT_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 namespace {
@@ -5191,7 +5240,9 @@ float* dir_table_prepare(RtScene* s, RtScene::ViewPool::Slot& sl, const RenderPa
 // -1: the launch then runs the kernels without views -- same pixels.  The caller holds call_mu from here to view_done.
 // `samples`: primary rays per pixel (the samples-only extension kernel: its jittered rays share the frame's origin too).
 // `primary`: the caller is launch() with p.tiles_x / tiles_y set -- the launch may also get a direction table (dir_table_prepare).
-int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 1, bool primary = false)
+// `caller_table` (rt_render_gbuffer_table): the launch reads this table, not one of the library's -- the pre-pass writes none and the
+// launch counts in neither dir_launches nor dir_skipped, which keep describing the library's own tables.
+int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 1, bool primary = false, const float* caller_table = nullptr)
 {
     if (!view_mode() || !s || p.num_instances < 1 || p.num_instances > kMaxViewInstances || p.num_ranks < 1) return -1;
     RtScene::ViewPool& v = s->view;
@@ -5245,12 +5296,12 @@ int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 
     p.view_frame_stride = (uint32_t)frame_bytes;
     for (int i = 0; i < job.n; i++) p.view_inst_off[i] = (int32_t)(((int64_t)job.first[i] - job.node_base[i]) * 64);
     job.record_blocks = (uint32_t)(((size_t)job.total * 4 + (size_t)job.n + 255) / 256);
-    p.dir_table = (primary && samples == 1) ? dir_table_prepare(s, v.slot[use], p) : nullptr;
+    p.dir_table = caller_table ? caller_table : (primary && samples == 1) ? dir_table_prepare(s, v.slot[use], p) : nullptr;
     // (four tiles per workgroup, the workgroups dealt to the rows of the grid)
-    job.dir_blocks = p.dir_table ? (uint32_t)((((size_t)p.tiles_x * (size_t)p.tiles_y + 3) / 4 + (size_t)p.num_frames - 1) / (size_t)p.num_frames) : 0u;
+    job.dir_blocks = p.dir_table && !caller_table ? (uint32_t)((((size_t)p.tiles_x * (size_t)p.tiles_y + 3) / 4 + (size_t)p.num_frames - 1) / (size_t)p.num_frames) : 0u;
     hipLaunchKernelGGL(view_records_kernel, dim3(job.record_blocks + job.dir_blocks, (unsigned)p.num_frames), dim3(256), 0, stream, p, job);
     if (hipGetLastError() != hipSuccess) { p.dir_table = nullptr; count(&RtScene::ViewPool::fallbacks); return -1; }
-    count(p.dir_table ? &RtScene::ViewPool::dir_launches : &RtScene::ViewPool::dir_skipped);
+    if (!caller_table) count(p.dir_table ? &RtScene::ViewPool::dir_launches : &RtScene::ViewPool::dir_skipped);
     return use;
 }
 
@@ -5430,7 +5481,8 @@ int launch(RenderParams& p, bool debug, hipStream_t stream, int synchronize, RtS
 // rt_render_gbuffer's launch: the un-ordered grid and the batch launch's choices of launch() -- the stack form by the tree's depth; view
 // records when view_prepare grants a slot (four frames or more, at most kMaxViewInstances instances, ...), with the direction table
 // when the frames share K_inv and D; plain records otherwise -- each as the gbuffer_kernel instantiation of that form.
-int launch_gbuffer(RtScene* scene, RenderParams& p, const GBufParams& g, hipStream_t stream)
+// `caller_table` (rt_render_gbuffer_table): every form reads it -- view records when a slot is granted, plain records otherwise.
+int launch_gbuffer(RtScene* scene, RenderParams& p, const GBufParams& g, hipStream_t stream, const float* caller_table = nullptr)
 {
     if (p.width <= 0 || p.local_rows <= 0) return RT_E_INVALID;
     p.tiles_x = (p.width + kPrimTile - 1) / kPrimTile;
@@ -5439,9 +5491,13 @@ int launch_gbuffer(RtScene* scene, RenderParams& p, const GBufParams& g, hipStre
     const bool shallow = lds_stack_suffices(p);
     const size_t lds = (size_t)(shallow ? lds_rows(p.stack_depth) : lds_block_rows<false, false, true>(p.stack_depth)) * kPrimBlock * sizeof(int);
     const dim3 grid((unsigned)p.tiles_x, (unsigned)p.tiles_y, (unsigned)p.num_frames), block(kPrimBlock);
-    const int view_slot = view_prepare(scene, p, stream, 1, true);
+    const int view_slot = view_prepare(scene, p, stream, 1, true, caller_table);
+    if (caller_table) p.dir_table = caller_table;               // (view_prepare leaves null where it grants no slot)
     const bool table = view_slot >= 0 && p.dir_table != nullptr;
-    if (shallow) {
+    if (caller_table && view_slot < 0) {
+        if (shallow) hipLaunchKernelGGL((gbuffer_kernel<false, false, true>), grid, block, lds, stream, p, g);
+        else hipLaunchKernelGGL((gbuffer_kernel<true, false, true>), grid, block, lds, stream, p, g);
+    } else if (shallow) {
         if (table) hipLaunchKernelGGL((gbuffer_kernel<false, true, true>), grid, block, lds, stream, p, g);
         else if (view_slot >= 0) hipLaunchKernelGGL((gbuffer_kernel<false, true, false>), grid, block, lds, stream, p, g);
         else hipLaunchKernelGGL((gbuffer_kernel<false, false, false>), grid, block, lds, stream, p, g);
@@ -6126,8 +6182,9 @@ int rt_render_ids(RtScene* s, const RtCameraParams* cam, uint8_t* d_img, size_t 
     return RT_OK;
 }
 
-int rt_render_gbuffer(RtScene* s, const RtCameraParams* cams, int32_t count, uint8_t* const* d_imgs, size_t pitch, const RtGBuffer* out,
-                      void* stream, int synchronize)
+// rt_render_gbuffer and rt_render_gbuffer_table (table: the caller's ray table, non-null; null = the cameras' own rays)
+static int render_gbuffer(RtScene* s, const RtRayTable* table, const RtCameraParams* cams, int32_t count, uint8_t* const* d_imgs, size_t pitch,
+                          const RtGBuffer* out, void* stream, int synchronize)
 {
     // (every argument is judged before the scene is touched)
     if (!s || !cams || !out || count < 1 || count > kMaxBatch || !camera_ok(&cams[0])) return RT_E_INVALID;
@@ -6138,6 +6195,8 @@ int rt_render_gbuffer(RtScene* s, const RtCameraParams* cams, int32_t count, uin
         if (pitch < (size_t)cams[0].width * 3) return RT_E_INVALID;
         for (int i = 0; i < count; i++) if (!d_imgs[i]) return RT_E_INVALID;
     }
+    // (the table is looked at last: whatever can be judged without it has been)
+    if (table && (cams[0].width != table->width || cams[0].height != table->height)) return RT_E_INVALID;
     {
         RT_SCENE_CALL(s);
         RenderParams p;
@@ -6150,10 +6209,23 @@ int rt_render_gbuffer(RtScene* s, const RtCameraParams* cams, int32_t count, uin
             const RtCameraParams& c = cams[i < count ? i : 0];
             g.q_pose[i] = euler2quat(v3(c.camera_pose[3], c.camera_pose[4], c.camera_pose[5]));
         }
-        if ((rc = launch_gbuffer(s, p, g, (hipStream_t)stream))) return rc;
+        if ((rc = launch_gbuffer(s, p, g, (hipStream_t)stream, table ? table->d_table : nullptr))) return rc;
     }
     RT_WAIT_IF(synchronize, stream);
     return RT_OK;
+}
+
+int rt_render_gbuffer(RtScene* s, const RtCameraParams* cams, int32_t count, uint8_t* const* d_imgs, size_t pitch, const RtGBuffer* out,
+                      void* stream, int synchronize)
+{
+    return render_gbuffer(s, nullptr, cams, count, d_imgs, pitch, out, stream, synchronize);
+}
+
+int rt_render_gbuffer_table(RtScene* s, const RtRayTable* table, const RtCameraParams* poses, int32_t count, uint8_t* const* d_imgs, size_t pitch,
+                            const RtGBuffer* out, void* stream, int synchronize)
+{
+    if (!table) return RT_E_INVALID;
+    return render_gbuffer(s, table, poses, count, d_imgs, pitch, out, stream, synchronize);
 }
 
 int rt_render_debug(RtScene* s, const RtCameraParams* cam, uint8_t* d_img, size_t pitch,
@@ -7146,6 +7218,74 @@ int rt_camera_rays(const RtCameraParams* cam, float* d_origins, float* d_directi
     if ((npix + 255) / 256 > (size_t)INT32_MAX) return RT_E_INVALID;
     hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, cam->width, npix,
                        d_origins, d_directions);
+    RT_HIP(hipGetLastError());
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_camera_directions(const RtCameraParams* cam, float* d_dirs, void* stream, int synchronize)
+{
+    if (!camera_ok(cam) || !d_dirs) return RT_E_INVALID;
+    FrameParams f;
+    memset(&f, 0, sizeof f);
+    fill_frame(f, cam);
+    const size_t npix = (size_t)cam->width * (size_t)cam->height;
+    if ((npix + 255) / 256 > (size_t)INT32_MAX) return RT_E_INVALID;
+    hipLaunchKernelGGL(camera_directions_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, cam->width, npix, d_dirs);
+    RT_HIP(hipGetLastError());
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+int rt_ray_table_create(const float* d_dirs, int32_t width, int32_t height, void* stream, int synchronize, RtRayTable** out)
+{
+    if (!d_dirs || !out || width < 1 || height < 1) return RT_E_INVALID;
+    const int32_t tiles_x = (width + kPrimTile - 1) / kPrimTile, tiles_y = (height + kPrimTile - 1) / kPrimTile;
+    const size_t ntiles = (size_t)tiles_x * (size_t)tiles_y;
+    if (tiles_y > 65535 || ntiles > ((size_t)1 << 24)) return RT_E_INVALID;     // (launch_gbuffer's and dir_table_prepare's limits)
+    RtRayTable* t = new (std::nothrow) RtRayTable;
+    if (!t) return RT_E_NOMEM;
+    t->width = width; t->height = height; t->tiles_x = tiles_x; t->tiles_y = tiles_y;
+    t->bytes = ntiles * 3 * 64 * sizeof(float);
+    t->d_table = nullptr;
+    if (hipMalloc((void**)&t->d_table, t->bytes) != hipSuccess) { (void)hipGetLastError(); delete t; return RT_E_NOMEM; }
+    const size_t nwords = ntiles * 3 * 64;                      // <= 2^24 * 192: the grid's x holds it
+    hipLaunchKernelGGL(ray_table_pack_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_dirs,
+                       width, height, tiles_x, nwords, (uint32_t*)t->d_table);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && synchronize) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { (void)hipFree(t->d_table); delete t; return (int)e; }
+    *out = t;
+    return RT_OK;
+}
+
+int rt_ray_table_info(const RtRayTable* t, int32_t* width, int32_t* height, size_t* device_bytes)
+{
+    if (!t) return RT_E_INVALID;
+    if (width) *width = t->width;
+    if (height) *height = t->height;
+    if (device_bytes) *device_bytes = t->bytes;
+    return RT_OK;
+}
+
+int rt_ray_table_destroy(RtRayTable* t)
+{
+    if (!t) return RT_OK;
+    const hipError_t e = hipFree(t->d_table);
+    delete t;
+    return e == hipSuccess ? RT_OK : (int)e;
+}
+
+int rt_ray_table_rays(const RtRayTable* t, const RtCameraParams* pose, float* d_origins, float* d_directions, void* stream, int synchronize)
+{
+    if (!t || !camera_ok(pose) || !d_origins || !d_directions) return RT_E_INVALID;
+    if (pose->width != t->width || pose->height != t->height) return RT_E_INVALID;
+    FrameParams f;
+    memset(&f, 0, sizeof f);
+    fill_frame(f, pose);                                        // (K_inv and D travel along unread)
+    const size_t npix = (size_t)t->width * (size_t)t->height;
+    hipLaunchKernelGGL(ray_table_rays_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, t->d_table, t->width,
+                       t->tiles_x, npix, d_origins, d_directions);
     RT_HIP(hipGetLastError());
     RT_WAIT_IF(synchronize, stream);
     return RT_OK;

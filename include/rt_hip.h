@@ -350,6 +350,46 @@ typedef struct RtGBuffer {      /* every pointer optional (NULL = not wanted); D
 int rt_render_gbuffer(RtScene *scene, const RtCameraParams *cams, int32_t count /* 1..RT_MAX_BATCH */,
                       uint8_t *const *d_imgs /* NULL = no colour frames */, size_t pitch,
                       const RtGBuffer *out, void *stream, int synchronize);
+/* ---- sensor frames: the G-buffer and the colour of a sensor that is not the reference's pinhole -- a spinning
+ *      lidar, an equirectangular panorama, a fisheye, a Brown-Conrady camera: any ray pattern with ONE centre of projection -- from a
+ *      table of camera-space directions the caller fills.
+ *      RtRayTable: a device-resident table of width x height directions in the layout the primary kernel's table form reads
+ *      (tile-major, one 8x8 tile = 3 x 64 floats, x / y / z planes 64 apart; tile ty * tiles_x + tx; lane (y & 7) * 8 + (x & 7); room
+ *      for whole tiles, 768 bytes each).  Immutable once created: any number of scenes, streams and host threads may use one table at
+ *      once.  Its memory belongs to no scene: not in rt_scene_info / rt_scene_memory, see rt_ray_table_info.
+ *      An entry c of pixel (x, y) is the vector in the camera frame after raycast.cu:182: +y the optical axis, +x image right, +z
+ *      image up.  Under a pose P (camera_pose, inv_camera_pose of RtCameraParams) the pixel's ray has origin P.xyz and direction
+ *      normalize3(apply_euler(inv_camera_pose.ypr, c)) -- raycast.cu:185-188, computed as the render kernels compute it, as a
+ *      quaternion product with q = euler2quat(inv_camera_pose.ypr) made on the host.  Entries need not have unit length; zero
+ *      components are ordinary input.  A non-finite or all-zero entry does not fault and does not change other pixels; its own values
+ *      are unspecified. */
+typedef struct RtRayTable RtRayTable;
+/* d_dirs: DEVICE [height][width][3] floats, row-major, read on `stream` (asynchronously unless synchronize != 0: keep it alive and
+ * unchanged until then).  The table holds the caller's bits unchanged; lanes beyond a ragged edge hold (0, 1, 0).
+ * RT_E_INVALID: NULL d_dirs or out, a size < 1, more than 65 535 rows of tiles, more than 2^24 tiles.  RT_E_NOMEM is possible. */
+int rt_ray_table_create(const float *d_dirs, int32_t width, int32_t height, void *stream, int synchronize, RtRayTable **out);
+/* every out pointer optional; device_bytes = tiles_x * tiles_y * 768 */
+int rt_ray_table_info(const RtRayTable *table, int32_t *width, int32_t *height, size_t *device_bytes);
+/* the caller has synchronised whatever reads the table (its creation included), as with rt_free; NULL is accepted */
+int rt_ray_table_destroy(RtRayTable *table);
+/* The camera-space direction of every pixel of a camera (raycast.cu:159-182: K_inv, the atan distortion, the swizzle), DEVICE
+ * [height * width][3], row-major: what the library's own direction tables hold.  A table created from this output makes
+ * rt_ray_table_rays equal rt_camera_rays and rt_render_gbuffer_table equal rt_render_gbuffer for that camera, bit for bit. */
+int rt_camera_directions(const RtCameraParams *cam, float *d_dirs, void *stream, int synchronize);
+/* rt_camera_rays for a table: DEVICE origins and world directions [height * width][3], row-major.  Of `pose` only camera_pose,
+ * inv_camera_pose, width and height are read (K_inv and D are ignored).  RT_E_INVALID: a NULL argument, a size that is not the table's. */
+int rt_ray_table_rays(const RtRayTable *table, const RtCameraParams *pose, float *d_origins, float *d_directions, void *stream,
+                      int synchronize);
+/* rt_render_gbuffer with the pixel's ray taken from the table.  Rule 1 becomes: every plane but `depth` holds, bit for bit, what
+ * rt_trace_rays gives for ray y * width + x of rt_ray_table_rays(table, &poses[i]); rules 2 and 3 are unchanged.  d_imgs[i] gets the
+ * flat shade of that hit -- the sky colour on a miss, otherwise as rt_render -- and images alone (every plane NULL) are a valid call:
+ * the colour render of a sensor.  With four frames or more (and whatever else rt_render_batch asks of a view launch) the launch
+ * takes view records, otherwise plain records; both read the caller's table, the library writes none, and
+ * rt_scene_dir_table_stats does not count the launch.
+ * RT_E_INVALID: the cases of rt_render_gbuffer, a NULL table, a pose whose width or height is not the table's. */
+int rt_render_gbuffer_table(RtScene *scene, const RtRayTable *table, const RtCameraParams *poses, int32_t count /* 1..RT_MAX_BATCH */,
+                            uint8_t *const *d_imgs /* NULL = no colour frames */, size_t pitch, const RtGBuffer *out, void *stream,
+                            int synchronize);
 /* same frame plus the parity planes (instrumented copy of the kernel: counts every visit) */
 int rt_render_debug(RtScene *scene, const RtCameraParams *cam, uint8_t *d_img, size_t pitch,
                     const RtDebugPlanes *planes, void *stream, int synchronize);

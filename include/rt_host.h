@@ -16,6 +16,7 @@ extern "C" {
 typedef struct RthMesh RthMesh;       /* MeshPrimitive */
 typedef struct RthScene RthScene;     /* Scene */
 typedef struct RthCamera RthCamera;   /* Camera */
+typedef struct RthSensor RthSensor;   /* Sensor */
 
 /* OBJLoader::load(fp) (OBJLoader.hpp:15); NULL on failure, message via rth_last_error() */
 RthMesh *rth_obj_load(const char *path);
@@ -97,6 +98,20 @@ int rth_camera_render_scene_batch(RthCamera *c, RthScene *s, const float *poses6
 /* Camera::render_gbuffer: G-buffer frames of `count` (1..RT_MAX_BATCH) poses in one launch (rt_render_gbuffer in rt_hip.h);
  * gbuffer = a const RtGBuffer * of device planes, d_imgs NULL = no colour frames; on `stream` (not the camera's own) */
 int rth_camera_render_gbuffer(RthCamera *c, RthScene *s, const float *poses6, int32_t count, const void *gbuffer,
+                              void *const *d_imgs, size_t pitch, void *stream, int synchronize);
+/* Camera::directions: the camera-space direction of every pixel (rt_camera_directions), DEVICE [height * width][3]; on `stream` */
+int rth_camera_directions(RthCamera *c, float *d_dirs, void *stream, int synchronize);
+/* Sensor (Sensor.h): one camera-space direction per pixel, HOST [height][width][3]; owns an RtRayTable (rt_hip.h, "sensor frames").
+ * create returns the error that kept the sensor from being made (a bad size, no memory, no device) and leaves *out alone then. */
+int rth_sensor_create(const float *dirs, int32_t width, int32_t height, RthSensor **out);
+void rth_sensor_destroy(RthSensor *s);
+void rth_sensor_set_pose(RthSensor *s, const float *pose6);
+void rth_sensor_set_stream(RthSensor *s, void *stream);
+/* Sensor::rays_on: the rays under pose6 (NULL = the set pose) on `stream` (rt_ray_table_rays) */
+int rth_sensor_rays(RthSensor *s, const float *pose6, float *d_origins, float *d_directions, void *stream, int synchronize);
+/* Sensor::render_gbuffer_on: as rth_camera_render_gbuffer, the rays from the sensor's table (rt_render_gbuffer_table).  This and
+ * rth_sensor_rays write nothing in the sensor: host threads may share one. */
+int rth_sensor_render_gbuffer(RthSensor *n, RthScene *s, const float *poses6, int32_t count, const void *gbuffer,
                               void *const *d_imgs, size_t pitch, void *stream, int synchronize);
 int rth_camera_render_scene_stripes_batch(RthCamera *c, RthScene *s, const float *poses6, void *const *d_locals,
                                           size_t local_pitch, int32_t count, int32_t stripe_rows, int32_t rank,
