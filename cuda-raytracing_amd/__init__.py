@@ -89,6 +89,17 @@ class RtGBuffer(C.Structure):               # include/rt_hip.h (device planes [c
     _fields_ = [(n, _vp) for n in _GBUFFER_OUTPUTS]
 
 
+# the fields of a point cloud in RT_CLOUD_* bit order (include/rt_hip.h, "point clouds"): name -> (trailing shape, type)
+_CLOUD_FIELDS = dict(range=((), np.float32), pixel=((), np.int32), frame=((), np.int32), instance=((), np.int32), triangle=((), np.int32),
+                     position=((3,), np.float32), local=((3,), np.float32), normal=((3,), np.float32), uv=((2,), np.float32))
+_CLOUD_OUTPUTS = tuple(_CLOUD_FIELDS)
+RT_CLOUD_BITS = {k: 1 << i for i, k in enumerate(_CLOUD_OUTPUTS)}     # RT_CLOUD_RANGE .. RT_CLOUD_UV
+
+
+class RtPointCloud(C.Structure):            # include/rt_hip.h (device arrays [capacity](xk), any may be NULL)
+    _fields_ = [(n, _vp) for n in _CLOUD_OUTPUTS]
+
+
 class RtPointHits(C.Structure):             # include/rt_hip.h (device pointers, any may be NULL)
     _fields_ = [(n, _vp) for n in _POINT_OUTPUTS]
 
@@ -159,7 +170,7 @@ RT_HIP_SYMBOLS = [
     "rt_abi_version", "rt_build_info", "rt_device_count", "rt_set_device", "rt_malloc", "rt_malloc_pitch", "rt_free", "rt_memcpy_d2h",
     "rt_memcpy_h2d", "rt_memcpy2d_d2h", "rt_stream_synchronize", "rt_device_synchronize", "rt_error_string",
     "rt_bvh_build", "rt_scene_upload", "rt_scene_update_instance", "rt_scene_update_instance_async", "rt_scene_refit_mesh", "rt_scene_refit_mesh_device", "rt_scene_rebuild_mesh_device", "rt_scene_debug_read", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh_capacity", "rt_scene_mesh_flags", "rt_render", "rt_render_overlapped", "rt_render_overlapped_stats", "rt_scene_view_stats", "rt_scene_dir_table_stats", "rt_scene_reserve_views", "rt_scene_memory", "rt_scene_loop_stats", "rt_render_batch",
-    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
+    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_point_cloud_workspace_bytes", "rt_point_cloud_offsets", "rt_point_cloud_offsets_table", "rt_point_cloud_fill", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
@@ -177,7 +188,7 @@ RT_HOST_SYMBOLS = [
     "rth_scene_set_material_params", "rth_scene_add_mesh", "rth_scene_add_mesh_instance", "rth_scene_upload_to_device", "rth_scene_update_mesh_instance", "rth_scene_update_mesh_instance_async", "rth_scene_refit_mesh", "rth_scene_rebuild_mesh",
     "rth_scene_num_mesh_instances", "rth_scene_device_handle", "rth_instance_build", "rth_camera_create", "rth_camera_free",
     "rth_camera_set_pose", "rth_camera_set_stream", "rth_camera_render_scene", "rth_camera_render_scene_stripes",
-    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_directions", "rth_sensor_create", "rth_sensor_destroy", "rth_sensor_set_pose", "rth_sensor_set_stream", "rth_sensor_rays", "rth_sensor_render_gbuffer", "rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
+    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_directions", "rth_sensor_create", "rth_sensor_destroy", "rth_sensor_set_pose", "rth_sensor_set_stream", "rth_sensor_rays", "rth_sensor_render_gbuffer", "rth_camera_point_cloud_offsets", "rth_sensor_point_cloud_offsets", "rth_point_cloud_fill", "rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
     "rth_camera_render_scene_ex", "rth_xorwow", "rth_save_png", "rth_write_png_bgr",
     "rth_read_image_bgr", "rth_zlib_inflate", "rth_overlay_text_bgr", "rth_display_image", "rth_on_mouse", "rth_on_key",
     "rth_camera_params", "rth_q_rsqrt", "rth_atanf", "rth_normalize", "rth_invert_lre", "rth_apply_lre", "rth_euler2quat",
@@ -279,6 +290,15 @@ def _declare(h, s):
     h.rt_render_batch.argtypes = [_vp, C.POINTER(RtCameraParams), C.POINTER(_vp), C.c_size_t, C.c_int32, _vp, C.c_int]
     h.rt_render_gbuffer.argtypes = [_vp, C.POINTER(RtCameraParams), C.c_int32, C.POINTER(_vp), C.c_size_t, C.POINTER(RtGBuffer), _vp, C.c_int]
     h.rt_render_gbuffer_table.argtypes = [_vp, _vp, C.POINTER(RtCameraParams), C.c_int32, C.POINTER(_vp), C.c_size_t, C.POINTER(RtGBuffer), _vp, C.c_int]
+    h.rt_point_cloud_workspace_bytes.restype = C.c_size_t
+    h.rt_point_cloud_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
+    cloud_tail = [C.c_int32, C.c_float, C.c_float, _vp, C.c_uint32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_point_cloud_offsets.argtypes = [_vp, C.POINTER(RtCameraParams)] + cloud_tail
+    h.rt_point_cloud_offsets_table.argtypes = [_vp, _vp, C.POINTER(RtCameraParams)] + cloud_tail
+    h.rt_point_cloud_fill.argtypes = [C.POINTER(RtCameraParams), C.c_int32, C.c_uint32, _vp, C.c_size_t, C.c_int64, C.POINTER(RtPointCloud), _vp, C.c_int]
+    s.rth_camera_point_cloud_offsets.argtypes = [_vp, _vp, _f] + cloud_tail
+    s.rth_sensor_point_cloud_offsets.argtypes = [_vp, _vp, _f] + cloud_tail
+    s.rth_point_cloud_fill.argtypes = [C.c_int32, C.c_int32, _f, C.c_int32, C.c_uint32, _vp, C.c_size_t, C.c_int64, C.POINTER(RtPointCloud), _vp, C.c_int]
     h.rt_ray_table_create.argtypes = [_vp, C.c_int32, C.c_int32, _vp, C.c_int, C.POINTER(_vp)]
     h.rt_ray_table_info.argtypes = [_vp, _i, _i, C.POINTER(C.c_size_t)]
     h.rt_ray_table_destroy.argtypes = [_vp]
@@ -1065,6 +1085,85 @@ def _render_gbuffer(call, what, owner, scene, poses, outputs, image, stream, as_
         return res
 
 
+def _point_cloud(call, what, owner, scene, poses, outputs, min_range, max_range, mask, stream, as_numpy):
+    """Camera.point_cloud and Sensor.point_cloud: the argument checks -- all before any device call -- and, per group of RT_MAX_BATCH
+    frames, the workspace, the offsets call, the one host read of the total, the exact allocation and the fill.  `call`:
+    rth_camera_point_cloud_offsets or rth_sensor_point_cloud_offsets; owner: .h, .width, .height, .current_pose()."""
+    outputs = tuple(outputs)
+    if not outputs or [o for o in outputs if o not in _CLOUD_OUTPUTS] or len(set(outputs)) != len(outputs):
+        raise ValueError("outputs must be a non-empty subset of %s, nothing twice, got %r" % (_CLOUD_OUTPUTS, outputs))
+    if poses is None:
+        P = _fa(owner.current_pose()).reshape(1, 6)
+    else:
+        P = np.asarray(poses, np.float32)
+        if P.ndim != 2 or P.shape[1] != 6 or P.shape[0] < 1:
+            raise ValueError("poses must be None or a non-empty sequence of (x, y, z, yaw, pitch, roll), got shape %s" % (P.shape,))
+        P = _fa(P)
+    n, h, w = int(P.shape[0]), owner.height, owner.width
+    if n * h * w > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 pixels per call, got %d frames of %d x %d" % (n, w, h))
+    lo, hi = float(np.float32(min_range)), float(np.float32(max_range))
+    if math.isnan(lo) or math.isnan(hi) or lo > hi:
+        raise ValueError("min_range <= max_range must hold, neither a NaN, got %r, %r" % (min_range, max_range))
+    torch_mask = mask is not None and type(mask).__module__.split(".")[0] == "torch"
+    if mask is not None:
+        if not torch_mask:
+            mask = np.asarray(mask)
+        if tuple(mask.shape) != (h, w) or str(mask.dtype).replace("torch.", "") not in ("bool", "uint8"):
+            raise ValueError("mask must be bool or uint8 [%d, %d] (height, width), got %s %s" % (h, w, mask.dtype, tuple(mask.shape)))
+    fields = 0
+    for k in outputs:
+        fields |= RT_CLOUD_BITS[k]
+    hip, host = libs()
+    with _staging(not as_numpy, stream) as sg:
+        d_mask = None
+        if mask is not None and as_numpy:
+            m8 = mask.detach().cpu().numpy() if torch_mask else mask
+            d_mask = sg.inputs([np.ascontiguousarray(m8.astype(np.uint8))])[0]
+        elif mask is not None:
+            keep_mask = (mask if torch_mask else sg.torch.from_numpy(np.ascontiguousarray(mask))).to(sg.dev).to(sg.torch.uint8).contiguous()
+            d_mask = sg.ptr(keep_mask)
+        groups, ends, base = [], [], 0                              # per group: its fields; its frames' end offsets, running on
+        for first in range(0, n, RT_MAX_BATCH):
+            m = min(RT_MAX_BATCH, n - first)
+            ws_bytes = int(hip.rt_point_cloud_workspace_bytes(w, h, m, fields))
+            ws = sg.alloc((ws_bytes,), np.uint8)
+            offsets = sg.alloc((m + 1,), np.int64)
+            Pg = _fp(P[first:first + m])
+            check(call(owner.h, scene.h, Pg, m, lo, hi, d_mask, fields, sg.ptr(offsets), sg.ptr(ws), ws_bytes, sg.stream, sg.sync), what)
+            total = sg.read_int64(offsets, m)                       # torch: the one host synchronisation per group, for the size of the outputs
+            out = {k: sg.alloc((total,) + _CLOUD_FIELDS[k][0], _CLOUD_FIELDS[k][1]) for k in outputs}
+            if total:
+                cloud = RtPointCloud(*[sg.ptr(out[k]) if k in out else None for k in _CLOUD_OUTPUTS])
+                check(host.rth_point_cloud_fill(w, h, Pg, m, fields, sg.ptr(ws), ws_bytes, total, C.byref(cloud), sg.stream, sg.sync),
+                      "point_cloud_fill")
+            got = {k: sg.result(a) for k, a in out.items()}
+            if first and "frame" in got:
+                got["frame"] = got["frame"] + first                 # (the call numbers its own frames from 0)
+            groups.append(got)
+            off = sg.result(offsets)
+            ends.append(off[1:] + base)
+            base += total
+        if as_numpy:
+            res = {k: groups[0][k] if len(groups) == 1 else np.concatenate([g[k] for g in groups]) for k in outputs}
+            res["offsets"] = np.concatenate([np.zeros(1, np.int64)] + ends)
+        else:
+            torch = sg.torch
+            res = {k: groups[0][k] if len(groups) == 1 else torch.cat([g[k] for g in groups]) for k in outputs}
+            res["offsets"] = torch.cat([torch.zeros(1, dtype=torch.int64, device=sg.dev)] + ends)
+        return res
+
+
+_POINT_CLOUD_DOC = """The point cloud of %s frames (rt_point_cloud_offsets%s + rt_point_cloud_fill; the rules are in include/rt_hip.h): the pixels
+        whose ray hit something with min_range <= t <= max_range and, with a mask (bool or uint8 [height, width], numpy or torch,
+        shared by all frames), mask != 0 -- packed in (frame, y, x) order.  poses: None = the current pose (one frame), or a sequence
+        of any length of (x, y, z, yaw, pitch, roll).  Returns a dict of the wanted CLOUD_OUTPUTS [total](, k) -- range (t), pixel
+        (y * width + x), frame, instance, triangle, position (world), local (apply_lre(pose, position): the sensor's own frame; local[:, 2]
+        is the G-buffer's depth), normal, uv, each the G-buffer plane's bits -- plus offsets, int64 [frames + 1]: frame i's points are
+        offsets[i]:offsets[i + 1].  torch tensors on the current device, enqueued on `stream` with one host read of the total per
+        RT_MAX_BATCH frames -- or numpy arrays with as_numpy=True."""
+
+
 class Camera:
     def __init__(self, width, height, K, D):
         self.width, self.height = int(width), int(height)
@@ -1109,6 +1208,14 @@ class Camera:
         (`outputs` may then be empty).  torch tensors on the current device, allocated and enqueued on `stream` (a torch.cuda.Stream
         or a raw hipStream_t; default the current torch stream) without a synchronise -- or numpy arrays with as_numpy=True."""
         return _render_gbuffer(libs()[1].rth_camera_render_gbuffer, "Camera::render_gbuffer", self, scene, poses, outputs, image, stream, as_numpy)
+
+    CLOUD_OUTPUTS = _CLOUD_OUTPUTS                                      # the fields of RtPointCloud
+
+    def point_cloud(self, scene, poses=None, outputs=("local", "range", "pixel"), min_range=0.0, max_range=math.inf, mask=None,
+                    stream=None, as_numpy=False):
+        return _point_cloud(libs()[1].rth_camera_point_cloud_offsets, "Camera::point_cloud_offsets", self, scene, poses, outputs, min_range,
+                            max_range, mask, stream, as_numpy)
+    point_cloud.__doc__ = _POINT_CLOUD_DOC % ("this camera's", "")
 
     def directions(self, as_numpy=False, stream=None):
         """float32 [height, width, 3]: the camera-space direction of every pixel (rt_camera_directions; +y the optical axis, +x image
@@ -1254,6 +1361,14 @@ class Sensor:
         """Camera.render_gbuffer for this sensor (rt_render_gbuffer_table): every plane but depth is, bit for bit, what
         Scene.trace_rays gives for rays(pose); "image" is the flat shade of that hit, the sky colour on a miss."""
         return _render_gbuffer(libs()[1].rth_sensor_render_gbuffer, "Sensor::render_gbuffer", self, scene, poses, outputs, image, stream, as_numpy)
+
+    CLOUD_OUTPUTS = _CLOUD_OUTPUTS
+
+    def point_cloud(self, scene, poses=None, outputs=("local", "range", "pixel"), min_range=0.0, max_range=math.inf, mask=None,
+                    stream=None, as_numpy=False):
+        return _point_cloud(libs()[1].rth_sensor_point_cloud_offsets, "Sensor::point_cloud_offsets", self, scene, poses, outputs, min_range,
+                            max_range, mask, stream, as_numpy)
+    point_cloud.__doc__ = _POINT_CLOUD_DOC % ("this sensor's", "_table")
 
     def close(self):
         if getattr(self, "h", None):

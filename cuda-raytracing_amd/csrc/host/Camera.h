@@ -9,6 +9,7 @@ using namespace transforms;
 
 struct RtComm;
 struct RtGBuffer;
+struct RtPointCloud;
 
 // Replacement for display_image()'s `cv::imwrite("out.png", ...)` (kernel.cu:30-43) without OpenCV: copies a pitched BGR
 // device image to the host and writes it as an 8-bit RGB PNG (stored, i.e. uncompressed, deflate blocks).
@@ -47,6 +48,11 @@ public:
     // The camera-space direction of every pixel (rt_camera_directions in rt_hip.h): DEVICE [height * width][3], what a Sensor built
     // from it reproduces this camera with, bit for bit.  Asynchronous on `stream`; returns last_error.
     int directions(float* d_dirs);
+    // Point cloud, first step (rt_point_cloud_offsets in rt_hip.h): the kept pixels of this camera at poses[i], counted into
+    // d_offsets (DEVICE int64 [poses.size() + 1]) and staged in the caller's workspace for point_cloud_fill below.  The stream is an
+    // argument and nothing in the camera is written: host threads may share one.  Returns the error code, last_error stays.
+    int point_cloud_offsets(void* on_stream, Scene& scene, const std::vector<lre>& poses, float min_range, float max_range,
+                            const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes) const;
     // rotate_first >= 0: the stripe owner rotates with the frame index -- frame i renders the stripes of owner
     // (rank + rotate_first + i) % num_ranks, so that every rank's share of a group of frames is the same (rt_hip.h)
     void render_scene_stripes_batch(Scene& scene, const lre* poses, int count, uchar3* const* local_ptrs, size_t local_pitch,
@@ -60,3 +66,9 @@ public:
     void render_scene_stripes(Scene& scene, uchar3* local_ptr, size_t local_pitch, int stripe_rows, int rank, int num_ranks,
                               bool synchronize = false);
 };
+
+// Point cloud, second step (rt_point_cloud_fill in rt_hip.h; also declared in Sensor.h): the points of the workspace a
+// point_cloud_offsets call of a camera or sensor of this size left, with the same poses and fields, into the wanted DEVICE arrays of
+// `out`, the first `capacity` of them.  Needs no scene.  Asynchronous on `on_stream`; returns the error code.
+int point_cloud_fill(void* on_stream, int width, int height, const std::vector<transforms::lre>& poses, uint32_t fields,
+                     const void* d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud& out);

@@ -10,6 +10,7 @@
 #include "transforms.hpp"
 
 struct RtGBuffer;
+struct RtPointCloud;
 struct RtRayTable;
 
 class Sensor {
@@ -42,7 +43,17 @@ public:
     int rays_on(void* on_stream, const transforms::lre& at, float* d_origins, float* d_directions) const;
     int render_gbuffer_on(void* on_stream, Scene& scene, const std::vector<transforms::lre>& poses, const RtGBuffer& out,
                           uint8_t* const* d_imgs = nullptr, size_t pitch = 0) const;
+    // Point cloud, first step (rt_point_cloud_offsets_table in rt_hip.h): as Camera::point_cloud_offsets, the rays from this
+    // sensor's table.  Writes nothing in the sensor; returns the error code and leaves last_error alone.
+    int point_cloud_offsets(void* on_stream, Scene& scene, const std::vector<transforms::lre>& poses, float min_range, float max_range,
+                            const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes) const;
 
 private:
     RtRayTable* d_table = nullptr;
 };
+
+// Point cloud, second step (rt_point_cloud_fill in rt_hip.h; also declared in Camera.h): the points of the workspace a
+// point_cloud_offsets call of a camera or sensor of this size left, with the same poses and fields, into the wanted DEVICE arrays of
+// `out`, the first `capacity` of them.  Needs no scene.  Asynchronous on `on_stream`; returns the error code.
+int point_cloud_fill(void* on_stream, int width, int height, const std::vector<transforms::lre>& poses, uint32_t fields,
+                     const void* d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud& out);

@@ -895,6 +895,29 @@ int Camera::render_gbuffer(Scene& scene, const std::vector<lre>& poses, const Rt
     return last_error = rt_render_gbuffer(scene.d_scene, p, (int32_t)poses.size(), d_imgs, pitch, &out, stream, 0);
 }
 
+int Camera::point_cloud_offsets(void* on_stream, Scene& scene, const std::vector<lre>& poses, float min_range, float max_range,
+                                const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes) const
+{
+    if (!scene.d_scene || poses.empty() || poses.size() > (size_t)RT_MAX_BATCH) return RT_E_INVALID;
+    RtCameraParams p[RT_MAX_BATCH];
+    for (size_t i = 0; i < poses.size(); i++) p[i] = camera_params(*this, poses[i]);
+    return rt_point_cloud_offsets(scene.d_scene, p, (int32_t)poses.size(), min_range, max_range, d_mask, fields, d_offsets, d_workspace,
+                                  workspace_bytes, on_stream, 0);
+}
+
+int point_cloud_fill(void* on_stream, int width, int height, const std::vector<lre>& poses, uint32_t fields, const void* d_workspace,
+                     size_t workspace_bytes, int64_t capacity, const RtPointCloud& out)
+{
+    if (poses.empty() || poses.size() > (size_t)RT_MAX_BATCH) return RT_E_INVALID;
+    RtCameraParams p[RT_MAX_BATCH];
+    memset(p, 0, sizeof p);
+    for (size_t i = 0; i < poses.size(); i++) {                 // (the fill reads the size and camera_pose only)
+        p[i].width = width; p[i].height = height;
+        memcpy(p[i].camera_pose, &poses[i], sizeof p[i].camera_pose);
+    }
+    return rt_point_cloud_fill(p, (int32_t)poses.size(), fields, d_workspace, workspace_bytes, capacity, &out, on_stream, 0);
+}
+
 int Camera::directions(float* d_dirs)
 {
     RtCameraParams p = camera_params(*this, pose);
@@ -943,6 +966,16 @@ int Sensor::render_gbuffer_on(void* on_stream, Scene& scene, const std::vector<l
     RtCameraParams p[RT_MAX_BATCH];
     for (size_t i = 0; i < poses.size(); i++) p[i] = sensor_params(*this, poses[i]);
     return rt_render_gbuffer_table(scene.d_scene, d_table, p, (int32_t)poses.size(), d_imgs, pitch, &out, on_stream, 0);
+}
+
+int Sensor::point_cloud_offsets(void* on_stream, Scene& scene, const std::vector<lre>& poses, float min_range, float max_range,
+                                const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes) const
+{
+    if (!d_table || !scene.d_scene || poses.empty() || poses.size() > (size_t)RT_MAX_BATCH) return RT_E_INVALID;
+    RtCameraParams p[RT_MAX_BATCH];
+    for (size_t i = 0; i < poses.size(); i++) p[i] = sensor_params(*this, poses[i]);
+    return rt_point_cloud_offsets_table(scene.d_scene, d_table, p, (int32_t)poses.size(), min_range, max_range, d_mask, fields, d_offsets,
+                                        d_workspace, workspace_bytes, on_stream, 0);
 }
 
 int Sensor::rays(float* d_origins, float* d_directions) { return last_error = rays_on(stream, pose, d_origins, d_directions); }

@@ -292,6 +292,45 @@ int rth_sensor_render_gbuffer(RthSensor* n, RthScene* s, const float* poses6, in
     return rc;
 }
 
+static bool lre_batch(const float* poses6, int32_t count, std::vector<lre>& poses)
+{
+    if (!poses6 || count < 1 || count > RT_MAX_BATCH) return false;
+    poses.resize((size_t)count);
+    for (int i = 0; i < count; i++) poses[(size_t)i] = LRE(poses6 + 6 * i);
+    return true;
+}
+int rth_camera_point_cloud_offsets(RthCamera* c, RthScene* s, const float* poses6, int32_t count, float min_range, float max_range,
+                                   const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes,
+                                   void* stream, int synchronize)
+{
+    std::vector<lre> poses;
+    if (!c || !s || !lre_batch(poses6, count, poses)) return RT_E_INVALID;
+    const int rc = c->cam.point_cloud_offsets(stream, s->scene, poses, min_range, max_range, d_mask, fields, d_offsets, d_workspace,
+                                              workspace_bytes);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+int rth_sensor_point_cloud_offsets(RthSensor* n, RthScene* s, const float* poses6, int32_t count, float min_range, float max_range,
+                                   const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes,
+                                   void* stream, int synchronize)
+{
+    std::vector<lre> poses;
+    if (!n || !s || !lre_batch(poses6, count, poses)) return RT_E_INVALID;
+    const int rc = n->sensor.point_cloud_offsets(stream, s->scene, poses, min_range, max_range, d_mask, fields, d_offsets, d_workspace,
+                                                 workspace_bytes);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+int rth_point_cloud_fill(int32_t width, int32_t height, const float* poses6, int32_t count, uint32_t fields, const void* d_workspace,
+                         size_t workspace_bytes, int64_t capacity, const void* cloud, void* stream, int synchronize)
+{
+    std::vector<lre> poses;
+    if (!cloud || !lre_batch(poses6, count, poses)) return RT_E_INVALID;
+    const int rc = point_cloud_fill(stream, width, height, poses, fields, d_workspace, workspace_bytes, capacity, *(const RtPointCloud*)cloud);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+
 int rth_camera_render_scene_stripes_batch(RthCamera* c, RthScene* s, const float* poses6, void* const* d_locals, size_t local_pitch,
                                           int32_t count, int32_t stripe_rows, int32_t rank, int32_t num_ranks, int synchronize)
 {

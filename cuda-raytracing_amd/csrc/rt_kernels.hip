@@ -1502,6 +1502,96 @@ __global__ __launch_bounds__(kPrimBlock, 8) void gbuffer_kernel(const RenderPara
                                                                            VIEW ? p.view_base + (uint32_t)frame * p.view_frame_stride : 0u, &g);
 }
 
+// Point clouds (rt_point_cloud_offsets / rt_point_cloud_fill, include/rt_hip.h "point clouds"): the kept pixels
+// of the staged G-buffer planes, packed in (frame, y, x) order.  A chunk is 64 consecutive pixels of ONE frame's row-major order -- a
+// frame has chunks_per_frame = ceil(px / 64) of them, the last one partial -- and one wave works on one chunk: its 64-bit ballot of the
+// keep predicate is the chunk's count (popcount) and every kept lane's place in the chunk (mbcnt).  No atomics and no dependence on
+// the order of workgroups: the order of the points is the order of the pixels.  Four chunks per workgroup of 256 threads.
+constexpr int kCloudBlock = 256, kCloudChunk = 64;
+struct CloudCountParams {
+    const float* t;             // staged planes [count][px]
+    const int32_t* instance;
+    const uint8_t* mask;        // [px] or null
+    int64_t px;                 // pixels per frame
+    int32_t chunks_per_frame, nchunks;
+    float min_range, max_range;
+    int32_t* counts;            // [nchunks]: what the scan reads
+    unsigned long long* keep;   // [nchunks]: the chunk's ballot, for the fill (which is given neither the gate nor the mask)
+};
+__global__ __launch_bounds__(kCloudBlock) void cloud_count_kernel(const CloudCountParams c)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int64_t chunk = (int64_t)blockIdx.x * (kCloudBlock / kCloudChunk) + ((int)threadIdx.x >> 6);
+    if (chunk >= (int64_t)c.nchunks) return;                    // (wave-uniform)
+    const int32_t frame = (int32_t)chunk / c.chunks_per_frame;
+    const int64_t at = (int64_t)((int32_t)chunk - frame * c.chunks_per_frame) * kCloudChunk + lane;     // pixel y * width + x
+    bool keep = false;
+    if (at < c.px) {
+        const size_t o = (size_t)frame * (size_t)c.px + (size_t)at;
+        const float t = c.t[o];
+        keep = c.instance[o] >= 0 && t >= c.min_range && t <= c.max_range && (!c.mask || c.mask[at] != 0);
+    }
+    const unsigned long long b = __ballot(keep);
+    if (lane == 0) { c.counts[chunk] = __popcll(b); c.keep[chunk] = b; }
+}
+
+// d_offsets[i] = the scanned offset of frame i's first chunk; d_offsets[count] = the total
+__global__ __launch_bounds__(64) void cloud_frame_offsets_kernel(const int64_t* chunk_offsets, int32_t chunks_per_frame, int32_t count, int64_t* d_offsets)
+{
+    const int i = (int)threadIdx.x;
+    if (i <= count) d_offsets[i] = chunk_offsets[(size_t)i * (size_t)chunks_per_frame];
+}
+
+struct CloudFillParams {
+    const int64_t* chunk_offsets;       // [nchunks + 1], scanned
+    const unsigned long long* keep;     // [nchunks]
+    const float* t;                     // staged planes; those the fields did not stage are null and their outputs are too
+    const int32_t *instance, *triangle;
+    const float *location, *normal, *uv;
+    int64_t px;
+    int32_t chunks_per_frame, nchunks;
+    int64_t capacity;
+    float* range;                       // RtPointCloud
+    int32_t *pixel, *frame, *out_instance, *out_triangle;
+    float *position, *local, *out_normal, *out_uv;
+    Q4 q_pose[kMaxBatch];               // euler2quat(camera_pose ypr) of frame i, as GBufParams::q_pose
+    float origin[kMaxBatch][3];         // camera_pose xyz of frame i, as FrameParams::origin
+};
+static_assert(sizeof(CloudFillParams) <= 4096, "kernel arguments must fit in 4 KB");
+// Everything read from the workspace is data: the pixel index is bounded by px before any plane is read and the slot -- compared as an
+// unsigned number, so that a negative offset of a stale workspace is large -- by capacity before anything is written.
+__global__ __launch_bounds__(kCloudBlock) void cloud_fill_kernel(const CloudFillParams c)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int64_t chunk = (int64_t)blockIdx.x * (kCloudBlock / kCloudChunk) + ((int)threadIdx.x >> 6);
+    if (chunk >= (int64_t)c.nchunks) return;                    // (wave-uniform)
+    const int32_t frame = (int32_t)chunk / c.chunks_per_frame;
+    const int64_t at = (int64_t)((int32_t)chunk - frame * c.chunks_per_frame) * kCloudChunk + lane;
+    const unsigned long long b = c.keep[chunk];                 // the count kernel's ballot
+    if (at >= c.px || !((b >> lane) & 1ull)) return;
+    // kept lanes below this one: v_mbcnt_lo / v_mbcnt_hi of the ballot
+    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    const unsigned long long slot = (unsigned long long)c.chunk_offsets[chunk] + below;
+    if (slot >= (unsigned long long)c.capacity) return;
+    const size_t o = (size_t)frame * (size_t)c.px + (size_t)at, j = (size_t)slot;
+    if (c.range) c.range[j] = c.t[o];
+    if (c.pixel) c.pixel[j] = (int32_t)at;
+    if (c.frame) c.frame[j] = frame;
+    if (c.out_instance) c.out_instance[j] = c.instance[o];
+    if (c.out_triangle) c.out_triangle[j] = c.triangle[o];
+    if (c.position || c.local) {
+        const V3 loc = v3(c.location[o * 3], c.location[o * 3 + 1], c.location[o * 3 + 2]);
+        if (c.position) { c.position[j * 3] = loc.x; c.position[j * 3 + 1] = loc.y; c.position[j * 3 + 2] = loc.z; }
+        if (c.local) {
+            // rt_hip.h, point clouds rule 5: render_pixel's depth expression, all three components
+            const V3 l = apply_quat(c.q_pose[frame], v3(loc.x - c.origin[frame][0], loc.y - c.origin[frame][1], loc.z - c.origin[frame][2]));
+            c.local[j * 3] = l.x; c.local[j * 3 + 1] = l.y; c.local[j * 3 + 2] = l.z;
+        }
+    }
+    if (c.out_normal) { c.out_normal[j * 3] = c.normal[o * 3]; c.out_normal[j * 3 + 1] = c.normal[o * 3 + 1]; c.out_normal[j * 3 + 2] = c.normal[o * 3 + 2]; }
+    if (c.out_uv) { c.out_uv[j * 2] = c.uv[o * 2]; c.out_uv[j * 2 + 1] = c.uv[o * 2 + 1]; }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Extension kernel (rt_render_ex): samples per pixel, specular bounces, and the sun + shadow pass that the reference
 // carries as commented-out code (raycast.cu:249-290).  The reference has no implementation of these, so the
@@ -7287,6 +7377,152 @@ int rt_ray_table_rays(const RtRayTable* t, const RtCameraParams* pose, float* d_
     hipLaunchKernelGGL(ray_table_rays_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, t->d_table, t->width,
                        t->tiles_x, npix, d_origins, d_directions);
     RT_HIP(hipGetLastError());
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+// ---- point clouds (include/rt_hip.h "point clouds") ------------------------------------------------------
+extern "C++" {
+namespace {
+// The workspace of one rt_point_cloud_offsets call, every part on a 256-byte boundary: the scan's own block (the chunk counts, int32
+// [nchunks], and its levels' block totals: offsets_bytes), the scanned chunk offsets (int64 [nchunks + 1]), the chunks' ballots
+// (uint64 [nchunks]), then the staged planes [count][px](xk) the fields need.  Both calls derive it from the same four arguments.
+struct CloudLayout {
+    int64_t px;
+    int32_t chunks_per_frame, nchunks;
+    int64_t blocks[8];
+    int levels;
+    size_t chunk_offsets, keep, t, instance, triangle, location, normal, uv;    // byte offsets; 0 = not staged (the scan's block is first)
+    size_t bytes;
+};
+bool cloud_layout(int32_t width, int32_t height, int32_t count, uint32_t fields, CloudLayout& L)
+{
+    if (width < 1 || height < 1 || count < 1 || count > kMaxBatch || fields == 0 || (fields & ~RT_CLOUD_ALL)) return false;
+    L.px = (int64_t)width * (int64_t)height;
+    const int64_t per_frame = (L.px + kCloudChunk - 1) / kCloudChunk, n = per_frame * count;
+    if (n > (int64_t)INT32_MAX) return false;                   // (the scan's int32 n)
+    L.chunks_per_frame = (int32_t)per_frame; L.nchunks = (int32_t)n;
+    size_t at = offsets_bytes(n, L.blocks, &L.levels);
+    const size_t pixels = (size_t)L.px * (size_t)count;
+    auto part = [&](bool wanted, size_t bytes) { const size_t o = wanted ? at : 0; if (wanted) at += scan_align(bytes); return o; };
+    L.chunk_offsets = part(true, ((size_t)n + 1) * sizeof(int64_t));
+    L.keep = part(true, (size_t)n * sizeof(unsigned long long));
+    L.t = part(true, pixels * sizeof(float));
+    L.instance = part(true, pixels * sizeof(int32_t));
+    L.triangle = part(fields & RT_CLOUD_TRIANGLE, pixels * sizeof(int32_t));
+    L.location = part(fields & (RT_CLOUD_POSITION | RT_CLOUD_LOCAL), pixels * 3 * sizeof(float));
+    L.normal = part(fields & RT_CLOUD_NORMAL, pixels * 3 * sizeof(float));
+    L.uv = part(fields & RT_CLOUD_UV, pixels * 2 * sizeof(float));
+    L.bytes = at;
+    return true;
+}
+// what both calls ask of their frames (render_gbuffer's checks of cams and count)
+bool cloud_frames_ok(const RtCameraParams* cams, int32_t count)
+{
+    if (!cams || count < 1 || count > kMaxBatch || !camera_ok(&cams[0])) return false;
+    for (int i = 1; i < count; i++) if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) return false;
+    return true;
+}
+int point_cloud_offsets(RtScene* s, const RtRayTable* table, const RtCameraParams* cams, int32_t count, float min_range, float max_range,
+                        const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream,
+                        int synchronize)
+{
+    // (every argument is judged before the scene is touched)
+    if (!s || !cloud_frames_ok(cams, count) || !d_offsets || !d_workspace) return RT_E_INVALID;
+    if (!(min_range <= max_range)) return RT_E_INVALID;         // (a NaN bound fails the comparison)
+    CloudLayout L;
+    if (!cloud_layout(cams[0].width, cams[0].height, count, fields, L) || workspace_bytes < L.bytes) return RT_E_INVALID;
+    if (table && (cams[0].width != table->width || cams[0].height != table->height)) return RT_E_INVALID;
+    char* const ws = (char*)d_workspace;
+    const hipStream_t st = (hipStream_t)stream;
+    {
+        RT_SCENE_CALL(s);
+        RenderParams p;
+        int rc = fill_params(p, s, cams, nullptr, count, 0, true);
+        if (rc) return rc;
+        GBufParams g;
+        memset(&g, 0, sizeof g);
+        g.t = (float*)(ws + L.t); g.instance = (int32_t*)(ws + L.instance);
+        if (L.triangle) g.triangle = (int32_t*)(ws + L.triangle);
+        if (L.location) g.location = (float*)(ws + L.location);
+        if (L.normal) g.normal = (float*)(ws + L.normal);
+        if (L.uv) g.uv = (float*)(ws + L.uv);
+        if ((rc = launch_gbuffer(s, p, g, st, table ? table->d_table : nullptr))) return rc;
+    }
+    // (the scene is no longer needed: the rest reads the workspace only)
+    CloudCountParams c;
+    c.t = (const float*)(ws + L.t); c.instance = (const int32_t*)(ws + L.instance); c.mask = d_mask;
+    c.px = L.px; c.chunks_per_frame = L.chunks_per_frame; c.nchunks = L.nchunks;
+    c.min_range = min_range; c.max_range = max_range;
+    c.counts = (int32_t*)ws; c.keep = (unsigned long long*)(ws + L.keep);
+    const unsigned grid = (unsigned)(((int64_t)L.nchunks + kCloudBlock / kCloudChunk - 1) / (kCloudBlock / kCloudChunk));
+    hipLaunchKernelGGL(cloud_count_kernel, dim3(grid), dim3(kCloudBlock), 0, st, c);
+    scan_offsets(d_workspace, L.nchunks, (int64_t*)(ws + L.chunk_offsets), L.blocks, L.levels, st);
+    hipLaunchKernelGGL(cloud_frame_offsets_kernel, dim3(1), dim3(64), 0, st, (const int64_t*)(ws + L.chunk_offsets), L.chunks_per_frame, count,
+                       d_offsets);
+    RT_HIP(hipGetLastError());
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t rt_point_cloud_workspace_bytes(int32_t width, int32_t height, int32_t count, uint32_t fields)
+{
+    CloudLayout L;
+    return cloud_layout(width, height, count, fields, L) ? L.bytes : 0;
+}
+
+int rt_point_cloud_offsets(RtScene* s, const RtCameraParams* cams, int32_t count, float min_range, float max_range, const uint8_t* d_mask,
+                           uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    return point_cloud_offsets(s, nullptr, cams, count, min_range, max_range, d_mask, fields, d_offsets, d_workspace, workspace_bytes, stream,
+                               synchronize);
+}
+
+int rt_point_cloud_offsets_table(RtScene* s, const RtRayTable* table, const RtCameraParams* poses, int32_t count, float min_range,
+                                 float max_range, const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace,
+                                 size_t workspace_bytes, void* stream, int synchronize)
+{
+    if (!table) return RT_E_INVALID;
+    return point_cloud_offsets(s, table, poses, count, min_range, max_range, d_mask, fields, d_offsets, d_workspace, workspace_bytes, stream,
+                               synchronize);
+}
+
+int rt_point_cloud_fill(const RtCameraParams* cams, int32_t count, uint32_t fields, const void* d_workspace, size_t workspace_bytes,
+                        int64_t capacity, const RtPointCloud* out, void* stream, int synchronize)
+{
+    if (!cloud_frames_ok(cams, count) || !d_workspace || !out || capacity < 0) return RT_E_INVALID;
+    CloudLayout L;
+    if (!cloud_layout(cams[0].width, cams[0].height, count, fields, L) || workspace_bytes < L.bytes) return RT_E_INVALID;
+    const void* const wanted[9] = { out->range, out->pixel, out->frame, out->instance, out->triangle, out->position, out->local, out->normal, out->uv };
+    bool any = false;
+    for (int k = 0; k < 9; k++) {
+        if (wanted[k] && !(fields & (1u << k))) return RT_E_INVALID;    // (its plane was not staged)
+        any = any || wanted[k];
+    }
+    if (!any) return RT_E_INVALID;
+    if (capacity > 0) {
+        const char* const ws = (const char*)d_workspace;
+        CloudFillParams c;
+        memset(&c, 0, sizeof c);
+        c.chunk_offsets = (const int64_t*)(ws + L.chunk_offsets); c.keep = (const unsigned long long*)(ws + L.keep);
+        c.t = (const float*)(ws + L.t); c.instance = (const int32_t*)(ws + L.instance);
+        if (L.triangle) c.triangle = (const int32_t*)(ws + L.triangle);
+        if (L.location) c.location = (const float*)(ws + L.location);
+        if (L.normal) c.normal = (const float*)(ws + L.normal);
+        if (L.uv) c.uv = (const float*)(ws + L.uv);
+        c.px = L.px; c.chunks_per_frame = L.chunks_per_frame; c.nchunks = L.nchunks; c.capacity = capacity;
+        c.range = out->range; c.pixel = out->pixel; c.frame = out->frame; c.out_instance = out->instance; c.out_triangle = out->triangle;
+        c.position = out->position; c.local = out->local; c.out_normal = out->normal; c.out_uv = out->uv;
+        for (int i = 0; i < count; i++) {
+            c.q_pose[i] = euler2quat(v3(cams[i].camera_pose[3], cams[i].camera_pose[4], cams[i].camera_pose[5]));
+            for (int a = 0; a < 3; a++) c.origin[i][a] = cams[i].camera_pose[a];
+        }
+        const unsigned grid = (unsigned)(((int64_t)L.nchunks + kCloudBlock / kCloudChunk - 1) / (kCloudBlock / kCloudChunk));
+        hipLaunchKernelGGL(cloud_fill_kernel, dim3(grid), dim3(kCloudBlock), 0, (hipStream_t)stream, c);
+        RT_HIP(hipGetLastError());
+    }
     RT_WAIT_IF(synchronize, stream);
     return RT_OK;
 }

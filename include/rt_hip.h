@@ -390,6 +390,71 @@ int rt_ray_table_rays(const RtRayTable *table, const RtCameraParams *pose, float
 int rt_render_gbuffer_table(RtScene *scene, const RtRayTable *table, const RtCameraParams *poses, int32_t count /* 1..RT_MAX_BATCH */,
                             uint8_t *const *d_imgs /* NULL = no colour frames */, size_t pitch, const RtGBuffer *out, void *stream,
                             int synchronize);
+/* ---- point clouds: the compacted returns of `count` (1..RT_MAX_BATCH) camera or sensor frames of one size --
+ *      only the pixels that hit something inside the range gate and the valid area, packed, with the sensor-frame coordinates and
+ *      the ring / column index of each point.  The accepted hit of pixel (x, y) of frame i is exactly what rt_render_gbuffer (cameras)
+ *      or rt_render_gbuffer_table (a ray table) puts in its planes for that pixel.
+ *      1. Keep rule.  A pixel is kept iff instance >= 0, and t >= min_range and t <= max_range as fp32 comparisons (a NaN t is
+ *         not kept; min_range = 0, max_range = +inf keeps every hit), and d_mask == NULL || d_mask[y * width + x] != 0 (d_mask:
+ *         DEVICE uint8 [height][width], shared by all frames).
+ *      2. Order.  Kept pixels are ordered by (i, y, x): deterministic, independent of launch form, stream or run.
+ *      3. Offsets.  d_offsets: DEVICE int64 [count + 1]; d_offsets[i] = the number of kept pixels in frames < i, d_offsets[count]
+ *         the total.
+ *      4. Fields of point j (RtPointCloud): each optional, tight, indexed in size_t.  range = t; pixel = y * width + x (ring y,
+ *         column x of a spinning lidar); frame = i; instance, triangle, position (= the location plane), normal, uv = the G-buffer
+ *         planes' bits of that pixel: the numpy compaction of the plane.
+ *      5. local = apply_lre(camera_pose_i, location), all three components, by rule 2 of the G-buffer frames: q = euler2quat(yaw,
+ *         pitch, roll of camera_pose_i) on the host, v = location - camera position per component, a, b, c, d as there, and, each
+ *         left to right in fp32 without contraction,
+ *           local.x = q.x*b - q.y*a - q.z*d + q.w*c
+ *           local.y = q.x*c - q.z*a - q.w*b + q.y*d
+ *           local.z = q.x*d - q.w*a - q.y*c + q.z*b        (= the depth plane, bit for bit)
+ *         (the quaternion is stored (w, x, y, z) in .x .y .z .w).
+ *      Two steps, so that one traversal serves an exact allocation and a fully asynchronous use alike:
+ *      rt_point_cloud_offsets(_table) renders the staging planes `fields` need into the caller's workspace with rt_render_gbuffer's
+ *      launch (its decisions, its view-pool behaviour, its serialisation of host threads on one scene; t and instance always,
+ *      triangle, normal, uv when asked, location for position or local; no images, no depth plane), counts the kept pixels per chunk
+ *      of 64 consecutive pixels of a frame, scans the counts (the per-chunk offsets stay in the workspace) and writes d_offsets.
+ *      Nothing of the scene is held after the launch: calls on one scene with different workspaces overlap as G-buffer calls do.
+ *      rt_point_cloud_fill needs no scene: it reads the workspace -- unchanged since *_offsets, later in the same stream order, with
+ *      the same cams, count and fields -- and writes point j only when j < capacity: a cloud larger than `capacity` is truncated to
+ *      its first `capacity` points (d_offsets keeps the true counts), capacity = 0 writes nothing.  Of cams only width, height and
+ *      camera_pose are read.  Every read is bounded by sizes derived from the arguments and every write by capacity: a stale or
+ *      foreign workspace gives wrong points, never an access outside the workspace or the outputs.
+ *      RT_E_INVALID, judged before any device call: the cases of rt_render_gbuffer(_table) that apply; NULL d_offsets or workspace;
+ *      a workspace smaller than rt_point_cloud_workspace_bytes; fields == 0 or unknown bits; a NaN min_range or max_range, or
+ *      min_range > max_range; more than 2^31 - 1 chunks; for fill also a NULL `out`, a non-NULL pointer whose bit is not in
+ *      `fields` (a NULL pointer for a bit that is set is fine: not wanted), a negative capacity, no output at all. ----------- */
+#define RT_CLOUD_RANGE    0x001u
+#define RT_CLOUD_PIXEL    0x002u
+#define RT_CLOUD_FRAME    0x004u
+#define RT_CLOUD_INSTANCE 0x008u
+#define RT_CLOUD_TRIANGLE 0x010u
+#define RT_CLOUD_POSITION 0x020u
+#define RT_CLOUD_LOCAL    0x040u
+#define RT_CLOUD_NORMAL   0x080u
+#define RT_CLOUD_UV       0x100u
+#define RT_CLOUD_ALL      0x1ffu
+typedef struct RtPointCloud {   /* every pointer optional (NULL = not wanted); DEVICE, tight, [capacity](xk); bit order of RT_CLOUD_* */
+    float   *range;             /* t */
+    int32_t *pixel;             /* y * width + x */
+    int32_t *frame;             /* i */
+    int32_t *instance, *triangle;
+    float   *position;          /* [..][3] world: the location plane */
+    float   *local;             /* [..][3] apply_lre(camera_pose_i, location) (rule 5) */
+    float   *normal;            /* [..][3] */
+    float   *uv;                /* [..][2] */
+} RtPointCloud;
+/* 0 for a size or count < 1, count > RT_MAX_BATCH, fields == 0 or unknown bits, or more than 2^31 - 1 chunks */
+size_t rt_point_cloud_workspace_bytes(int32_t width, int32_t height, int32_t count, uint32_t fields);
+int rt_point_cloud_offsets(RtScene *scene, const RtCameraParams *cams, int32_t count /* 1..RT_MAX_BATCH */, float min_range,
+                           float max_range, const uint8_t *d_mask /* NULL = every pixel valid */, uint32_t fields, int64_t *d_offsets,
+                           void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+int rt_point_cloud_offsets_table(RtScene *scene, const RtRayTable *table, const RtCameraParams *poses, int32_t count, float min_range,
+                                 float max_range, const uint8_t *d_mask, uint32_t fields, int64_t *d_offsets, void *d_workspace,
+                                 size_t workspace_bytes, void *stream, int synchronize);
+int rt_point_cloud_fill(const RtCameraParams *cams, int32_t count, uint32_t fields, const void *d_workspace, size_t workspace_bytes,
+                        int64_t capacity, const RtPointCloud *out, void *stream, int synchronize);
 /* same frame plus the parity planes (instrumented copy of the kernel: counts every visit) */
 int rt_render_debug(RtScene *scene, const RtCameraParams *cam, uint8_t *d_img, size_t pitch,
                     const RtDebugPlanes *planes, void *stream, int synchronize);

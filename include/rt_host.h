@@ -113,6 +113,20 @@ int rth_sensor_rays(RthSensor *s, const float *pose6, float *d_origins, float *d
  * rth_sensor_rays write nothing in the sensor: host threads may share one. */
 int rth_sensor_render_gbuffer(RthSensor *n, RthScene *s, const float *poses6, int32_t count, const void *gbuffer,
                               void *const *d_imgs, size_t pitch, void *stream, int synchronize);
+/* Point clouds (rt_hip.h, "point clouds"): Camera::point_cloud_offsets / Sensor::point_cloud_offsets -- the kept pixels of `count`
+ * (1..RT_MAX_BATCH) poses counted into d_offsets (DEVICE int64 [count + 1]) and staged in the caller's workspace of
+ * rt_point_cloud_workspace_bytes bytes (of width, height, count, fields); on `stream`, nothing written in the camera or sensor -- and
+ * point_cloud_fill: the first `capacity` points of that workspace into cloud = a const RtPointCloud * of device arrays, with the
+ * same size, poses and fields; it needs no scene. */
+int rth_camera_point_cloud_offsets(RthCamera *c, RthScene *s, const float *poses6, int32_t count, float min_range, float max_range,
+                                   const uint8_t *d_mask, uint32_t fields, int64_t *d_offsets, void *d_workspace,
+                                   size_t workspace_bytes, void *stream, int synchronize);
+int rth_sensor_point_cloud_offsets(RthSensor *n, RthScene *s, const float *poses6, int32_t count, float min_range, float max_range,
+                                   const uint8_t *d_mask, uint32_t fields, int64_t *d_offsets, void *d_workspace,
+                                   size_t workspace_bytes, void *stream, int synchronize);
+int rth_point_cloud_fill(int32_t width, int32_t height, const float *poses6, int32_t count, uint32_t fields,
+                         const void *d_workspace, size_t workspace_bytes, int64_t capacity, const void *cloud, void *stream,
+                         int synchronize);
 int rth_camera_render_scene_stripes_batch(RthCamera *c, RthScene *s, const float *poses6, void *const *d_locals,
                                           size_t local_pitch, int32_t count, int32_t stripe_rows, int32_t rank,
                                           int32_t num_ranks, int synchronize);
