@@ -89,6 +89,13 @@ class RtGBuffer(C.Structure):               # include/rt_hip.h (device planes [c
     _fields_ = [(n, _vp) for n in _GBUFFER_OUTPUTS]
 
 
+class RtRollingPose(C.Structure):           # include/rt_hip.h, "rolling frames": the pose of one slice and its inverse
+    _fields_ = [("camera_pose", C.c_float * 6), ("inv_camera_pose", C.c_float * 6)]
+
+
+ROLLING_AXES = {"x": 0, "y": 1}             # the axis argument of the rolling calls: "x" = a slice is columns, "y" = rows
+
+
 # the fields of a point cloud in RT_CLOUD_* bit order (include/rt_hip.h, "point clouds"): name -> (trailing shape, type)
 _CLOUD_FIELDS = dict(range=((), np.float32), pixel=((), np.int32), frame=((), np.int32), instance=((), np.int32), triangle=((), np.int32),
                      position=((3,), np.float32), local=((3,), np.float32), normal=((3,), np.float32), uv=((2,), np.float32))
@@ -170,7 +177,7 @@ RT_HIP_SYMBOLS = [
     "rt_abi_version", "rt_build_info", "rt_device_count", "rt_set_device", "rt_malloc", "rt_malloc_pitch", "rt_free", "rt_memcpy_d2h",
     "rt_memcpy_h2d", "rt_memcpy2d_d2h", "rt_stream_synchronize", "rt_device_synchronize", "rt_error_string",
     "rt_bvh_build", "rt_scene_upload", "rt_scene_update_instance", "rt_scene_update_instance_async", "rt_scene_refit_mesh", "rt_scene_refit_mesh_device", "rt_scene_rebuild_mesh_device", "rt_scene_debug_read", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh_capacity", "rt_scene_mesh_flags", "rt_render", "rt_render_overlapped", "rt_render_overlapped_stats", "rt_scene_view_stats", "rt_scene_dir_table_stats", "rt_scene_reserve_views", "rt_scene_memory", "rt_scene_loop_stats", "rt_render_batch",
-    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_point_cloud_workspace_bytes", "rt_point_cloud_offsets", "rt_point_cloud_offsets_table", "rt_point_cloud_fill", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
+    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_point_cloud_workspace_bytes", "rt_point_cloud_offsets", "rt_point_cloud_offsets_table", "rt_point_cloud_fill", "rt_rolling_slices", "rt_rolling_workspace_bytes", "rt_render_gbuffer_rolling", "rt_point_cloud_rolling_workspace_bytes", "rt_point_cloud_offsets_rolling", "rt_point_cloud_fill_rolling", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
@@ -188,7 +195,7 @@ RT_HOST_SYMBOLS = [
     "rth_scene_set_material_params", "rth_scene_add_mesh", "rth_scene_add_mesh_instance", "rth_scene_upload_to_device", "rth_scene_update_mesh_instance", "rth_scene_update_mesh_instance_async", "rth_scene_refit_mesh", "rth_scene_rebuild_mesh",
     "rth_scene_num_mesh_instances", "rth_scene_device_handle", "rth_instance_build", "rth_camera_create", "rth_camera_free",
     "rth_camera_set_pose", "rth_camera_set_stream", "rth_camera_render_scene", "rth_camera_render_scene_stripes",
-    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_directions", "rth_sensor_create", "rth_sensor_destroy", "rth_sensor_set_pose", "rth_sensor_set_stream", "rth_sensor_rays", "rth_sensor_render_gbuffer", "rth_camera_point_cloud_offsets", "rth_sensor_point_cloud_offsets", "rth_point_cloud_fill", "rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
+    "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_directions", "rth_sensor_create", "rth_sensor_destroy", "rth_sensor_set_pose", "rth_sensor_set_stream", "rth_sensor_rays", "rth_sensor_render_gbuffer", "rth_camera_point_cloud_offsets", "rth_sensor_point_cloud_offsets", "rth_point_cloud_fill", "rth_sensor_render_rolling", "rth_sensor_point_cloud_offsets_rolling", "rth_point_cloud_fill_rolling","rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
     "rth_camera_render_scene_ex", "rth_xorwow", "rth_save_png", "rth_write_png_bgr",
     "rth_read_image_bgr", "rth_zlib_inflate", "rth_overlay_text_bgr", "rth_display_image", "rth_on_mouse", "rth_on_key",
     "rth_camera_params", "rth_q_rsqrt", "rth_atanf", "rth_normalize", "rth_invert_lre", "rth_apply_lre", "rth_euler2quat",
@@ -298,6 +305,22 @@ def _declare(h, s):
     h.rt_point_cloud_fill.argtypes = [C.POINTER(RtCameraParams), C.c_int32, C.c_uint32, _vp, C.c_size_t, C.c_int64, C.POINTER(RtPointCloud), _vp, C.c_int]
     s.rth_camera_point_cloud_offsets.argtypes = [_vp, _vp, _f] + cloud_tail
     s.rth_sensor_point_cloud_offsets.argtypes = [_vp, _vp, _f] + cloud_tail
+    h.rt_rolling_slices.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i]
+    h.rt_rolling_workspace_bytes.restype = C.c_size_t
+    h.rt_rolling_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    h.rt_render_gbuffer_rolling.argtypes = [_vp, _vp, C.POINTER(RtRollingPose), C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), C.c_size_t,
+                                            C.POINTER(RtGBuffer), _vp, _vp, C.c_size_t, _vp, C.c_int]
+    h.rt_point_cloud_rolling_workspace_bytes.restype = C.c_size_t
+    h.rt_point_cloud_rolling_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32]
+    h.rt_point_cloud_offsets_rolling.argtypes = [_vp, _vp, C.POINTER(RtRollingPose), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _vp,
+                                                 C.c_uint32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    roll_fill = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _vp, C.c_size_t, C.c_int64, C.POINTER(RtPointCloud), _vp, C.c_int]
+    h.rt_point_cloud_fill_rolling.argtypes = roll_fill
+    s.rth_point_cloud_fill_rolling.argtypes = roll_fill
+    s.rth_sensor_render_rolling.argtypes = [_vp, _vp, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RtGBuffer), _vp, C.POINTER(_vp),
+                                            C.c_size_t, _vp, C.c_size_t, _vp, C.c_int]
+    s.rth_sensor_point_cloud_offsets_rolling.argtypes = [_vp, _vp, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _vp,
+                                                         C.c_uint32, _vp, _vp, C.c_size_t, _vp, C.c_int]
     s.rth_point_cloud_fill.argtypes = [C.c_int32, C.c_int32, _f, C.c_int32, C.c_uint32, _vp, C.c_size_t, C.c_int64, C.POINTER(RtPointCloud), _vp, C.c_int]
     h.rt_ray_table_create.argtypes = [_vp, C.c_int32, C.c_int32, _vp, C.c_int, C.POINTER(_vp)]
     h.rt_ray_table_info.argtypes = [_vp, _i, _i, C.POINTER(C.c_size_t)]
@@ -1085,14 +1108,35 @@ def _render_gbuffer(call, what, owner, scene, poses, outputs, image, stream, as_
         return res
 
 
-def _point_cloud(call, what, owner, scene, poses, outputs, min_range, max_range, mask, stream, as_numpy):
+def _rolling_args(owner, poses, axis, slice_pixels):
+    """Sensor.render_rolling and Sensor.rolling_point_cloud: (poses float32 [n, slices, 6], axis number, slices), every ValueError of
+    the rolling arguments -- before any device call"""
+    if axis not in ROLLING_AXES:
+        raise ValueError("axis must be 'x' (a slice is columns) or 'y' (rows), got %r" % (axis,))
+    if isinstance(slice_pixels, bool) or int(slice_pixels) != slice_pixels or slice_pixels < 8 or slice_pixels % 8:
+        raise ValueError("slice_pixels must be a positive multiple of 8 (slices are whole 8x8 tiles), got %r" % (slice_pixels,))
+    ax = ROLLING_AXES[axis]
+    slices = -(-(owner.height if ax else owner.width) // int(slice_pixels))
+    P = np.asarray(poses, np.float32)
+    if P.ndim != 3 or P.shape[2] != 6 or P.shape[0] < 1:
+        raise ValueError("poses must be [frames, slices, 6] of (x, y, z, yaw, pitch, roll), got shape %s" % (P.shape,))
+    if P.shape[1] != slices:
+        raise ValueError("%d x %d with axis %r and slice_pixels %d has %d slices, poses has %d" % (owner.width, owner.height, axis, slice_pixels, slices, P.shape[1]))
+    return _fa(P), ax, slices
+
+
+def _point_cloud(call, what, owner, scene, poses, outputs, min_range, max_range, mask, stream, as_numpy, rolling=None):
     """Camera.point_cloud and Sensor.point_cloud: the argument checks -- all before any device call -- and, per group of RT_MAX_BATCH
     frames, the workspace, the offsets call, the one host read of the total, the exact allocation and the fill.  `call`:
-    rth_camera_point_cloud_offsets or rth_sensor_point_cloud_offsets; owner: .h, .width, .height, .current_pose()."""
+    rth_camera_point_cloud_offsets or rth_sensor_point_cloud_offsets; owner: .h, .width, .height, .current_pose().
+    rolling = (axis, slice_pixels) (Sensor.rolling_point_cloud): poses are [n, slices, 6], `call` is
+    rth_sensor_point_cloud_offsets_rolling and the fill is the rolling one, which finds the poses in the workspace."""
     outputs = tuple(outputs)
     if not outputs or [o for o in outputs if o not in _CLOUD_OUTPUTS] or len(set(outputs)) != len(outputs):
         raise ValueError("outputs must be a non-empty subset of %s, nothing twice, got %r" % (_CLOUD_OUTPUTS, outputs))
-    if poses is None:
+    if rolling is not None:
+        P, axis, slices = _rolling_args(owner, poses, *rolling)
+    elif poses is None:
         P = _fa(owner.current_pose()).reshape(1, 6)
     else:
         P = np.asarray(poses, np.float32)
@@ -1126,14 +1170,25 @@ def _point_cloud(call, what, owner, scene, poses, outputs, min_range, max_range,
         groups, ends, base = [], [], 0                              # per group: its fields; its frames' end offsets, running on
         for first in range(0, n, RT_MAX_BATCH):
             m = min(RT_MAX_BATCH, n - first)
-            ws_bytes = int(hip.rt_point_cloud_workspace_bytes(w, h, m, fields))
+            if rolling is not None:
+                ws_bytes = int(hip.rt_point_cloud_rolling_workspace_bytes(w, h, m, fields, slices))
+            else:
+                ws_bytes = int(hip.rt_point_cloud_workspace_bytes(w, h, m, fields))
             ws = sg.alloc((ws_bytes,), np.uint8)
             offsets = sg.alloc((m + 1,), np.int64)
             Pg = _fp(P[first:first + m])
-            check(call(owner.h, scene.h, Pg, m, lo, hi, d_mask, fields, sg.ptr(offsets), sg.ptr(ws), ws_bytes, sg.stream, sg.sync), what)
+            if rolling is not None:
+                check(call(owner.h, scene.h, Pg, m, slices, axis, rolling[1], lo, hi, d_mask, fields, sg.ptr(offsets), sg.ptr(ws), ws_bytes,
+                           sg.stream, sg.sync), what)
+            else:
+                check(call(owner.h, scene.h, Pg, m, lo, hi, d_mask, fields, sg.ptr(offsets), sg.ptr(ws), ws_bytes, sg.stream, sg.sync), what)
             total = sg.read_int64(offsets, m)                       # torch: the one host synchronisation per group, for the size of the outputs
             out = {k: sg.alloc((total,) + _CLOUD_FIELDS[k][0], _CLOUD_FIELDS[k][1]) for k in outputs}
-            if total:
+            if total and rolling is not None:
+                cloud = RtPointCloud(*[sg.ptr(out[k]) if k in out else None for k in _CLOUD_OUTPUTS])
+                check(host.rth_point_cloud_fill_rolling(w, h, m, axis, rolling[1], fields, sg.ptr(ws), ws_bytes, total, C.byref(cloud), sg.stream,
+                                                        sg.sync), "point_cloud_fill_rolling")
+            elif total:
                 cloud = RtPointCloud(*[sg.ptr(out[k]) if k in out else None for k in _CLOUD_OUTPUTS])
                 check(host.rth_point_cloud_fill(w, h, Pg, m, fields, sg.ptr(ws), ws_bytes, total, C.byref(cloud), sg.stream, sg.sync),
                       "point_cloud_fill")
@@ -1369,6 +1424,58 @@ class Sensor:
         return _point_cloud(libs()[1].rth_sensor_point_cloud_offsets, "Sensor::point_cloud_offsets", self, scene, poses, outputs, min_range,
                             max_range, mask, stream, as_numpy)
     point_cloud.__doc__ = _POINT_CLOUD_DOC % ("this sensor's", "_table")
+
+    ROLLING_OUTPUTS = _GBUFFER_OUTPUTS + ("local",)
+
+    def render_rolling(self, scene, poses, axis="x", slice_pixels=8, outputs=("t", "instance", "triangle"), image=False, stream=None,
+                       as_numpy=False):
+        """Rolling frames (rt_render_gbuffer_rolling, "rolling frames" in include/rt_hip.h): render_gbuffer with a pose per SLICE of
+        slice_pixels columns (axis "x": a spinning lidar's revolution) or rows (axis "y": a rolling shutter) -- slice_pixels a
+        multiple of 8, the last slice may be narrower.  poses: [n, slices, 6], slices = ceil(extent / slice_pixels); see
+        sensors.rolling_poses.  outputs: any of ROLLING_OUTPUTS -- the G-buffer planes, each what Scene.trace_rays gives for
+        rays(pose of the pixel's slice), plus "local" [n, h, w, 3]: the hit in the sensor's frame at the moment its slice was taken
+        (the raw, motion-distorted scan; "location" is the de-skewed truth), local[..., 2] == depth.  n is cut into launches of
+        RT_MAX_BATCH frames; always plain records (no view slot).  Every ValueError is raised before a device call."""
+        outputs = tuple(outputs)
+        if [o for o in outputs if o not in Sensor.ROLLING_OUTPUTS] or len(set(outputs)) != len(outputs) or not (outputs or image):
+            raise ValueError("outputs must be a subset of %s (non-empty unless image=True), nothing twice, got %r" % (Sensor.ROLLING_OUTPUTS, outputs))
+        P, ax, slices = _rolling_args(self, poses, axis, slice_pixels)
+        n, h, w = int(P.shape[0]), self.height, self.width
+        if n * h * w > 2 ** 31 - 1:
+            raise ValueError("at most 2^31 - 1 pixels per call, got %d frames of %d x %d" % (n, w, h))
+        hip, host = libs()
+        kinds = dict(_FIELDS, local=((3,), np.float32))
+        with _staging(not as_numpy, stream) as sg:
+            out = {k: sg.alloc((n, h, w) + kinds[k][0], kinds[k][1]) for k in outputs}
+            img = sg.alloc((n, h, w, 3), np.uint8) if image else None
+            ws_bytes = int(hip.rt_rolling_workspace_bytes(min(n, RT_MAX_BATCH), slices))
+            spaces = []                                                 # (one workspace per launch: each stays untouched until its render has run)
+            for first in range(0, n, RT_MAX_BATCH):
+                m = min(RT_MAX_BATCH, n - first)
+                at = {k: sg.ptr(a) for k, a in out.items()}
+                at = {k: (v.value if isinstance(v, _vp) else int(v)) + first * h * w * math.prod(kinds[k][0]) * 4 for k, v in at.items()}
+                planes = RtGBuffer(*[at.get(k) for k in _GBUFFER_OUTPUTS])
+                ptrs = None
+                if image:
+                    base = sg.ptr(img)
+                    base = base.value if isinstance(base, _vp) else int(base)
+                    ptrs = (_vp * m)(*[base + (first + i) * h * w * 3 for i in range(m)])
+                spaces.append(sg.alloc((ws_bytes,), np.uint8))
+                check(host.rth_sensor_render_rolling(self.h, scene.h, _fp(P[first:first + m]), m, slices, ax, int(slice_pixels), C.byref(planes),
+                                                     at.get("local"), ptrs, w * 3, sg.ptr(spaces[-1]), ws_bytes, sg.stream, sg.sync),
+                      "Sensor::render_rolling")
+            res = {k: sg.result(a) for k, a in out.items()}
+            if image:
+                res["image"] = sg.result(img)
+            return res
+
+    def rolling_point_cloud(self, scene, poses, axis="x", slice_pixels=8, outputs=("local", "range", "pixel"), min_range=0.0,
+                            max_range=math.inf, mask=None, stream=None, as_numpy=False):
+        """point_cloud for rolling frames (rt_point_cloud_offsets_rolling + rt_point_cloud_fill_rolling): poses, axis and slice_pixels
+        as render_rolling takes them, everything else as point_cloud.  `local` is in the sensor's frame at the moment each point's
+        slice was taken -- the raw, motion-distorted scan a driver delivers -- `position` the de-skewed truth in the world."""
+        return _point_cloud(libs()[1].rth_sensor_point_cloud_offsets_rolling, "Sensor::point_cloud_offsets_rolling", self, scene, poses, outputs,
+                            min_range, max_range, mask, stream, as_numpy, rolling=(axis, slice_pixels))
 
     def close(self):
         if getattr(self, "h", None):

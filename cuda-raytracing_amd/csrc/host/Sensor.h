@@ -47,6 +47,19 @@ public:
     // sensor's table.  Writes nothing in the sensor; returns the error code and leaves last_error alone.
     int point_cloud_offsets(void* on_stream, Scene& scene, const std::vector<transforms::lre>& poses, float min_range, float max_range,
                             const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes) const;
+    // Rolling frames (rt_render_gbuffer_rolling in rt_hip.h): a pose per slice of slice_pixels columns (axis 0) or rows (axis 1).
+    // poses: [count][slices] flattened, slices = rolling_slices(axis, slice_pixels); the inverse of each is the host's own invert_lre.
+    // d_local: optional DEVICE plane [count][height][width][3]; d_workspace: rt_rolling_workspace_bytes(count, slices) DEVICE bytes.
+    // Writes nothing in the sensor; returns the error code and leaves last_error alone.
+    int rolling_slices(int axis, int slice_pixels) const;       // 0 for a bad axis or slice_pixels
+    int render_rolling_on(void* on_stream, Scene& scene, const std::vector<transforms::lre>& poses, int count, int axis, int slice_pixels,
+                          const RtGBuffer& out, float* d_local, void* d_workspace, size_t workspace_bytes, uint8_t* const* d_imgs = nullptr,
+                          size_t pitch = 0) const;
+    // Rolling cloud, first step (rt_point_cloud_offsets_rolling in rt_hip.h); the workspace is
+    // rt_point_cloud_rolling_workspace_bytes(width, height, count, fields, slices) bytes.
+    int point_cloud_offsets_rolling(void* on_stream, Scene& scene, const std::vector<transforms::lre>& poses, int count, int axis,
+                                    int slice_pixels, float min_range, float max_range, const uint8_t* d_mask, uint32_t fields,
+                                    int64_t* d_offsets, void* d_workspace, size_t workspace_bytes) const;
 
 private:
     RtRayTable* d_table = nullptr;
@@ -57,3 +70,8 @@ private:
 // `out`, the first `capacity` of them.  Needs no scene.  Asynchronous on `on_stream`; returns the error code.
 int point_cloud_fill(void* on_stream, int width, int height, const std::vector<transforms::lre>& poses, uint32_t fields,
                      const void* d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud& out);
+// Rolling cloud, second step (rt_point_cloud_fill_rolling in rt_hip.h): the points of the workspace a point_cloud_offsets_rolling
+// call left, with the same size, count, axis, slice_pixels and fields.  Needs neither the scene nor the poses: the pose records are
+// in the workspace.  Asynchronous on `on_stream`; returns the error code.
+int point_cloud_fill_rolling(void* on_stream, int width, int height, int count, int axis, int slice_pixels, uint32_t fields,
+                             const void* d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud& out);

@@ -978,6 +978,52 @@ int Sensor::point_cloud_offsets(void* on_stream, Scene& scene, const std::vector
                                         d_workspace, workspace_bytes, on_stream, 0);
 }
 
+int Sensor::rolling_slices(int axis, int slice_pixels) const
+{
+    int32_t n = 0;
+    return rt_rolling_slices(width, height, axis, slice_pixels, &n) == RT_OK ? (int)n : 0;
+}
+
+// [count][slices] poses -> RtRollingPose, the inverse from the host's own invert_lre; false for a wrong count of poses
+static bool rolling_params(const Sensor& s, const std::vector<lre>& poses, int count, int axis, int slice_pixels, std::vector<RtRollingPose>& out)
+{
+    const int slices = s.rolling_slices(axis, slice_pixels);
+    if (slices < 1 || count < 1 || count > RT_MAX_BATCH || poses.size() != (size_t)count * (size_t)slices) return false;
+    out.resize(poses.size());
+    for (size_t i = 0; i < poses.size(); i++) {
+        lre inv = invert_lre(poses[i]);
+        memcpy(out[i].camera_pose, &poses[i], sizeof out[i].camera_pose);
+        memcpy(out[i].inv_camera_pose, &inv, sizeof out[i].inv_camera_pose);
+    }
+    return true;
+}
+
+int Sensor::render_rolling_on(void* on_stream, Scene& scene, const std::vector<lre>& poses, int count, int axis, int slice_pixels,
+                              const RtGBuffer& out, float* d_local, void* d_workspace, size_t workspace_bytes, uint8_t* const* d_imgs,
+                              size_t pitch) const
+{
+    std::vector<RtRollingPose> p;
+    if (!d_table || !scene.d_scene || !rolling_params(*this, poses, count, axis, slice_pixels, p)) return RT_E_INVALID;
+    return rt_render_gbuffer_rolling(scene.d_scene, d_table, p.data(), count, axis, slice_pixels, d_imgs, pitch, &out, d_local, d_workspace,
+                                     workspace_bytes, on_stream, 0);
+}
+
+int Sensor::point_cloud_offsets_rolling(void* on_stream, Scene& scene, const std::vector<lre>& poses, int count, int axis, int slice_pixels,
+                                        float min_range, float max_range, const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets,
+                                        void* d_workspace, size_t workspace_bytes) const
+{
+    std::vector<RtRollingPose> p;
+    if (!d_table || !scene.d_scene || !rolling_params(*this, poses, count, axis, slice_pixels, p)) return RT_E_INVALID;
+    return rt_point_cloud_offsets_rolling(scene.d_scene, d_table, p.data(), count, axis, slice_pixels, min_range, max_range, d_mask, fields,
+                                          d_offsets, d_workspace, workspace_bytes, on_stream, 0);
+}
+
+int point_cloud_fill_rolling(void* on_stream, int width, int height, int count, int axis, int slice_pixels, uint32_t fields,
+                             const void* d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud& out)
+{
+    return rt_point_cloud_fill_rolling(width, height, count, axis, slice_pixels, fields, d_workspace, workspace_bytes, capacity, &out, on_stream, 0);
+}
+
 int Sensor::rays(float* d_origins, float* d_directions) { return last_error = rays_on(stream, pose, d_origins, d_directions); }
 
 int Sensor::render_gbuffer(Scene& scene, const std::vector<lre>& poses, const RtGBuffer& out, uint8_t* const* d_imgs, size_t pitch)

@@ -331,6 +331,47 @@ int rth_point_cloud_fill(int32_t width, int32_t height, const float* poses6, int
     return rc;
 }
 
+// [count][slices][6] -> lre, when `slices` is what the sensor's size, axis and slice_pixels give
+static bool lre_rolling(const RthSensor* n, const float* poses6, int32_t count, int32_t slices, int32_t axis, int32_t slice_pixels,
+                        std::vector<lre>& poses)
+{
+    if (!n || !poses6 || count < 1 || count > RT_MAX_BATCH || slices < 1 || n->sensor.rolling_slices(axis, slice_pixels) != slices) return false;
+    poses.resize((size_t)count * (size_t)slices);
+    for (size_t i = 0; i < poses.size(); i++) poses[i] = LRE(poses6 + 6 * i);
+    return true;
+}
+int rth_sensor_render_rolling(RthSensor* n, RthScene* s, const float* poses6, int32_t count, int32_t slices, int32_t axis, int32_t slice_pixels,
+                              const void* gbuffer, float* d_local, void* const* d_imgs, size_t pitch, void* d_workspace, size_t workspace_bytes,
+                              void* stream, int synchronize)
+{
+    std::vector<lre> poses;
+    if (!s || !gbuffer || !lre_rolling(n, poses6, count, slices, axis, slice_pixels, poses)) return RT_E_INVALID;
+    const int rc = n->sensor.render_rolling_on(stream, s->scene, poses, count, axis, slice_pixels, *(const RtGBuffer*)gbuffer, d_local, d_workspace,
+                                               workspace_bytes, (uint8_t* const*)d_imgs, pitch);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+int rth_sensor_point_cloud_offsets_rolling(RthSensor* n, RthScene* s, const float* poses6, int32_t count, int32_t slices, int32_t axis,
+                                           int32_t slice_pixels, float min_range, float max_range, const uint8_t* d_mask, uint32_t fields,
+                                           int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    std::vector<lre> poses;
+    if (!s || !lre_rolling(n, poses6, count, slices, axis, slice_pixels, poses)) return RT_E_INVALID;
+    const int rc = n->sensor.point_cloud_offsets_rolling(stream, s->scene, poses, count, axis, slice_pixels, min_range, max_range, d_mask, fields,
+                                                         d_offsets, d_workspace, workspace_bytes);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+int rth_point_cloud_fill_rolling(int32_t width, int32_t height, int32_t count, int32_t axis, int32_t slice_pixels, uint32_t fields,
+                                 const void* d_workspace, size_t workspace_bytes, int64_t capacity, const void* cloud, void* stream, int synchronize)
+{
+    if (!cloud) return RT_E_INVALID;
+    const int rc = point_cloud_fill_rolling(stream, width, height, count, axis, slice_pixels, fields, d_workspace, workspace_bytes, capacity,
+                                            *(const RtPointCloud*)cloud);
+    if (rc == RT_OK && synchronize) return rt_stream_synchronize(stream);
+    return rc;
+}
+
 int rth_camera_render_scene_stripes_batch(RthCamera* c, RthScene* s, const float* poses6, void* const* d_locals, size_t local_pitch,
                                           int32_t count, int32_t stripe_rows, int32_t rank, int32_t num_ranks, int synchronize)
 {

@@ -1280,13 +1280,37 @@ struct GBufParams {
 static_assert(sizeof(RenderParams) + sizeof(GBufParams) <= 4096, "kernel arguments must fit in 4 KB");
 __device__ __forceinline__ V3 hit_normal(const RenderParams& p, const Hit& hit);
 
-template <bool DEBUG, bool PROF, bool COUNT = false, bool SPILL = true, bool VIEW = false, bool STATS = false, bool TABLE = false, bool GBUF = false>
+// ROLL (rt_render_gbuffer_rolling, rolling_gbuffer_kernel below): the pose of one slice of one rolling frame, packed by the host -- the
+// quaternions are the host's euler2quat, so their bits are those of rt_ray_table_rays and GBufParams::q_pose.  One record per frame
+// and slice, [frame][slice], in the caller's workspace; a wave reads its own with scalar loads (the address space says the words do
+// not change while the kernel runs: the records were written earlier in the stream's order).
+struct RollRecord {
+    float origin[3];            // camera_pose xyz of the slice, as FrameParams::origin
+    uint32_t pad;
+    Q4 q_cam;                   // euler2quat(inv_camera_pose ypr), as FrameParams::q_cam
+    Q4 q_pose;                  // euler2quat(camera_pose ypr), as GBufParams::q_pose
+};
+static_assert(sizeof(RollRecord) == 48, "three scalar fetches of four words");
+typedef const __attribute__((address_space(4))) RollRecord* RollRecordPtr;
+struct RollParams {
+    const RollRecord* records;  // [num_frames][slices]
+    float* local;               // optional plane [frame][height][width][3]: apply_lre(camera_pose of the pixel's slice, location)
+    int32_t slices;
+    int32_t axis;               // 0: the column x selects the slice, 1: the row y
+    int32_t slice_tiles;        // slice_pixels / 8: a slice is whole tiles
+};
+static_assert(sizeof(RenderParams) + sizeof(GBufParams) + sizeof(RollParams) <= 4096, "kernel arguments must fit in 4 KB");
+
+template <bool DEBUG, bool PROF, bool COUNT = false, bool SPILL = true, bool VIEW = false, bool STATS = false, bool TABLE = false, bool GBUF = false, bool ROLL = false>
 __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameParams& f, int x0, int y0, lds_int* lds_base, lds_int*& lds_column,
-                                             int* iters = nullptr, uint32_t view_off = 0, const GBufParams* g = nullptr)
+                                             int* iters = nullptr, uint32_t view_off = 0, const GBufParams* g = nullptr,
+                                             const Q4* roll_q_pose = nullptr, float* roll_local = nullptr)
 {
     // (a caller's table -- RtRayTable, rt_render_gbuffer_table -- also serves a launch without view records: the G-buffer form only)
     static_assert(!TABLE || ((VIEW || GBUF) && !COUNT && !DEBUG && !PROF && kPrimBlock == 64), "direction table: the batched view kernels and the G-buffer kernels, one 8x8 tile per workgroup");
     static_assert(!GBUF || (!COUNT && !DEBUG && !PROF && !STATS && kPrimBlock == 64), "G-buffer: the un-ordered production kernels");
+    // (f is then the kernel's own copy: origin and q_cam from the slice's record, img / rank / local_rows from p.frames[frame])
+    static_assert(!ROLL || (GBUF && TABLE && !VIEW), "rolling frames: the caller's table over plain records");
     V3 cdir;
     if constexpr (TABLE) {
         const float* t = p.dir_table + ((size_t)(blockIdx.y * (unsigned)p.tiles_x + blockIdx.x) * (3 * 64) + (size_t)(lds_column - lds_base));
@@ -1350,13 +1374,16 @@ __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameP
         if (g->t) g->t[o] = hit.min;
         if (g->instance) g->instance[o] = hit.instance;
         if (g->triangle) g->triangle[o] = got ? p.tri_id[hit.slot] : -1;
-        if (g->location || g->depth) {
+        bool want_local = false;
+        if constexpr (ROLL) want_local = roll_local != nullptr;
+        if (g->location || g->depth || want_local) {
             // The accepted candidate once more, as triangle_test<.., EX> evaluates it for query_kernel (raycast.cu:33-51, TrianglePrimitive.hpp:62-79,
             // raycast.cu:98-104): the pixel's ray from the same table entry or the same intrinsics, to_mesh_space of the winning
             // instance, the record of the winning slot, the transform always applied.  Same operations on the same inputs: the
             // bits of rt_trace_rays' location.
             V3 loc = v3(0.0f, 0.0f, 0.0f);
             float depth = FLT_MAX;
+            V3 local = v3(0.0f, 0.0f, 0.0f);                    // (ROLL only)
             if (got) {
                 V3 cd;
                 if constexpr (TABLE) {
@@ -1376,10 +1403,16 @@ __device__ __forceinline__ void render_pixel(const RenderParams& p, const FrameP
                 loc = v3(pt.x * in.scale[0], pt.y * in.scale[1], pt.z * in.scale[2]);
                 loc = apply_quat(in.q_inv_pose, v3(loc.x - in.inv_pose_xyz[0], loc.y - in.inv_pose_xyz[1], loc.z - in.inv_pose_xyz[2]));
                 // depth (rt_hip.h, G-buffer rule 2): apply_lre(camera_pose, location).z
+                if constexpr (ROLL) {
+                    // rolling frames rule 2: all three components of apply_lre(camera_pose of the slice, location); depth is its z
+                    local = apply_quat(*roll_q_pose, v3(loc.x - f.origin[0], loc.y - f.origin[1], loc.z - f.origin[2]));
+                    depth = local.z;
+                } else
                 depth = apply_quat(g->q_pose[blockIdx.z], v3(loc.x - f.origin[0], loc.y - f.origin[1], loc.z - f.origin[2])).z;
             }
             if (g->location) { g->location[o * 3] = loc.x; g->location[o * 3 + 1] = loc.y; g->location[o * 3 + 2] = loc.z; }
             if (g->depth) g->depth[o] = depth;
+            if constexpr (ROLL) if (want_local) { roll_local[o * 3] = local.x; roll_local[o * 3 + 1] = local.y; roll_local[o * 3 + 2] = local.z; }
         }
         if (g->normal) {
             const V3 n = got ? hit_normal(p, hit) : v3(0.0f, 0.0f, 0.0f);
@@ -1502,6 +1535,33 @@ __global__ __launch_bounds__(kPrimBlock, 8) void gbuffer_kernel(const RenderPara
                                                                            VIEW ? p.view_base + (uint32_t)frame * p.view_frame_stride : 0u, &g);
 }
 
+// rt_render_gbuffer_rolling (include/rt_hip.h "rolling frames"): gbuffer_kernel<SPILL, false, true> -- the
+// caller's table over plain records, the same grid, LDS block and launch bounds -- with a pose per slice of whole tiles.  A workgroup
+// is one wave and one tile, so the wave still has ONE origin and ONE rotation: its slice is an expression of blockIdx, hence provably
+// wave-uniform, and the slice's record arrives by scalar loads into the kernel's own copy of the frame's parameters.  The traversal
+// is the timed one, untouched; img, rank and local_rows are the frame's.  The slice index is bounded by `slices` before the record is
+// read.
+template <bool SPILL>
+__global__ __launch_bounds__(kPrimBlock, 8) void rolling_gbuffer_kernel(const RenderParams p, const GBufParams g, const RollParams r)
+{
+    extern __shared__ int lds_stack[];                          // [lds_block_rows(stack_depth)][kPrimBlock]
+    const int frame = (int)blockIdx.z, x0 = (int)blockIdx.x * kPrimTile, y0 = (int)blockIdx.y * kPrimTile;
+    int slice = (int)(r.axis ? blockIdx.y : blockIdx.x) / r.slice_tiles;
+    slice = slice < r.slices ? slice : r.slices - 1;
+    const RollRecordPtr rec = (RollRecordPtr)(uintptr_t)(r.records + ((size_t)frame * (size_t)r.slices + (size_t)slice));
+    FrameParams f;                                              // (kinv and D: not read under a table)
+    f.origin[0] = rec->origin[0]; f.origin[1] = rec->origin[1]; f.origin[2] = rec->origin[2];
+    f.q_cam.x = rec->q_cam.x; f.q_cam.y = rec->q_cam.y; f.q_cam.z = rec->q_cam.z; f.q_cam.w = rec->q_cam.w;
+    f.img = p.frames[frame].img; f.rank = p.frames[frame].rank; f.local_rows = p.frames[frame].local_rows;
+    Q4 q_pose;
+    q_pose.x = rec->q_pose.x; q_pose.y = rec->q_pose.y; q_pose.z = rec->q_pose.z; q_pose.w = rec->q_pose.w;
+    lds_int* column = (lds_int*)lds_stack + threadIdx.x;
+    int x, ly, y;
+    pixel_of(p, f, (int)threadIdx.x, x0, y0, x, ly, y);
+    if (x < p.width && ly < f.local_rows)
+        render_pixel<false, false, false, SPILL, false, false, true, true, true>(p, f, x0, y0, (lds_int*)lds_stack, column, nullptr, 0u, &g, &q_pose, r.local);
+}
+
 // Point clouds (rt_point_cloud_offsets / rt_point_cloud_fill, include/rt_hip.h "point clouds"): the kept pixels
 // of the staged G-buffer planes, packed in (frame, y, x) order.  A chunk is 64 consecutive pixels of ONE frame's row-major order -- a
 // frame has chunks_per_frame = ceil(px / 64) of them, the last one partial -- and one wave works on one chunk: its 64-bit ballot of the
@@ -1560,6 +1620,13 @@ struct CloudFillParams {
 static_assert(sizeof(CloudFillParams) <= 4096, "kernel arguments must fit in 4 KB");
 // Everything read from the workspace is data: the pixel index is bounded by px before any plane is read and the slot -- compared as an
 // unsigned number, so that a negative offset of a stale workspace is large -- by capacity before anything is written.
+// ROLL (rt_point_cloud_fill_rolling): `local` takes the pose of the point's slice from the records rt_point_cloud_offsets_rolling left
+// in the workspace -- data like the rest: the slice index is bounded by `slices` before a record is read.  q_pose and origin of `c`
+// are then not read.
+struct CloudRollParams {
+    const RollRecord* records;  // [count][slices]
+    int32_t width, slices, axis, slice_pixels;
+};
 __global__ __launch_bounds__(kCloudBlock) void cloud_fill_kernel(const CloudFillParams c)
 {
     const int lane = (int)threadIdx.x & 63;
@@ -1585,6 +1652,42 @@ __global__ __launch_bounds__(kCloudBlock) void cloud_fill_kernel(const CloudFill
         if (c.local) {
             // rt_hip.h, point clouds rule 5: render_pixel's depth expression, all three components
             const V3 l = apply_quat(c.q_pose[frame], v3(loc.x - c.origin[frame][0], loc.y - c.origin[frame][1], loc.z - c.origin[frame][2]));
+            c.local[j * 3] = l.x; c.local[j * 3 + 1] = l.y; c.local[j * 3 + 2] = l.z;
+        }
+    }
+    if (c.out_normal) { c.out_normal[j * 3] = c.normal[o * 3]; c.out_normal[j * 3 + 1] = c.normal[o * 3 + 1]; c.out_normal[j * 3 + 2] = c.normal[o * 3 + 2]; }
+    if (c.out_uv) { c.out_uv[j * 2] = c.uv[o * 2]; c.out_uv[j * 2 + 1] = c.uv[o * 2 + 1]; }
+}
+// cloud_fill_kernel with the pose of `local` from the record of the pixel's slice: a sibling, so that the kernel above stays what it was
+__global__ __launch_bounds__(kCloudBlock) void cloud_fill_rolling_kernel(const CloudFillParams c, const CloudRollParams r)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int64_t chunk = (int64_t)blockIdx.x * (kCloudBlock / kCloudChunk) + ((int)threadIdx.x >> 6);
+    if (chunk >= (int64_t)c.nchunks) return;                    // (wave-uniform)
+    const int32_t frame = (int32_t)chunk / c.chunks_per_frame;
+    const int64_t at = (int64_t)((int32_t)chunk - frame * c.chunks_per_frame) * kCloudChunk + lane;
+    const unsigned long long b = c.keep[chunk];                 // the count kernel's ballot
+    if (at >= c.px || !((b >> lane) & 1ull)) return;
+    // kept lanes below this one: v_mbcnt_lo / v_mbcnt_hi of the ballot
+    const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    const unsigned long long slot = (unsigned long long)c.chunk_offsets[chunk] + below;
+    if (slot >= (unsigned long long)c.capacity) return;
+    const size_t o = (size_t)frame * (size_t)c.px + (size_t)at, j = (size_t)slot;
+    if (c.range) c.range[j] = c.t[o];
+    if (c.pixel) c.pixel[j] = (int32_t)at;
+    if (c.frame) c.frame[j] = frame;
+    if (c.out_instance) c.out_instance[j] = c.instance[o];
+    if (c.out_triangle) c.out_triangle[j] = c.triangle[o];
+    if (c.position || c.local) {
+        const V3 loc = v3(c.location[o * 3], c.location[o * 3 + 1], c.location[o * 3 + 2]);
+        if (c.position) { c.position[j * 3] = loc.x; c.position[j * 3 + 1] = loc.y; c.position[j * 3 + 2] = loc.z; }
+        if (c.local) {
+            // rule 5 with the pose of the pixel's slice
+            const int32_t px_y = (int32_t)(at / (int64_t)r.width), px_x = (int32_t)(at - (int64_t)px_y * (int64_t)r.width);
+            int32_t slice = (r.axis ? px_y : px_x) / r.slice_pixels;
+            slice = slice < r.slices ? slice : r.slices - 1;
+            const RollRecord& rec = r.records[(size_t)frame * (size_t)r.slices + (size_t)slice];
+            const V3 l = apply_quat(rec.q_pose, v3(loc.x - rec.origin[0], loc.y - rec.origin[1], loc.z - rec.origin[2]));
             c.local[j * 3] = l.x; c.local[j * 3 + 1] = l.y; c.local[j * 3 + 2] = l.z;
         }
     }
@@ -5601,6 +5704,24 @@ int launch_gbuffer(RtScene* scene, RenderParams& p, const GBufParams& g, hipStre
     return e == hipSuccess ? RT_OK : (int)e;
 }
 
+// rt_render_gbuffer_rolling's launch: launch_gbuffer's grid, tile limits and stack form, always over plain records and the caller's
+// table -- no view_prepare call: the launch takes no view slot, grows no pool and is counted by neither statistic.
+int launch_gbuffer_rolling(RenderParams& p, const GBufParams& g, const RollParams& r, hipStream_t stream, const float* caller_table)
+{
+    if (p.width <= 0 || p.local_rows <= 0 || !caller_table) return RT_E_INVALID;
+    p.tiles_x = (p.width + kPrimTile - 1) / kPrimTile;
+    p.tiles_y = (p.local_rows + kPrimTile - 1) / kPrimTile;
+    if (p.tiles_y > 65535) return RT_E_INVALID;                 // (a grid's y ends at 65 535, as in launch())
+    const bool shallow = lds_stack_suffices(p);
+    const size_t lds = (size_t)(shallow ? lds_rows(p.stack_depth) : lds_block_rows<false, false, true>(p.stack_depth)) * kPrimBlock * sizeof(int);
+    const dim3 grid((unsigned)p.tiles_x, (unsigned)p.tiles_y, (unsigned)p.num_frames), block(kPrimBlock);
+    p.dir_table = caller_table;
+    if (shallow) hipLaunchKernelGGL((rolling_gbuffer_kernel<false>), grid, block, lds, stream, p, g, r);
+    else hipLaunchKernelGGL((rolling_gbuffer_kernel<true>), grid, block, lds, stream, p, g, r);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RT_OK : (int)e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -6316,6 +6437,95 @@ int rt_render_gbuffer_table(RtScene* s, const RtRayTable* table, const RtCameraP
 {
     if (!table) return RT_E_INVALID;
     return render_gbuffer(s, table, poses, count, d_imgs, pitch, out, stream, synchronize);
+}
+
+// ---- rolling frames (include/rt_hip.h "rolling frames") --------------------------------------------------
+extern "C++" {
+namespace {
+bool rolling_axis_ok(int32_t axis, int32_t slice_pixels) { return (axis == 0 || axis == 1) && slice_pixels >= 8 && slice_pixels % 8 == 0; }
+bool rolling_shape(int32_t width, int32_t height, int32_t axis, int32_t slice_pixels, int32_t& slices)
+{
+    if (width < 1 || height < 1 || !rolling_axis_ok(axis, slice_pixels)) return false;
+    const int32_t extent = axis ? height : width;
+    slices = (int32_t)(((int64_t)extent + slice_pixels - 1) / slice_pixels);
+    return true;
+}
+size_t rolling_record_bytes(int32_t count, int32_t slices)
+{
+    if (count < 1 || count > kMaxBatch || slices < 1) return 0;
+    return ((size_t)count * (size_t)slices * sizeof(RollRecord) + 255) / 256 * 256;     // (whole 256-byte blocks, as the cloud workspace's parts)
+}
+// the records of count x slices poses: the host's quaternions, so that their bits are rt_ray_table_rays' and GBufParams::q_pose's
+void rolling_pack(const RtRollingPose* poses, size_t n, std::vector<RollRecord>& rec)
+{
+    rec.resize(n);
+    for (size_t k = 0; k < n; k++) {
+        const RtRollingPose& ps = poses[k];
+        RollRecord& o = rec[k];
+        for (int a = 0; a < 3; a++) o.origin[a] = ps.camera_pose[a];
+        o.pad = 0;
+        o.q_cam = euler2quat(v3(ps.inv_camera_pose[3], ps.inv_camera_pose[4], ps.inv_camera_pose[5]));
+        o.q_pose = euler2quat(v3(ps.camera_pose[3], ps.camera_pose[4], ps.camera_pose[5]));
+    }
+}
+// The rolling render of `count` frames into the planes of g (and `d_local`), the records into `d_records` first, on `stream`.  Every
+// argument has been judged.  The copy reads pageable host memory: it returns when the records have left `rec` (it may wait for work
+// issued EARLIER on the stream, never for the launch that follows it).
+int rolling_render(RtScene* s, const RtRayTable* table, const RtRollingPose* poses, int32_t count, int32_t slices, int32_t axis,
+                   int32_t slice_pixels, uint8_t* const* d_imgs, size_t pitch, GBufParams& g, float* d_local, void* d_records, hipStream_t st)
+{
+    std::vector<RollRecord> rec;
+    rolling_pack(poses, (size_t)count * (size_t)slices, rec);
+    RT_HIP(hipMemcpyAsync(d_records, rec.data(), rec.size() * sizeof(RollRecord), hipMemcpyHostToDevice, st));
+    RtCameraParams cams[kMaxBatch];
+    memset(cams, 0, sizeof cams);
+    for (int i = 0; i < count; i++) {                           // (the size and, for fill_params, the first slice's pose: the kernel reads the records)
+        cams[i].width = table->width; cams[i].height = table->height;
+        memcpy(cams[i].camera_pose, poses[(size_t)i * slices].camera_pose, sizeof cams[i].camera_pose);
+        memcpy(cams[i].inv_camera_pose, poses[(size_t)i * slices].inv_camera_pose, sizeof cams[i].inv_camera_pose);
+    }
+    RollParams r;
+    r.records = (const RollRecord*)d_records; r.local = d_local; r.slices = slices; r.axis = axis; r.slice_tiles = slice_pixels / kPrimTile;
+    RT_SCENE_CALL(s);                                           // (held for the launch only)
+    RenderParams p;
+    int rc = fill_params(p, s, cams, d_imgs, count, pitch, d_imgs == nullptr);
+    if (rc) return rc;
+    return launch_gbuffer_rolling(p, g, r, st, table->d_table);
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_rolling_slices(int32_t width, int32_t height, int32_t axis, int32_t slice_pixels, int32_t* slices)
+{
+    int32_t n = 0;
+    if (!slices || !rolling_shape(width, height, axis, slice_pixels, n)) return RT_E_INVALID;
+    *slices = n;
+    return RT_OK;
+}
+
+size_t rt_rolling_workspace_bytes(int32_t count, int32_t slices) { return rolling_record_bytes(count, slices); }
+
+int rt_render_gbuffer_rolling(RtScene* s, const RtRayTable* table, const RtRollingPose* poses, int32_t count, int32_t axis, int32_t slice_pixels,
+                              uint8_t* const* d_imgs, size_t pitch, const RtGBuffer* out, float* d_local, void* d_workspace,
+                              size_t workspace_bytes, void* stream, int synchronize)
+{
+    // (every argument is judged before any device call)
+    int32_t slices = 0;
+    if (!s || !table || !poses || !out || !d_workspace || count < 1 || count > kMaxBatch || !rolling_axis_ok(axis, slice_pixels)) return RT_E_INVALID;
+    const bool planes = out->t || out->depth || out->instance || out->triangle || out->location || out->normal || out->uv || d_local;
+    if (!planes && !d_imgs) return RT_E_INVALID;
+    if (d_imgs) for (int i = 0; i < count; i++) if (!d_imgs[i]) return RT_E_INVALID;
+    // (the table is looked at last: whatever can be judged without it has been)
+    if (!rolling_shape(table->width, table->height, axis, slice_pixels, slices) || workspace_bytes < rolling_record_bytes(count, slices)) return RT_E_INVALID;
+    if (d_imgs && pitch < (size_t)table->width * 3) return RT_E_INVALID;
+    GBufParams g;
+    memset(&g, 0, sizeof g);                                    // (q_pose: not read, the records carry it)
+    g.t = out->t; g.depth = out->depth; g.instance = out->instance; g.triangle = out->triangle;
+    g.location = out->location; g.normal = out->normal; g.uv = out->uv;
+    const int rc = rolling_render(s, table, poses, count, slices, axis, slice_pixels, d_imgs, pitch, g, d_local, d_workspace, (hipStream_t)stream);
+    if (rc) return rc;
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
 }
 
 int rt_render_debug(RtScene* s, const RtCameraParams* cam, uint8_t* d_img, size_t pitch,
@@ -7423,6 +7633,24 @@ bool cloud_frames_ok(const RtCameraParams* cams, int32_t count)
     for (int i = 1; i < count; i++) if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) return false;
     return true;
 }
+// the part of *_offsets that reads the workspace only: the count kernel over the staged t and instance planes, the scan, the frame offsets
+int cloud_count_and_scan(const CloudLayout& L, void* d_workspace, int32_t count, float min_range, float max_range, const uint8_t* d_mask,
+                         int64_t* d_offsets, hipStream_t st)
+{
+    char* const ws = (char*)d_workspace;
+    CloudCountParams c;
+    c.t = (const float*)(ws + L.t); c.instance = (const int32_t*)(ws + L.instance); c.mask = d_mask;
+    c.px = L.px; c.chunks_per_frame = L.chunks_per_frame; c.nchunks = L.nchunks;
+    c.min_range = min_range; c.max_range = max_range;
+    c.counts = (int32_t*)ws; c.keep = (unsigned long long*)(ws + L.keep);
+    const unsigned grid = (unsigned)(((int64_t)L.nchunks + kCloudBlock / kCloudChunk - 1) / (kCloudBlock / kCloudChunk));
+    hipLaunchKernelGGL(cloud_count_kernel, dim3(grid), dim3(kCloudBlock), 0, st, c);
+    scan_offsets(d_workspace, L.nchunks, (int64_t*)(ws + L.chunk_offsets), L.blocks, L.levels, st);
+    hipLaunchKernelGGL(cloud_frame_offsets_kernel, dim3(1), dim3(64), 0, st, (const int64_t*)(ws + L.chunk_offsets), L.chunks_per_frame, count,
+                       d_offsets);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
 int point_cloud_offsets(RtScene* s, const RtRayTable* table, const RtCameraParams* cams, int32_t count, float min_range, float max_range,
                         const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream,
                         int synchronize)
@@ -7450,19 +7678,66 @@ int point_cloud_offsets(RtScene* s, const RtRayTable* table, const RtCameraParam
         if ((rc = launch_gbuffer(s, p, g, st, table ? table->d_table : nullptr))) return rc;
     }
     // (the scene is no longer needed: the rest reads the workspace only)
-    CloudCountParams c;
-    c.t = (const float*)(ws + L.t); c.instance = (const int32_t*)(ws + L.instance); c.mask = d_mask;
-    c.px = L.px; c.chunks_per_frame = L.chunks_per_frame; c.nchunks = L.nchunks;
-    c.min_range = min_range; c.max_range = max_range;
-    c.counts = (int32_t*)ws; c.keep = (unsigned long long*)(ws + L.keep);
-    const unsigned grid = (unsigned)(((int64_t)L.nchunks + kCloudBlock / kCloudChunk - 1) / (kCloudBlock / kCloudChunk));
-    hipLaunchKernelGGL(cloud_count_kernel, dim3(grid), dim3(kCloudBlock), 0, st, c);
-    scan_offsets(d_workspace, L.nchunks, (int64_t*)(ws + L.chunk_offsets), L.blocks, L.levels, st);
-    hipLaunchKernelGGL(cloud_frame_offsets_kernel, dim3(1), dim3(64), 0, st, (const int64_t*)(ws + L.chunk_offsets), L.chunks_per_frame, count,
-                       d_offsets);
-    RT_HIP(hipGetLastError());
+    if (int rc = cloud_count_and_scan(L, d_workspace, count, min_range, max_range, d_mask, d_offsets, st)) return rc;
     RT_WAIT_IF(synchronize, stream);
     return RT_OK;
+}
+// the staging planes g renders for `fields` into a workspace of layout L
+void cloud_staging(const CloudLayout& L, char* ws, GBufParams& g)
+{
+    memset(&g, 0, sizeof g);
+    g.t = (float*)(ws + L.t); g.instance = (int32_t*)(ws + L.instance);
+    if (L.triangle) g.triangle = (int32_t*)(ws + L.triangle);
+    if (L.location) g.location = (float*)(ws + L.location);
+    if (L.normal) g.normal = (float*)(ws + L.normal);
+    if (L.uv) g.uv = (float*)(ws + L.uv);
+}
+// rt_point_cloud_offsets_rolling: the staging planes by the rolling launch, the pose records behind the static layout (L.bytes is a
+// multiple of 256), then the count, the scan and the frame offsets as they are
+int point_cloud_offsets_rolling(RtScene* s, const RtRayTable* table, const RtRollingPose* poses, int32_t count, int32_t axis, int32_t slice_pixels,
+                                float min_range, float max_range, const uint8_t* d_mask, uint32_t fields, int64_t* d_offsets, void* d_workspace,
+                                size_t workspace_bytes, void* stream, int synchronize)
+{
+    int32_t slices = 0;
+    if (!s || !table || !poses || !d_offsets || !d_workspace || count < 1 || count > kMaxBatch || !rolling_axis_ok(axis, slice_pixels)) return RT_E_INVALID;
+    if (!(min_range <= max_range) || fields == 0 || (fields & ~RT_CLOUD_ALL)) return RT_E_INVALID;     // (a NaN bound fails the comparison)
+    CloudLayout L;                                              // (the table is looked at last: whatever can be judged without it has been)
+    if (!rolling_shape(table->width, table->height, axis, slice_pixels, slices) || !cloud_layout(table->width, table->height, count, fields, L) ||
+        workspace_bytes < L.bytes + rolling_record_bytes(count, slices)) return RT_E_INVALID;
+    char* const ws = (char*)d_workspace;
+    const hipStream_t st = (hipStream_t)stream;
+    GBufParams g;
+    cloud_staging(L, ws, g);
+    int rc = rolling_render(s, table, poses, count, slices, axis, slice_pixels, nullptr, 0, g, nullptr, ws + L.bytes, st);
+    if (rc) return rc;
+    if ((rc = cloud_count_and_scan(L, d_workspace, count, min_range, max_range, d_mask, d_offsets, st))) return rc;
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+// what both fills ask of `out`: no pointer whose plane was not staged, something wanted
+bool cloud_outputs_ok(const RtPointCloud* out, uint32_t fields)
+{
+    const void* const wanted[9] = { out->range, out->pixel, out->frame, out->instance, out->triangle, out->position, out->local, out->normal, out->uv };
+    bool any = false;
+    for (int k = 0; k < 9; k++) {
+        if (wanted[k] && !(fields & (1u << k))) return false;   // (its plane was not staged)
+        any = any || wanted[k];
+    }
+    return any;
+}
+// the fill's parameters but the poses
+void cloud_fill_params(const CloudLayout& L, const char* ws, int64_t capacity, const RtPointCloud* out, CloudFillParams& c)
+{
+    memset(&c, 0, sizeof c);
+    c.chunk_offsets = (const int64_t*)(ws + L.chunk_offsets); c.keep = (const unsigned long long*)(ws + L.keep);
+    c.t = (const float*)(ws + L.t); c.instance = (const int32_t*)(ws + L.instance);
+    if (L.triangle) c.triangle = (const int32_t*)(ws + L.triangle);
+    if (L.location) c.location = (const float*)(ws + L.location);
+    if (L.normal) c.normal = (const float*)(ws + L.normal);
+    if (L.uv) c.uv = (const float*)(ws + L.uv);
+    c.px = L.px; c.chunks_per_frame = L.chunks_per_frame; c.nchunks = L.nchunks; c.capacity = capacity;
+    c.range = out->range; c.pixel = out->pixel; c.frame = out->frame; c.out_instance = out->instance; c.out_triangle = out->triangle;
+    c.position = out->position; c.local = out->local; c.out_normal = out->normal; c.out_uv = out->uv;
 }
 }  // namespace
 }  // extern "C++"
@@ -7495,32 +7770,54 @@ int rt_point_cloud_fill(const RtCameraParams* cams, int32_t count, uint32_t fiel
     if (!cloud_frames_ok(cams, count) || !d_workspace || !out || capacity < 0) return RT_E_INVALID;
     CloudLayout L;
     if (!cloud_layout(cams[0].width, cams[0].height, count, fields, L) || workspace_bytes < L.bytes) return RT_E_INVALID;
-    const void* const wanted[9] = { out->range, out->pixel, out->frame, out->instance, out->triangle, out->position, out->local, out->normal, out->uv };
-    bool any = false;
-    for (int k = 0; k < 9; k++) {
-        if (wanted[k] && !(fields & (1u << k))) return RT_E_INVALID;    // (its plane was not staged)
-        any = any || wanted[k];
-    }
-    if (!any) return RT_E_INVALID;
+    if (!cloud_outputs_ok(out, fields)) return RT_E_INVALID;
     if (capacity > 0) {
-        const char* const ws = (const char*)d_workspace;
         CloudFillParams c;
-        memset(&c, 0, sizeof c);
-        c.chunk_offsets = (const int64_t*)(ws + L.chunk_offsets); c.keep = (const unsigned long long*)(ws + L.keep);
-        c.t = (const float*)(ws + L.t); c.instance = (const int32_t*)(ws + L.instance);
-        if (L.triangle) c.triangle = (const int32_t*)(ws + L.triangle);
-        if (L.location) c.location = (const float*)(ws + L.location);
-        if (L.normal) c.normal = (const float*)(ws + L.normal);
-        if (L.uv) c.uv = (const float*)(ws + L.uv);
-        c.px = L.px; c.chunks_per_frame = L.chunks_per_frame; c.nchunks = L.nchunks; c.capacity = capacity;
-        c.range = out->range; c.pixel = out->pixel; c.frame = out->frame; c.out_instance = out->instance; c.out_triangle = out->triangle;
-        c.position = out->position; c.local = out->local; c.out_normal = out->normal; c.out_uv = out->uv;
+        cloud_fill_params(L, (const char*)d_workspace, capacity, out, c);
         for (int i = 0; i < count; i++) {
             c.q_pose[i] = euler2quat(v3(cams[i].camera_pose[3], cams[i].camera_pose[4], cams[i].camera_pose[5]));
             for (int a = 0; a < 3; a++) c.origin[i][a] = cams[i].camera_pose[a];
         }
         const unsigned grid = (unsigned)(((int64_t)L.nchunks + kCloudBlock / kCloudChunk - 1) / (kCloudBlock / kCloudChunk));
         hipLaunchKernelGGL(cloud_fill_kernel, dim3(grid), dim3(kCloudBlock), 0, (hipStream_t)stream, c);
+        RT_HIP(hipGetLastError());
+    }
+    RT_WAIT_IF(synchronize, stream);
+    return RT_OK;
+}
+
+size_t rt_point_cloud_rolling_workspace_bytes(int32_t width, int32_t height, int32_t count, uint32_t fields, int32_t slices)
+{
+    CloudLayout L;
+    const size_t rec = rolling_record_bytes(count, slices);
+    return rec && cloud_layout(width, height, count, fields, L) ? L.bytes + rec : 0;
+}
+
+int rt_point_cloud_offsets_rolling(RtScene* s, const RtRayTable* table, const RtRollingPose* poses, int32_t count, int32_t axis,
+                                   int32_t slice_pixels, float min_range, float max_range, const uint8_t* d_mask, uint32_t fields,
+                                   int64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* stream, int synchronize)
+{
+    return point_cloud_offsets_rolling(s, table, poses, count, axis, slice_pixels, min_range, max_range, d_mask, fields, d_offsets, d_workspace,
+                                       workspace_bytes, stream, synchronize);
+}
+
+int rt_point_cloud_fill_rolling(int32_t width, int32_t height, int32_t count, int32_t axis, int32_t slice_pixels, uint32_t fields,
+                                const void* d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud* out, void* stream,
+                                int synchronize)
+{
+    int32_t slices = 0;
+    if (!d_workspace || !out || capacity < 0 || !rolling_shape(width, height, axis, slice_pixels, slices)) return RT_E_INVALID;
+    CloudLayout L;
+    if (!cloud_layout(width, height, count, fields, L) || workspace_bytes < L.bytes + rolling_record_bytes(count, slices)) return RT_E_INVALID;
+    if (!cloud_outputs_ok(out, fields)) return RT_E_INVALID;
+    if (capacity > 0) {
+        CloudFillParams c;
+        cloud_fill_params(L, (const char*)d_workspace, capacity, out, c);
+        CloudRollParams r;
+        r.records = (const RollRecord*)((const char*)d_workspace + L.bytes);
+        r.width = width; r.slices = slices; r.axis = axis; r.slice_pixels = slice_pixels;
+        const unsigned grid = (unsigned)(((int64_t)L.nchunks + kCloudBlock / kCloudChunk - 1) / (kCloudBlock / kCloudChunk));
+        hipLaunchKernelGGL(cloud_fill_rolling_kernel, dim3(grid), dim3(kCloudBlock), 0, (hipStream_t)stream, c, r);
         RT_HIP(hipGetLastError());
     }
     RT_WAIT_IF(synchronize, stream);

@@ -62,6 +62,18 @@ def fisheye_equidistant(width, height, fov, centre=None, with_mask=False):
     return _finish(d, r <= R, with_mask)
 
 
+def rolling_poses(start, end, slices):
+    """The poses of one rolling frame (Sensor.render_rolling): float32 [slices, 6], slice s at start + (end - start) * s / slices of the
+    six numbers (x, y, z, yaw, pitch, roll) -- slice 0 fires at `start`, the slice after the last would fire at `end`, which is the
+    next frame's start.  Computed in float64 and rounded to float32 once.  A plain interpolation of the six numbers: adequate for the
+    small rotations of one sweep or one exposure, NOT a slerp -- for large rotations interpolate the rotations yourself."""
+    a, b = np.asarray(start, np.float64), np.asarray(end, np.float64)
+    if a.shape != (6,) or b.shape != (6,) or int(slices) != slices or slices < 1:
+        raise ValueError("start and end must be (x, y, z, yaw, pitch, roll) and slices a positive integer, got %s, %s, %r" % (a.shape, b.shape, slices))
+    s = np.arange(int(slices), dtype=np.float64)[:, None]
+    return np.ascontiguousarray(a[None] + (b - a)[None] * s / float(slices), np.float32)
+
+
 BROWN_CONRADY_ITERATIONS = 20
 
 

@@ -455,6 +455,66 @@ int rt_point_cloud_offsets_table(RtScene *scene, const RtRayTable *table, const 
                                  size_t workspace_bytes, void *stream, int synchronize);
 int rt_point_cloud_fill(const RtCameraParams *cams, int32_t count, uint32_t fields, const void *d_workspace, size_t workspace_bytes,
                         int64_t capacity, const RtPointCloud *out, void *stream, int synchronize);
+/* ---- rolling frames: sensor frames and clouds whose pixels are NOT taken from one pose -- a spinning lidar
+ *      that fires its columns over a revolution while the vehicle moves, a rolling-shutter camera that exposes its rows one after
+ *      another (the same call with a table made from rt_camera_directions).  A rolling frame belongs to a ray table of width x height
+ *      and is defined by an axis (0: the column x selects the slice, 1: the row y does), slice_pixels, a positive multiple of 8, and
+ *      slices = ceil(extent / slice_pixels) poses, extent = width for axis 0, height for axis 1.  The slice of pixel (x, y) is
+ *      (axis ? y : x) / slice_pixels; the last slice may be narrower than the others.  Frame i uses poses[i * slices + s] for slice s.
+ *      Slices are whole 8x8 tiles, so a wave of the primary kernel still has one origin and one rotation: slices finer than a tile
+ *      (a pose per column) have no common centre per wave and stay with rt_trace_rays.
+ *      1. Every plane except `depth` and `local` holds, bit for bit, what rt_trace_rays gives for the ray rt_ray_table_rays(table,
+ *         pose of the pixel's slice) makes for that pixel -- the reference's quirks included, as for G-buffer and sensor frames.
+ *      2. local = apply_lre(camera_pose of the pixel's slice, location): the hit in the sensor's frame at the moment the pixel was
+ *         taken -- the raw, motion-distorted scan -- while `location` is the de-skewed truth in the world.  All three components by
+ *         rule 5 of the point clouds (q = the host's euler2quat of that camera_pose, every sum left to right, nothing contracted);
+ *         depth equals local.z bit for bit.  On a miss local is 0 and depth FLT_MAX.
+ *      3. Layout, images (d_imgs, pitch) and non-finite poses as for rt_render_gbuffer_table; d_local is one more optional plane,
+ *         [count][height][width][3].  A slice whose pose is non-finite may put unspecified values into its own pixels; it does not
+ *         fault and does not change other slices or frames.
+ *      4. A rolling launch always reads plain records: it never takes a view slot, never grows the view pool and is counted by
+ *         neither rt_scene_view_stats nor rt_scene_dir_table_stats (view records are box - origin per frame and instance: a set
+ *         per slice would take hundreds of times the memory).  The stack form is chosen as rt_render_gbuffer chooses it.
+ *      5. RT_E_INVALID, judged before any device call: an axis that is neither 0 nor 1; slice_pixels < 8 or not a multiple of 8;
+ *         NULL poses, table, workspace, scene or out; a workspace smaller than rt_rolling_workspace_bytes; count outside
+ *         1..RT_MAX_BATCH; no output at all (no plane, no d_local and no d_imgs); a NULL entry in a non-NULL d_imgs; pitch <
+ *         3 * width with d_imgs.
+ *      poses: a HOST array [count][slices].  The call packs one 48-byte record per frame and slice -- the position, euler2quat of
+ *      inv_camera_pose's and of camera_pose's angles, made on the host so that their bits are those rt_ray_table_rays uses -- and
+ *      copies the records into the caller's workspace, ordered on `stream`, in front of the launch.  `poses` may be reused when the
+ *      call returns.  The copy reads ordinary host memory: it may wait until the work issued EARLIER on `stream` has finished (as
+ *      any copy from pageable memory), never for the render it precedes; the render itself is asynchronous unless synchronize != 0.
+ *      The workspace must stay untouched until the stream has passed the render.  The scene is held for the launch only: calls on
+ *      one scene with different workspaces overlap as G-buffer calls do. */
+typedef struct RtRollingPose {  /* camera_pose and inv_camera_pose of RtCameraParams */
+    float camera_pose[6];       /* x, y, z, yaw, pitch, roll */
+    float inv_camera_pose[6];   /* invert_lre(camera_pose) */
+} RtRollingPose;
+/* slices = ceil((axis ? height : width) / slice_pixels).  RT_E_INVALID: a size < 1, a bad axis or slice_pixels, a NULL slices. */
+int rt_rolling_slices(int32_t width, int32_t height, int32_t axis, int32_t slice_pixels, int32_t *slices);
+/* count x slices records of 48 bytes, in whole 256-byte blocks; 0 for count outside 1..RT_MAX_BATCH or slices < 1 */
+size_t rt_rolling_workspace_bytes(int32_t count, int32_t slices);
+int rt_render_gbuffer_rolling(RtScene *scene, const RtRayTable *table, const RtRollingPose *poses /* HOST [count][slices] */,
+                              int32_t count /* 1..RT_MAX_BATCH */, int32_t axis, int32_t slice_pixels,
+                              uint8_t *const *d_imgs /* NULL = no colour frames */, size_t pitch, const RtGBuffer *out,
+                              float *d_local /* optional [count][height][width][3] */, void *d_workspace, size_t workspace_bytes,
+                              void *stream, int synchronize);
+/* Rolling clouds: rt_point_cloud_offsets_table / rt_point_cloud_fill for rolling frames.  Rules 1-4 of the point clouds hold
+ * unchanged; rule 5's `local` uses the camera_pose of the point's slice (= the compacted `local` plane of the rolling frame), and
+ * `position` stays the world location.  The workspace is the static cloud's followed by the pose records, so the fill needs neither
+ * the scene nor the poses: it is given the table's size, count, axis, slice_pixels and fields as *_offsets_rolling was.  Everything
+ * read from the workspace is data: the slice index is bounded by `slices` before a record is read, the slot by `capacity` before a
+ * store.  The record copy of *_offsets_rolling waits as rt_render_gbuffer_rolling's does.
+ * RT_E_INVALID, judged before any device call: the cases of rt_render_gbuffer_rolling and of rt_point_cloud_offsets / _fill that
+ * apply, a workspace smaller than rt_point_cloud_rolling_workspace_bytes. */
+/* 0 where rt_point_cloud_workspace_bytes or rt_rolling_workspace_bytes is */
+size_t rt_point_cloud_rolling_workspace_bytes(int32_t width, int32_t height, int32_t count, uint32_t fields, int32_t slices);
+int rt_point_cloud_offsets_rolling(RtScene *scene, const RtRayTable *table, const RtRollingPose *poses, int32_t count, int32_t axis,
+                                   int32_t slice_pixels, float min_range, float max_range, const uint8_t *d_mask, uint32_t fields,
+                                   int64_t *d_offsets, void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+int rt_point_cloud_fill_rolling(int32_t width, int32_t height, int32_t count, int32_t axis, int32_t slice_pixels, uint32_t fields,
+                                const void *d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud *out,
+                                void *stream, int synchronize);
 /* same frame plus the parity planes (instrumented copy of the kernel: counts every visit) */
 int rt_render_debug(RtScene *scene, const RtCameraParams *cam, uint8_t *d_img, size_t pitch,
                     const RtDebugPlanes *planes, void *stream, int synchronize);

@@ -127,6 +127,19 @@ int rth_sensor_point_cloud_offsets(RthSensor *n, RthScene *s, const float *poses
 int rth_point_cloud_fill(int32_t width, int32_t height, const float *poses6, int32_t count, uint32_t fields,
                          const void *d_workspace, size_t workspace_bytes, int64_t capacity, const void *cloud, void *stream,
                          int synchronize);
+/* Rolling frames and clouds of a sensor (rt_hip.h "rolling frames"): poses6 is [count][slices][6], slices as rt_rolling_slices gives
+ * it for the sensor's size; the inverse poses are the host's invert_lre.  gbuffer: const RtGBuffer *; d_local optional; the
+ * workspaces as rt_rolling_workspace_bytes / rt_point_cloud_rolling_workspace_bytes size them.  Nothing of the sensor is written. */
+int rth_sensor_render_rolling(RthSensor *n, RthScene *s, const float *poses6, int32_t count, int32_t slices, int32_t axis,
+                              int32_t slice_pixels, const void *gbuffer, float *d_local, void *const *d_imgs, size_t pitch,
+                              void *d_workspace, size_t workspace_bytes, void *stream, int synchronize);
+int rth_sensor_point_cloud_offsets_rolling(RthSensor *n, RthScene *s, const float *poses6, int32_t count, int32_t slices, int32_t axis,
+                                           int32_t slice_pixels, float min_range, float max_range, const uint8_t *d_mask,
+                                           uint32_t fields, int64_t *d_offsets, void *d_workspace, size_t workspace_bytes,
+                                           void *stream, int synchronize);
+int rth_point_cloud_fill_rolling(int32_t width, int32_t height, int32_t count, int32_t axis, int32_t slice_pixels, uint32_t fields,
+                                 const void *d_workspace, size_t workspace_bytes, int64_t capacity, const void *cloud, void *stream,
+                                 int synchronize);
 int rth_camera_render_scene_stripes_batch(RthCamera *c, RthScene *s, const float *poses6, void *const *d_locals,
                                           size_t local_pitch, int32_t count, int32_t stripe_rows, int32_t rank,
                                           int32_t num_ranks, int synchronize);
