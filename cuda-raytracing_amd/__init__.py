@@ -176,7 +176,7 @@ class RtSceneDesc(C.Structure):
 RT_HIP_SYMBOLS = [
     "rt_abi_version", "rt_build_info", "rt_device_count", "rt_set_device", "rt_malloc", "rt_malloc_pitch", "rt_free", "rt_memcpy_d2h",
     "rt_memcpy_h2d", "rt_memcpy2d_d2h", "rt_stream_synchronize", "rt_device_synchronize", "rt_error_string",
-    "rt_bvh_build", "rt_scene_upload", "rt_scene_update_instance", "rt_scene_update_instance_async", "rt_scene_refit_mesh", "rt_scene_refit_mesh_device", "rt_scene_rebuild_mesh_device", "rt_scene_debug_read", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh_capacity", "rt_scene_mesh_flags", "rt_render", "rt_render_overlapped", "rt_render_overlapped_stats", "rt_scene_view_stats", "rt_scene_dir_table_stats", "rt_scene_reserve_views", "rt_scene_memory", "rt_scene_loop_stats", "rt_render_batch",
+    "rt_bvh_build", "rt_scene_upload", "rt_scene_update_instance", "rt_scene_update_instance_async", "rt_scene_refit_mesh", "rt_scene_refit_mesh_device", "rt_scene_rebuild_mesh_device", "rt_scene_debug_read", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh_capacity", "rt_scene_mesh_flags", "rt_render", "rt_render_overlapped", "rt_render_overlapped_stats", "rt_scene_view_stats", "rt_scene_view_cull_stats", "rt_scene_dir_table_stats", "rt_scene_reserve_views", "rt_scene_memory", "rt_scene_loop_stats", "rt_render_batch",
     "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_point_cloud_workspace_bytes", "rt_point_cloud_offsets", "rt_point_cloud_offsets_table", "rt_point_cloud_fill", "rt_rolling_slices", "rt_rolling_workspace_bytes", "rt_render_gbuffer_rolling", "rt_point_cloud_rolling_workspace_bytes", "rt_point_cloud_offsets_rolling", "rt_point_cloud_fill_rolling", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
@@ -288,6 +288,7 @@ def _declare(h, s):
     h.rt_render_overlapped.argtypes = [_vp, C.POINTER(RtCameraParams), _vp, C.c_size_t]
     h.rt_render_overlapped_stats.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     h.rt_scene_view_stats.argtypes = [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+    h.rt_scene_view_cull_stats.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
     h.rt_scene_dir_table_stats.argtypes = [_vp, C.POINTER(C.c_uint64)]
     h.rt_scene_reserve_views.argtypes = [_vp, C.c_int32]
     h.rt_scene_memory.argtypes = [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _i, _i]
@@ -656,6 +657,13 @@ class Scene:
         check(libs()[0].rt_scene_view_stats(self.device_handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "rt_scene_view_stats")
         return dict(launches=a.value, fallbacks=b.value, grows=c.value, slot_frames=d.value)
 
+    def view_cull_stats(self):
+        """rt_scene_view_cull_stats: the culled leaf children per frame in the views the scene's last pre-pass wrote -- a list with one
+        count per frame of that launch, empty when it wrote no culled views (RT_VIEW_CULL=0, a samples-only extension launch, none yet)"""
+        n, out = C.c_int32(0), (C.c_uint64 * 32)()
+        check(libs()[0].rt_scene_view_cull_stats(self.device_handle, C.byref(n), out), "rt_scene_view_cull_stats")
+        return [int(out[k]) for k in range(n.value)]
+
     def dir_table_stats(self):
         """rt_scene_dir_table_stats: dict(launches=, skipped=, grows=, bytes=) -- launches that read a direction table, view launches
         that did not, times a slot's table was replaced by a larger one, bytes the tables hold now"""
@@ -673,7 +681,7 @@ class Scene:
         check(libs()[0].rt_scene_memory(self.device_handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)), "rt_scene_memory")
         return dict(records_bytes=a.value, view_pool_bytes=b.value, device_bytes=c.value, view_slots=d.value, view_slot_frames=e.value)
 
-    LOOP_STATS = ("waves", "asm", "asm_posed", "cpp_octant", "cpp_generic", "deep", "retraced_lanes")     # RT_LOOP_* of include/rt_hip.h
+    LOOP_STATS = ("waves", "asm", "asm_posed", "cpp_octant", "cpp_generic", "deep", "retraced_lanes", "cpp_iters")     # RT_LOOP_* of include/rt_hip.h
 
     def loop_stats(self, camera, poses, d_imgs, pitch, stream=None):
         """rt_scene_loop_stats: renders the batch (poses[i] -> d_imgs[i]) through the instrumented copy of the production kernel and says

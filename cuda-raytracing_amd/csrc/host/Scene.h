@@ -53,6 +53,10 @@ public:
     // Direction tables of batched launches (rt_scene_dir_table_stats of include/rt_hip.h): launches that read one, view launches
     // that did not, buffer growths, bytes held.  Returns the status (also in last_error).
     int dir_table_stats(uint64_t out[4]);
+    // Back-facing leaves culled in the views of the scene's last batched launch (rt_scene_view_cull_stats of include/rt_hip.h; it waits
+    // for the device): *frames = the frames of that launch, 0 when its views hold no culled box; culled_leaves[k] for k < *frames, room
+    // for 32 entries.  Returns the status (also in last_error).
+    int view_cull_stats(int32_t* frames, uint64_t* culled_leaves);
     // A mesh deforms (same triangle count and order): host copy and device copy get the moved vertices and normals and refitted
     // bounds -- texture coordinates stay; no rebuild, no re-upload of anything else.  Ordered on `stream` like update_mesh_instance(.., stream).
     void refit_mesh(int mesh_index, std::vector<TrianglePrimitive> moved, void* stream = nullptr);

@@ -818,6 +818,11 @@ int Scene::dir_table_stats(uint64_t out[4])
     return last_error = d_scene ? rt_scene_dir_table_stats(d_scene, out) : RT_E_INVALID;
 }
 
+int Scene::view_cull_stats(int32_t* frames, uint64_t* culled_leaves)
+{
+    return last_error = d_scene ? rt_scene_view_cull_stats(d_scene, frames, culled_leaves) : RT_E_INVALID;
+}
+
 // -------------------------------------------------------------------------------- Camera
 
 Camera::Camera(int width, int height, float3x3 K, float4 D) : width(width), height(height), K(K), D(D)

@@ -1189,7 +1189,11 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
     else {
     // (the C++ loop reads view records for the primary kernels' rays only; an extension ray that does not qualify for the hand-written
     // loop reads the records themselves)
-#define RT_TRACE_LOOP(O) trace_loop<DEBUG, PROF, EX, COUNT, STK, POPS, O, ANYHIT, (VIEW && !EX)>(p, in, inst_index, r, org, stack, hit, cnt, iters, pops, vdelta, tmax)
+    // (STATS: the lanes' iterations on the compiler's loops are counted too, RT_LOOP_CPP_ITERS -- the loops that take a view's box
+    // words through the generic slab test)
+    static_assert(!(STATS && COUNT), "one iteration counter");
+    int stat_iters = 0;
+#define RT_TRACE_LOOP(O) trace_loop<DEBUG, PROF, EX, (COUNT || STATS), STK, POPS, O, ANYHIT, (VIEW && !EX)>(p, in, inst_index, r, org, stack, hit, cnt, STATS ? &stat_iters : iters, pops, vdelta, tmax)
     if constexpr (STATS) loop_stat(p, STK::kSpill ? RT_LOOP_DEEP : (oct >= 0 ? RT_LOOP_CPP_OCTANT : RT_LOOP_CPP_GENERIC));
     switch (oct) {                                              // (wave-uniform: a scalar branch)
     case 0: RT_TRACE_LOOP(0); break;
@@ -1203,6 +1207,7 @@ __device__ __forceinline__ void trace_instance(const RenderParams& p, const DevI
     default: RT_TRACE_LOOP(-1); break;
     }
 #undef RT_TRACE_LOOP
+    if constexpr (STATS) atomicAdd(&p.loop_stats[RT_LOOP_CPP_ITERS], (unsigned long long)stat_iters);
     }
 }
 
@@ -2194,10 +2199,13 @@ __global__ __launch_bounds__(kRefitRunThreads) void refit_run_kernel(float4* rec
 // like any launch and needs no host buffer that outlives the call
 __global__ void set_instance_kernel(DevInstance* dst, const DevInstance value) { *dst = value; }
 
-// View records of the frames of one launch (RtScene::ViewPool, trace_loop<.., VIEW>): for every frame (blockIdx.y) and every
+// View records of the frames of one launch (RtScene::ViewPool, trace_loop<.., VIEW>): for every frame and every
 // instance, the instance's interior records with `box - origin` in place of the twelve box words -- origin = the frame's camera
 // position in the instance's mesh space, computed by the function the traversal uses (to_mesh_space), the subtraction being
-// the one box_differences does per visit: the same fp32 operation on the same operands, done once.  One thread per 16 bytes.
+// the one box_differences does per visit: the same fp32 operation on the same operands, done once.  One thread per 16 bytes of a
+// record, for kViewFrameChunk frames of the launch in turn (blockIdx.y = the chunk): what does not depend on the frame -- the record's
+// words, the triangles the cull below looks at -- is read once per chunk, a wave's stores of one frame are one run of 1 KiB, and the
+// origins of the chunk's frames, one per instance, are computed once per workgroup (LDS) instead of once per thread.
 // In front of a frame's view records stand its ray headers (RayHeader, rt_device_types.h), one 64-byte block per instance, written
 // by one thread each: that same origin and the instance fields a wave of render_kernel<.., VIEW> needs before its loop.
 struct ViewJob {
@@ -2209,10 +2217,49 @@ struct ViewJob {
     // the launch's direction table (RenderParams::dir_table; 0 blocks = none): workgroups record_blocks .. of every row of the grid
     // write it, `dir_blocks` per row, four 8x8 tiles each -- every row takes a share, so no row brings workgroups with nothing to do
     uint32_t record_blocks, dir_blocks;
+    // back-facing leaves: 1 = the views of this launch are read by kernels that report no visit counts -- a leaf child
+    // none of whose triangles can be accepted from the frame's origin gets a box that no ray passes.  0 = boxes as they are.
+    int32_t cull;
+    uint32_t records_end;                       // records of the scene: a leaf reference is followed only below it
 };
+
+// Back-facing leaves.  A candidate is accepted only with denom < 0 and !(tt < 0), tt = N / denom, N = (v0 - ro) . n: N depends on the
+// frame's origin and the triangle alone.  With N >= kCullMin and denom < 0, tt < 0 strictly -- 2^-20 / |denom| is above 2^-149 for every
+// finite denom, and the IEEE division does not round it to -0; an infinite denom gives -0 and a NaN point.
+constexpr float kCullMin = 9.5367431640625e-07f;        // 2^-20
+static_assert(kCullMin * 1048576.0f == 1.0f, "2^-20");
+// the six box words of a culled child: a quiet NaN with a payload that no subtraction produces (rt_scene_view_cull_stats looks for it)
+constexpr int kCullWord = 0x7fc0c011;
+
+// What triangle k of the leaf child `ref` says about culling that child, whatever the frame: kCullKeeps for anything that is not a leaf
+// of one to four coded triangles (interior nodes, empty leaves, leaves whose count is looked up or above four are left alone),
+// kCullSilent for k beyond the leaf's count, kCullAsk for a triangle to evaluate per frame -- v0 and the normal are then in t0, t1.
+constexpr int kCullKeeps = 0, kCullSilent = 1, kCullAsk = 2;
+__device__ __forceinline__ int cull_triangle(const RenderParams& p, const ViewJob& job, int32_t ref, int k, float4& t0, float4& t1)
+{
+    const int coded = (ref >> kSlotBits) & 31;
+    const uint32_t slot = (uint32_t)(ref & kSlotMask);
+    if (ref >= 0 || coded < 1 || coded > 4 || slot + (uint32_t)coded > job.records_end) return kCullKeeps;
+    if (k >= coded) return kCullSilent;
+    const float4* t = p.records + (size_t)(slot + (uint32_t)k) * 4;
+    t0 = t[0]; t1 = t[1];
+    return kCullAsk;
+}
+// "This triangle keeps its leaf alive for the frame whose origin is o": !(N >= kCullMin), N from the hand-written loop's own operations
+// in their order (RT_ASM_LOOP_TEXT "numerator"; dot(v0 - r.ro, nrm) in triangle_test)
+__device__ __forceinline__ bool cull_keeps(int state, float4 t0, float4 t1, V3 o)
+{
+    const float x = t0.x - o.x, y = t0.y - o.y, z = t0.z - o.z;
+    const float n = x * t0.w + y * t1.x + z * t1.y;
+    return state == kCullKeeps || (state == kCullAsk && !(n >= kCullMin));
+}
+
+constexpr int kViewFrameChunk = 8;
+static_assert(kViewFrameChunk * kMaxViewInstances <= 256, "one thread per (frame of the chunk, instance) computes its origin");
 
 __global__ __launch_bounds__(256) void view_records_kernel(const RenderParams p, const ViewJob job)
 {
+    __shared__ float origin[kViewFrameChunk * kMaxViewInstances][3];
     if (blockIdx.x >= job.record_blocks) {
         // one thread per lane of a tile: the lane's camera_space_direction, from the intrinsics every frame of the launch shares.
         // Lanes beyond a ragged edge write what they compute: the table has room for whole tiles and nothing reads those.
@@ -2226,37 +2273,91 @@ __global__ __launch_bounds__(256) void view_records_kernel(const RenderParams p,
         out[0] = d.x; out[64] = d.y; out[128] = d.z;
         return;
     }
-    const int t = (int)(blockIdx.x * 256 + threadIdx.x), frame = (int)blockIdx.y;
+    // the frames of this row of the grid, and their origins in every instance's mesh space
+    const int frame0 = (int)blockIdx.y * kViewFrameChunk, frames = min(kViewFrameChunk, p.num_frames - frame0);
+    if ((int)threadIdx.x < frames * job.n) {
+        const FrameParams& f = p.frames[frame0 + (int)threadIdx.x / job.n];
+        const V3 o = to_mesh_space(p.instances[(int)threadIdx.x % job.n], v3(f.origin[0], f.origin[1], f.origin[2]), v3(0.0f, 0.0f, 1.0f)).ro;
+        origin[threadIdx.x][0] = o.x; origin[threadIdx.x][1] = o.y; origin[threadIdx.x][2] = o.z;
+    }
+    __syncthreads();
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int rec = t >> 2;
     const int quarter = t & 3;
-    const FrameParams& f = p.frames[frame];
-    char* view = (char*)p.records + p.view_base + (size_t)frame * p.view_frame_stride;
+    char* view = (char*)p.records + p.view_base;
     if (rec >= job.total) {
-        // the job.n threads behind the last record: the ray header of (frame, instance), see RayHeader
+        // the job.n threads behind the last record: the ray headers of the instance, one per frame, see RayHeader
         const int i = t - job.total * 4;
         if (i >= job.n) return;
         const DevInstance& in = p.instances[i];
-        const V3 o = to_mesh_space(in, v3(f.origin[0], f.origin[1], f.origin[2]), v3(0.0f, 0.0f, 1.0f)).ro;
-        const float inf = __int_as_float(0x7f800000);
-        const uint32_t flags = (fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf ? kRayOriginFinite : 0u) |
-                               ((p.mesh_flags[in.mesh_index] & kBoxUnordered) != 0 ? kRayBoxUnordered : 0u) |
-                               (in.exact_uv != 0 ? kRayExactUv : 0u) | (in.unit_inv != 0 ? kRayUnitInv : 0u);
-        const uint32_t vdelta = p.view_base + (uint32_t)frame * p.view_frame_stride + (uint32_t)p.view_inst_off[i];
-        float4* h = (float4*)view + (size_t)i * 4;
-        h[0] = make_float4(o.x, o.y, o.z, __uint_as_float(flags));
-        h[1] = make_float4(in.q_rot.x, in.q_rot.y, in.q_rot.z, in.q_rot.w);
-        h[2] = make_float4(in.inv_scale[0], in.inv_scale[1], in.inv_scale[2], __int_as_float(in.root_ref));
-        h[3] = make_float4(in.inv_pose_xyz[0], in.inv_pose_xyz[1], in.inv_pose_xyz[2], __uint_as_float(vdelta));
+        for (int k = 0; k < frames; k++) {
+            const int frame = frame0 + k;
+            const V3 o = v3(origin[k * job.n + i][0], origin[k * job.n + i][1], origin[k * job.n + i][2]);
+            const float inf = __int_as_float(0x7f800000);
+            const uint32_t flags = (fabsf(o.x) < inf && fabsf(o.y) < inf && fabsf(o.z) < inf ? kRayOriginFinite : 0u) |
+                                   ((p.mesh_flags[in.mesh_index] & kBoxUnordered) != 0 ? kRayBoxUnordered : 0u) |
+                                   (in.exact_uv != 0 ? kRayExactUv : 0u) | (in.unit_inv != 0 ? kRayUnitInv : 0u);
+            const uint32_t vdelta = p.view_base + (uint32_t)frame * p.view_frame_stride + (uint32_t)p.view_inst_off[i];
+            float4* h = (float4*)(view + (size_t)frame * p.view_frame_stride) + (size_t)i * 4;
+            h[0] = make_float4(o.x, o.y, o.z, __uint_as_float(flags));
+            h[1] = make_float4(in.q_rot.x, in.q_rot.y, in.q_rot.z, in.q_rot.w);
+            h[2] = make_float4(in.inv_scale[0], in.inv_scale[1], in.inv_scale[2], __int_as_float(in.root_ref));
+            h[3] = make_float4(in.inv_pose_xyz[0], in.inv_pose_xyz[1], in.inv_pose_xyz[2], __uint_as_float(vdelta));
+        }
         return;
     }
     int i = 0;
     while (i + 1 < job.n && rec >= job.count[i]) { rec -= job.count[i]; i++; }
-    const V3 o = to_mesh_space(p.instances[i], v3(f.origin[0], f.origin[1], f.origin[2]), v3(0.0f, 0.0f, 1.0f)).ro;
-    float4 v = p.records[(size_t)(job.node_base[i] + rec) * 4 + quarter];
-    if (quarter == 0) v = make_float4(v.x - o.x, v.y - o.y, v.z - o.z, v.w - o.x);          // the operand order of box_differences
-    else if (quarter == 1) v = make_float4(v.x - o.y, v.y - o.z, v.z - o.x, v.w - o.y);
-    else if (quarter == 2) v = make_float4(v.x - o.z, v.y - o.x, v.z - o.y, v.w - o.z);
-    ((float4*)view)[(size_t)(job.first[i] + rec) * 4 + quarter] = v;
+    const float4 w = p.records[(size_t)(job.node_base[i] + rec) * 4 + quarter];
+    // The cull: the four threads of a record take one triangle each of either child, read here once for all frames.
+    int state_a = kCullKeeps, state_b = kCullKeeps;
+    float4 a0 = w, a1 = w, b0 = w, b1 = w;
+    if (job.cull) {
+        const float4 q3 = p.records[(size_t)(job.node_base[i] + rec) * 4 + 3];
+        state_a = cull_triangle(p, job, __float_as_int(q3.x), quarter, a0, a1);
+        state_b = cull_triangle(p, job, __float_as_int(q3.y), quarter, b0, b1);
+    }
+    float4* out = (float4*)view + (size_t)(job.first[i] + rec) * 4 + quarter;
+    for (int k = 0; k < frames; k++) {
+        const int frame = frame0 + k;
+        const V3 o = v3(origin[k * job.n + i][0], origin[k * job.n + i][1], origin[k * job.n + i][2]);
+        float4 v = w;
+        if (quarter == 0) v = make_float4(w.x - o.x, w.y - o.y, w.z - o.z, w.w - o.x);          // the operand order of box_differences
+        else if (quarter == 1) v = make_float4(w.x - o.y, w.y - o.z, w.z - o.x, w.w - o.y);
+        else if (quarter == 2) v = make_float4(w.x - o.z, w.y - o.x, w.z - o.y, w.w - o.z);
+        if (job.cull) {
+            // A child none of whose triangles keeps it gets six NaN box words (kCullWord): every plane product is a NaN for any dinv,
+            // min / max of NaNs stay NaN, and `far >= near` is false in the octant forms and in the generic slab test alike -- the
+            // generic test sorts the two products of an axis, so +inf / -inf planes would PASS it.  (Wave-uniform control flow here:
+            // the four threads of a record are neighbours of one wave, and every thread of the wave runs the same frames.)
+            const unsigned long long ka = __ballot(cull_keeps(state_a, a0, a1, o));
+            const unsigned long long kb = __ballot(cull_keeps(state_b, b0, b1, o));
+            const int group = (int)(threadIdx.x & 60u);
+            const bool dead_a = ((ka >> group) & 15ull) == 0ull, dead_b = ((kb >> group) & 15ull) == 0ull;
+            const float dead = __int_as_float(kCullWord);
+            if (quarter == 0) { if (dead_a) v = make_float4(dead, dead, dead, dead); }
+            else if (quarter == 1) { if (dead_a) { v.x = dead; v.y = dead; } if (dead_b) { v.z = dead; v.w = dead; } }
+            else if (quarter == 2) { if (dead_b) v = make_float4(dead, dead, dead, dead); }
+        }
+        *(float4*)((char*)out + (size_t)frame * p.view_frame_stride) = v;
+    }
+}
+
+// rt_scene_view_cull_stats (diagnostics, never part of a render): the culled children in one instance's part of the views of one
+// launch -- a leaf child of one to four coded triangles whose x planes are kCullWord, the NaN no box minus origin gives.
+// One thread per view record, blockIdx.y = the frame.
+__global__ __launch_bounds__(256) void view_cull_count_kernel(const float4* records, uint32_t view_base, uint32_t frame_stride, int32_t first,
+                                                              int32_t count, unsigned long long* out)
+{
+    const int rec = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (rec >= count) return;
+    const float4* q = (const float4*)((const char*)records + view_base + (size_t)blockIdx.y * frame_stride) + (size_t)(first + rec) * 4;
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    const int pinf = kCullWord, ninf = kCullWord;
+    auto coded_leaf = [](int32_t ref) { const int c = (ref >> kSlotBits) & 31; return ref < 0 && c >= 1 && c <= 4; };
+    const int n = (coded_leaf(__float_as_int(q3.x)) && __float_as_int(q0.x) == pinf && __float_as_int(q0.w) == ninf ? 1 : 0) +
+                  (coded_leaf(__float_as_int(q3.y)) && __float_as_int(q1.z) == pinf && __float_as_int(q2.y) == ninf ? 1 : 0);
+    if (n) atomicAdd(&out[blockIdx.y], (unsigned long long)n);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -5390,6 +5491,7 @@ int view_resize(RtScene* s, int frames)
     s->records_alloc_bytes = total;
     v.base_bytes = base; v.slot_frames = frames; v.slots = slots; v.grows++;
     for (auto& sl : v.slot) { sl.used = false; sl.stream = nullptr; }
+    v.written = RtScene::ViewPool::Written();                   // (the views of the last launch did not move with the records)
     return RT_OK;
 }
 
@@ -5397,6 +5499,13 @@ int view_resize(RtScene* s, int frames)
 int dir_table_mode()
 {
     static const int mode = [] { const char* e = getenv("RT_DIR_TABLE"); return e && e[0] == '0' ? 0 : 1; }();
+    return mode;
+}
+
+// RT_VIEW_CULL=0: the pre-pass writes every view with the boxes as they are (read once; the A/B switch, and the tests')
+int view_cull_mode()
+{
+    static const int mode = [] { const char* e = getenv("RT_VIEW_CULL"); return e && e[0] == '0' ? 0 : 1; }();
     return mode;
 }
 
@@ -5491,9 +5600,20 @@ int view_prepare(RtScene* s, RenderParams& p, hipStream_t stream, int samples = 
     job.record_blocks = (uint32_t)(((size_t)job.total * 4 + (size_t)job.n + 255) / 256);
     p.dir_table = caller_table ? caller_table : (primary && samples == 1) ? dir_table_prepare(s, v.slot[use], p) : nullptr;
     // (four tiles per workgroup, the workgroups dealt to the rows of the grid)
-    job.dir_blocks = p.dir_table && !caller_table ? (uint32_t)((((size_t)p.tiles_x * (size_t)p.tiles_y + 3) / 4 + (size_t)p.num_frames - 1) / (size_t)p.num_frames) : 0u;
-    hipLaunchKernelGGL(view_records_kernel, dim3(job.record_blocks + job.dir_blocks, (unsigned)p.num_frames), dim3(256), 0, stream, p, job);
+    const size_t rows = ((size_t)p.num_frames + kViewFrameChunk - 1) / kViewFrameChunk;
+    job.dir_blocks = p.dir_table && !caller_table ? (uint32_t)((((size_t)p.tiles_x * (size_t)p.tiles_y + 3) / 4 + rows - 1) / rows) : 0u;
+    // culled views go to the kernels that report no visit counts: the primary and G-buffer launches.  The samples-only extension
+    // kernel counts node pops against the oracle's and reads the boxes as they are.
+    job.cull = primary && view_cull_mode() ? 1 : 0;
+    job.records_end = (uint32_t)(s->records_bytes / 64);
+    hipLaunchKernelGGL(view_records_kernel, dim3(job.record_blocks + job.dir_blocks, (unsigned)rows), dim3(256), 0, stream, p, job);
     if (hipGetLastError() != hipSuccess) { p.dir_table = nullptr; count(&RtScene::ViewPool::fallbacks); return -1; }
+    {
+        // (what rt_scene_view_cull_stats counts: the views this launch wrote, while they stand)
+        RtScene::ViewPool::Written& w = v.written;
+        w.culled = job.cull != 0; w.view_base = p.view_base; w.frames = p.num_frames; w.n = job.n;
+        for (int i = 0; i < job.n; i++) { w.first[i] = job.first[i]; w.count[i] = job.count[i]; }
+    }
     if (!caller_table) count(p.dir_table ? &RtScene::ViewPool::dir_launches : &RtScene::ViewPool::dir_skipped);
     return use;
 }
@@ -6203,6 +6323,32 @@ int rt_scene_view_stats(RtScene* s, uint64_t* launches, uint64_t* fallbacks, uin
     if (fallbacks) *fallbacks = s->view.fallbacks;
     if (grows) *grows = s->view.grows;
     if (slot_frames) *slot_frames = s->view.slot_frames;
+    return RT_OK;
+}
+
+int rt_scene_view_cull_stats(RtScene* s, int32_t* frames, uint64_t* culled_leaves)
+{
+    RT_SCENE_CALL(s);
+    if (!frames || !culled_leaves) return RT_E_INVALID;
+    *frames = 0;
+    const RtScene::ViewPool::Written w = s->view.written;
+    if (!w.culled || w.frames < 1 || w.frames > kMaxBatch || s->view.slot_frames < 1) return RT_OK;
+    RT_HIP(hipDeviceSynchronize());                             // (the pre-pass that wrote them, and nothing writes them meanwhile: call_mu)
+    unsigned long long* d_out = nullptr;
+    RT_HIP(hipMalloc((void**)&d_out, sizeof(unsigned long long) * kMaxBatch));
+    hipError_t e = hipMemset(d_out, 0, sizeof(unsigned long long) * kMaxBatch);
+    for (int i = 0; i < w.n && e == hipSuccess; i++) {
+        if (w.count[i] < 1) continue;
+        hipLaunchKernelGGL(view_cull_count_kernel, dim3((unsigned)((w.count[i] + 255) / 256), (unsigned)w.frames), dim3(256), 0, nullptr,
+                           s->d_records, w.view_base, (uint32_t)((size_t)s->view.frame_records * 64), w.first[i], w.count[i], d_out);
+        e = hipGetLastError();
+    }
+    unsigned long long host[kMaxBatch] = {};
+    if (e == hipSuccess) e = hipMemcpy(host, d_out, sizeof(host), hipMemcpyDeviceToHost);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return (int)e;
+    for (int k = 0; k < w.frames; k++) culled_leaves[k] = host[k];
+    *frames = w.frames;
     return RT_OK;
 }
 

@@ -116,6 +116,8 @@ struct RtScene {
         // order, or its event completed) is all the ordering it needs.  It grows inside the launch that needs more room, after a wait
         // for the slot's event, and is freed with the scene.  Its bytes are counted in dir_bytes, not in RtScene::device_bytes.
         struct Slot { hipStream_t stream = nullptr; hipEvent_t done = nullptr; bool used = false; float* d_dirs = nullptr; size_t dirs_bytes = 0; } slot[3];
+        // the views the last pre-pass of this scene wrote (rt_scene_view_cull_stats counts the culled children in them)
+        struct Written { bool culled = false; uint32_t view_base = 0; int32_t frames = 0, n = 0; int32_t first[rt::kMaxViewInstances] = {}, count[rt::kMaxViewInstances] = {}; } written;
         uint64_t launches = 0, fallbacks = 0, grows = 0;
         uint64_t dir_launches = 0, dir_skipped = 0, dir_grows = 0, dir_bytes = 0;   // rt_scene_dir_table_stats
     } view;

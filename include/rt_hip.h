@@ -261,6 +261,15 @@ int rt_scene_reserve_views(RtScene *scene, int32_t frames_per_launch);
 int rt_scene_memory(RtScene *scene, size_t *records_bytes, size_t *view_pool_bytes, size_t *device_bytes, int32_t *view_slots,
                     int32_t *view_slot_frames);
 int rt_scene_view_stats(RtScene *scene, uint64_t *launches, uint64_t *fallbacks, uint64_t *grows, int32_t *slot_frames);
+/* Back-facing leaves (no counterpart in the reference, which visits them).  In the views of primary and G-buffer launches -- the
+ * kernels that report no visit counts -- a leaf child of one to four triangles gets a box no ray passes (NaN words) when none of its triangles
+ * can be accepted from the frame's origin: (v0 - origin) . n >= 2^-20 for each of them, evaluated with the traversal's own fp32
+ * operations.  Frames and hit ids are bit for bit what they were; the kernels visit fewer nodes than the
+ * reference.  RT_VIEW_CULL=0 (read once per process) writes every view with the boxes as they are.
+ * rt_scene_view_cull_stats (diagnostics; it waits for the device) counts, in the views that the scene's last pre-pass wrote,
+ * the culled leaf children of each frame: *frames = the frames of that launch, or 0 when it wrote no culled views (none yet, the
+ * switch, a launch of the samples-only extension kernel); culled_leaves[k] for k < *frames, room for 32 entries. */
+int rt_scene_view_cull_stats(RtScene *scene, int32_t *frames, uint64_t *culled_leaves);
 /* Direction tables (no counterpart in the reference, whose kernel derives every pixel's ray from K_inv and D in every frame,
  * raycast.cu:159-182).  A primary launch that renders through view records, for one rank, of at least two frames whose K_inv and D
  * are equal BIT FOR BIT in every frame (memcmp, so a NaN equals itself and -0 differs from 0), reads each pixel's camera-space
@@ -291,6 +300,7 @@ enum {
     RT_LOOP_CPP_GENERIC = 4,    /* casts on the compiler's generic loop (mixed octants in the wave, zero / non-finite direction inverses, unordered boxes) */
     RT_LOOP_DEEP = 5,           /* casts traced again on the general stack (some lane outgrew the LDS part) */
     RT_LOOP_RETRACED_LANES = 6, /* rays (lanes) traced again */
+    RT_LOOP_CPP_ITERS = 7,      /* loop iterations of all lanes on the compiler's loops (octant, generic, deep): nodes and triangles visited there */
     RT_LOOP_WORDS = 8
 };
 int rt_scene_loop_stats(RtScene *scene, const RtCameraParams *cams, uint8_t *const *d_imgs, size_t pitch, int32_t count,
