@@ -89,7 +89,14 @@ class RtGBuffer(C.Structure):               # include/rt_hip.h (device planes [c
     _fields_ = [(n, _vp) for n in _GBUFFER_OUTPUTS]
 
 
-class RtRollingPose(C.Structure):           # include/rt_hip.h, "rolling frames": the pose of one slice and its inverse
+_VISIBILITY_OUTPUTS = ("visible", "facing")
+
+
+class RtVisibility(C.Structure):            # include/rt_hip.h, "visibility masks" (device planes [count][height][width], at least one)
+    _fields_ = [(n, _vp) for n in _VISIBILITY_OUTPUTS]
+
+
+class RtRollingPose(C.Structure):          # include/rt_hip.h, "rolling frames": the pose of one slice and its inverse
     _fields_ = [("camera_pose", C.c_float * 6), ("inv_camera_pose", C.c_float * 6)]
 
 
@@ -177,7 +184,7 @@ RT_HIP_SYMBOLS = [
     "rt_abi_version", "rt_build_info", "rt_device_count", "rt_set_device", "rt_malloc", "rt_malloc_pitch", "rt_free", "rt_memcpy_d2h",
     "rt_memcpy_h2d", "rt_memcpy2d_d2h", "rt_stream_synchronize", "rt_device_synchronize", "rt_error_string",
     "rt_bvh_build", "rt_scene_upload", "rt_scene_update_instance", "rt_scene_update_instance_async", "rt_scene_refit_mesh", "rt_scene_refit_mesh_device", "rt_scene_rebuild_mesh_device", "rt_scene_debug_read", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh_capacity", "rt_scene_mesh_flags", "rt_render", "rt_render_overlapped", "rt_render_overlapped_stats", "rt_scene_view_stats", "rt_scene_view_cull_stats", "rt_scene_dir_table_stats", "rt_scene_reserve_views", "rt_scene_memory", "rt_scene_loop_stats", "rt_render_batch",
-    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_point_cloud_workspace_bytes", "rt_point_cloud_offsets", "rt_point_cloud_offsets_table", "rt_point_cloud_fill", "rt_rolling_slices", "rt_rolling_workspace_bytes", "rt_render_gbuffer_rolling", "rt_point_cloud_rolling_workspace_bytes", "rt_point_cloud_offsets_rolling", "rt_point_cloud_fill_rolling", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
+    "rt_render_debug", "rt_render_ids", "rt_render_gbuffer", "rt_render_gbuffer_table", "rt_ray_table_create", "rt_ray_table_info", "rt_ray_table_destroy", "rt_ray_table_rays", "rt_camera_directions", "rt_point_cloud_workspace_bytes", "rt_point_cloud_offsets", "rt_point_cloud_offsets_table", "rt_point_cloud_fill", "rt_rolling_slices", "rt_rolling_workspace_bytes", "rt_render_gbuffer_rolling", "rt_point_cloud_rolling_workspace_bytes", "rt_point_cloud_offsets_rolling", "rt_point_cloud_fill_rolling", "rt_visibility", "rt_render_ex", "rt_render_ex_stripes", "rt_stripe_rows", "rt_render_stripes", "rt_render_stripes_batch", "rt_render_stripes_batch_rotating", "rt_unstripe", "rt_unstripe_batch", "rt_unstripe_batch_rotating",
     "rt_comm_available", "rt_comm_last_error", "rt_comm_last_error_any", "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_info", "rt_comm_destroy",
     "rt_group_start", "rt_group_end", "rt_gather", "rt_all_to_all", "rt_render_tiled", "rt_render_tiled_all", "rt_timer_create", "rt_timer_start", "rt_timer_stop",
     "rt_timer_elapsed_ms", "rt_timer_destroy", "rt_trace_workspace_bytes", "rt_trace_rays", "rt_occluded", "rt_camera_rays",
@@ -193,7 +200,7 @@ RT_HOST_SYMBOLS = [
     "rth_mesh_num_nodes", "rth_mesh_max_level", "rth_mesh_get_triangles", "rth_mesh_get_nodes", "rth_mesh_get_leaf_indices",
     "rth_mesh_print_stats", "rth_scene_create", "rth_scene_free", "rth_scene_add_material", "rth_scene_add_material_ppm",
     "rth_scene_set_material_params", "rth_scene_add_mesh", "rth_scene_add_mesh_instance", "rth_scene_upload_to_device", "rth_scene_update_mesh_instance", "rth_scene_update_mesh_instance_async", "rth_scene_refit_mesh", "rth_scene_rebuild_mesh",
-    "rth_scene_num_mesh_instances", "rth_scene_device_handle", "rth_instance_build", "rth_camera_create", "rth_camera_free",
+    "rth_scene_num_mesh_instances", "rth_scene_device_handle", "rth_scene_visibility", "rth_instance_build", "rth_camera_create", "rth_camera_free",
     "rth_camera_set_pose", "rth_camera_set_stream", "rth_camera_render_scene", "rth_camera_render_scene_stripes",
     "rth_camera_render_scene_tiled", "rth_camera_render_scene_batch", "rth_camera_render_gbuffer", "rth_camera_directions", "rth_sensor_create", "rth_sensor_destroy", "rth_sensor_set_pose", "rth_sensor_set_stream", "rth_sensor_rays", "rth_sensor_render_gbuffer", "rth_camera_point_cloud_offsets", "rth_sensor_point_cloud_offsets", "rth_point_cloud_fill", "rth_sensor_render_rolling", "rth_sensor_point_cloud_offsets_rolling", "rth_point_cloud_fill_rolling","rth_camera_render_scene_stripes_batch", "rth_camera_render_scene_stripes_batch_rotating", "rth_camera_set_options",
     "rth_camera_render_scene_ex", "rth_xorwow", "rth_save_png", "rth_write_png_bgr",
@@ -353,6 +360,9 @@ def _declare(h, s):
     h.rt_trace_workspace_bytes.argtypes = [C.c_int32]
     h.rt_trace_rays.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtRayHits), _vp, C.c_size_t, _vp, C.c_int]
     h.rt_occluded.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, _vp, C.c_int]
+    visibility = [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_float, C.POINTER(RtVisibility), _vp, C.c_int]
+    h.rt_visibility.argtypes = visibility
+    s.rth_scene_visibility.argtypes = visibility
     h.rt_closest_points.argtypes = [_vp, _vp, _vp, C.c_int32, C.POINTER(RtPointHits), _vp, C.c_int]
     h.rt_count_crossings.argtypes = [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(RtCrossings), _vp, C.c_int]
     h.rt_winding_numbers.argtypes = [_vp, _vp, C.c_int32, _vp, _vp, C.c_int]
@@ -1062,6 +1072,43 @@ class Scene:
                                               sg.ptr(out["count"]) if "count" in out else None, sg.stream, sg.sync), "rt_occupancy_grid")
             return {k: sg.result(a) for k, a in out.items()}
 
+    VISIBILITY_OUTPUTS = _VISIBILITY_OUTPUTS
+
+    def visibility(self, instance, location, points, normal=None, bias=2.0 ** -10, outputs=("visible",), stream=None, as_numpy=False):
+        """Visibility masks (rt_visibility; the rule is in include/rt_hip.h, "visibility masks"): which of `points` see the surface
+        each pixel's ray hit.  instance [n, h, w] int32 and location [n, h, w, 3] float32 (normal [n, h, w, 3] too when "facing" is
+        wanted) are G-buffer planes -- of Camera.render_gbuffer, Sensor.render_gbuffer, Sensor.render_rolling, or Scene.trace_rays
+        reshaped -- as torch tensors on the scene's GPU or numpy arrays.  points: [K, 3] (the same for every frame) or [n, K, 3],
+        world, 1 <= K <= 32, anything numpy converts to float32 or a torch tensor.  bias in [0, 1): the relative amount by which
+        the ray from a point stops short of the surface (0 lets the surface shadow itself).  Returns a dict of the wanted
+        VISIBILITY_OUTPUTS, int32 [n, h, w]: bit k of visible = points[k] sees the hit (no front face lies before it), of facing =
+        the hit's front side is turned to points[k]; a miss is 0; `visible & facing` is "lit by" / "valid for".  Tensors for
+        tensors, enqueued on `stream` (default the current torch stream) without a synchronise; numpy arrays for numpy arrays or
+        with as_numpy=True.  Every ValueError is raised before a device call."""
+        outputs, bias = _visibility_options(outputs, bias)
+        facing = "facing" in outputs
+        if facing and normal is None:
+            raise ValueError("outputs with 'facing' need the normal plane")
+        if instance is None or location is None:
+            raise ValueError("instance and location are required")
+        torch_in, lead, _n, dev = _query_inputs([("location", location), ("instance", instance)], ints=("instance",))
+        if facing:                                                      # (a vector plane of its own: checked as a first input is)
+            if _query_inputs([("normal", normal)])[0] != torch_in:
+                raise ValueError("instance, location, normal must all be torch tensors or all numpy arrays")
+            if tuple(normal.shape) != tuple(location.shape):
+                raise ValueError("normal must have the shape %s, got %s" % (tuple(location.shape), tuple(normal.shape)))
+        if len(lead) != 3 or min(lead) < 1:
+            raise ValueError("instance must be [n, h, w] and location [n, h, w, 3], non-empty, got %s" % (tuple(location.shape),))
+        n, h, w = (int(x) for x in lead)
+        P = _visibility_points(points, n, keep_device=torch_in)
+        with _staging(torch_in, stream, dev) as sg:
+            ins = sg.inputs([instance, location, normal if facing else None])
+            out = _visibility_launch(sg, self, dict(instance=ins[0], location=ins[1], normal=ins[2]), n, h, w, P, bias, outputs)
+            res = {k: sg.result(a) for k, a in out.items()}
+        if as_numpy and torch_in:
+            res = {k: a.cpu().numpy() for k, a in res.items()}
+        return res
+
     def info(self):
         b = C.c_size_t(0)
         d = C.c_int32(0)
@@ -1080,12 +1127,20 @@ class Scene:
             pass
 
 
-def _render_gbuffer(call, what, owner, scene, poses, outputs, image, stream, as_numpy):
+def _render_gbuffer(call, what, owner, scene, poses, outputs, image, stream, as_numpy, visibility=None):
     """Camera.render_gbuffer and Sensor.render_gbuffer: the argument checks, the staging and the cut into launches of RT_MAX_BATCH
-    frames.  `call`: rth_camera_render_gbuffer or rth_sensor_render_gbuffer; owner: .h, .width, .height, .current_pose()."""
+    frames.  `call`: rth_camera_render_gbuffer or rth_sensor_render_gbuffer; owner: .h, .width, .height, .current_pose().
+    visibility = (points, bias, mask outputs) (render_visibility): the launches also render the planes the masks are made from,
+    rt_visibility follows them on the same stream, and the result holds the masks beside the planes `outputs` names (which may
+    then be empty)."""
     outputs = tuple(outputs)
-    if [o for o in outputs if o not in _GBUFFER_OUTPUTS] or len(set(outputs)) != len(outputs) or not (outputs or image):
+    if [o for o in outputs if o not in _GBUFFER_OUTPUTS] or len(set(outputs)) != len(outputs) or not (outputs or image or visibility):
         raise ValueError("outputs must be a subset of %s (non-empty unless image=True), nothing twice, got %r" % (_GBUFFER_OUTPUTS, outputs))
+    wanted = outputs
+    if visibility is not None:
+        masks, bias = _visibility_options(visibility[2], visibility[1])
+        needed = ("instance", "location") + (("normal",) if "facing" in masks else ())
+        outputs = outputs + tuple(k for k in needed if k not in outputs)
     if poses is None:
         P = _fa(owner.current_pose()).reshape(1, 6)
     else:
@@ -1096,6 +1151,8 @@ def _render_gbuffer(call, what, owner, scene, poses, outputs, image, stream, as_
     n, h, w = int(P.shape[0]), owner.height, owner.width
     if n * h * w > 2 ** 31 - 1:
         raise ValueError("at most 2^31 - 1 pixels per call, got %d frames of %d x %d" % (n, w, h))
+    if visibility is not None:
+        points = _visibility_points(visibility[0], n)
     with _staging(not as_numpy, stream) as sg:
         out = {k: sg.alloc((n, h, w) + _FIELDS[k][0], _FIELDS[k][1]) for k in outputs}
         img = sg.alloc((n, h, w, 3), np.uint8) if image else None
@@ -1110,7 +1167,10 @@ def _render_gbuffer(call, what, owner, scene, poses, outputs, image, stream, as_
                 base = base.value if isinstance(base, _vp) else int(base)
                 ptrs = (_vp * m)(*[base + (first + i) * h * w * 3 for i in range(m)])
             check(call(owner.h, scene.h, _fp(P[first:first + m]), m, C.byref(planes), ptrs, w * 3, sg.stream, sg.sync), what)
-        res = {k: sg.result(a) for k, a in out.items()}
+        res = {k: sg.result(out[k]) for k in wanted}
+        if visibility is not None:
+            staged = _visibility_launch(sg, scene, {k: sg.ptr(out[k]) for k in needed}, n, h, w, points, bias, masks)
+            res.update({k: sg.result(a) for k, a in staged.items()})
         if image:
             res["image"] = sg.result(img)
         return res
@@ -1217,6 +1277,11 @@ def _point_cloud(call, what, owner, scene, poses, outputs, min_range, max_range,
         return res
 
 
+_RENDER_VISIBILITY_DOC = """Visibility masks of this %s's frames: render_gbuffer for instance, location (normal for "facing") and whatever `gbuffer`
+names -- one launch per RT_MAX_BATCH frames -- then rt_visibility on the same stream (the rule is in include/rt_hip.h, "visibility
+masks"; Scene.visibility has the arguments).  points: [K, 3] world (every frame) or [n, K, 3], n = len(poses); a torch tensor is
+copied to the host first.  Returns a dict of the masks named in `outputs` (int32 [n, h, w]), the `gbuffer` planes and, with
+image=True, "image", as render_gbuffer returns them.  Every ValueError is raised before a device call."""
 _POINT_CLOUD_DOC = """The point cloud of %s frames (rt_point_cloud_offsets%s + rt_point_cloud_fill; the rules are in include/rt_hip.h): the pixels
         whose ray hit something with min_range <= t <= max_range and, with a mask (bool or uint8 [height, width], numpy or torch,
         shared by all frames), mask != 0 -- packed in (frame, y, x) order.  poses: None = the current pose (one frame), or a sequence
@@ -1271,6 +1336,14 @@ class Camera:
         (`outputs` may then be empty).  torch tensors on the current device, allocated and enqueued on `stream` (a torch.cuda.Stream
         or a raw hipStream_t; default the current torch stream) without a synchronise -- or numpy arrays with as_numpy=True."""
         return _render_gbuffer(libs()[1].rth_camera_render_gbuffer, "Camera::render_gbuffer", self, scene, poses, outputs, image, stream, as_numpy)
+
+    VISIBILITY_OUTPUTS = _VISIBILITY_OUTPUTS
+
+    def render_visibility(self, scene, points, poses=None, bias=2.0 ** -10, outputs=("visible",), gbuffer=(), image=False, stream=None,
+                          as_numpy=False):
+        return _render_gbuffer(libs()[1].rth_camera_render_gbuffer, "Camera::render_gbuffer", self, scene, poses, gbuffer, image, stream, as_numpy,
+                               visibility=(points, bias, outputs))
+    render_visibility.__doc__ = _RENDER_VISIBILITY_DOC % "camera"
 
     CLOUD_OUTPUTS = _CLOUD_OUTPUTS                                      # the fields of RtPointCloud
 
@@ -1424,6 +1497,14 @@ class Sensor:
         """Camera.render_gbuffer for this sensor (rt_render_gbuffer_table): every plane but depth is, bit for bit, what
         Scene.trace_rays gives for rays(pose); "image" is the flat shade of that hit, the sky colour on a miss."""
         return _render_gbuffer(libs()[1].rth_sensor_render_gbuffer, "Sensor::render_gbuffer", self, scene, poses, outputs, image, stream, as_numpy)
+
+    VISIBILITY_OUTPUTS = _VISIBILITY_OUTPUTS
+
+    def render_visibility(self, scene, points, poses=None, bias=2.0 ** -10, outputs=("visible",), gbuffer=(), image=False, stream=None,
+                          as_numpy=False):
+        return _render_gbuffer(libs()[1].rth_sensor_render_gbuffer, "Sensor::render_gbuffer", self, scene, poses, gbuffer, image, stream, as_numpy,
+                               visibility=(points, bias, outputs))
+    render_visibility.__doc__ = _RENDER_VISIBILITY_DOC % "sensor"
 
     CLOUD_OUTPUTS = _CLOUD_OUTPUTS
 
@@ -1927,6 +2008,60 @@ def _device_query(scene, inputs, outs, call, stream, shape=(3,), ints=(), scratc
             ws = (None if workspace is None else sg.ptr(workspace), ws_bytes)
         call(h, handle, ins, {k: sg.ptr(a) for k, a in out.items()}, n, sg.stream, sg.sync, *ws)
         return {k: sg.result(a) for k, a in out.items()}
+
+
+def _visibility_options(outputs, bias):
+    """Scene.visibility and the render_visibility wrappers: (outputs as a tuple, bias as a float) or a ValueError"""
+    outputs = _check_outputs(outputs, _VISIBILITY_OUTPUTS)
+    if len(set(outputs)) != len(outputs):
+        raise ValueError("outputs must not name a mask twice, got %r" % (outputs,))
+    ok = isinstance(bias, (int, float, np.integer, np.floating)) and not isinstance(bias, bool)
+    if not ok or not 0.0 <= float(np.float32(bias)) < 1.0:              # (as the C-ABI sees it: a float32; NaN fails both)
+        raise ValueError("bias must be a number in [0, 1), got %r" % (bias,))
+    return outputs, float(bias)
+
+
+def _visibility_points(points, n, keep_device=False):
+    """`points` as float32 [n, K, 3] with 1 <= K <= 32, from [K, 3] (every frame) or [n, K, 3]: a contiguous numpy array -- or, with
+    keep_device, the caller's CUDA tensor in that shape.  Every ValueError before a device call."""
+    is_torch = type(points).__module__.split(".")[0] == "torch"
+    if is_torch:
+        if str(points.dtype) != "torch.float32":
+            raise ValueError("points must be float32, got %s" % points.dtype)
+        P = points
+    else:
+        try:
+            P = np.asarray(points, np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("points must be [K, 3] or [n, K, 3] numbers, got %r" % (type(points),))
+    shape = tuple(P.shape)
+    if len(shape) not in (2, 3) or shape[-1] != 3 or not 1 <= shape[-2] <= 32 or (len(shape) == 3 and shape[0] != n):
+        raise ValueError("points must be [K, 3] or [%d, K, 3] with 1 <= K <= 32, got %s" % (n, shape))
+    K = int(shape[-2])
+    if is_torch and keep_device and P.is_cuda:
+        return P.detach().expand(n, K, 3)                               # (_visibility_launch makes it contiguous, on the call's stream)
+    if is_torch:
+        P = P.detach().cpu().numpy()
+    return np.array(np.broadcast_to(P, (n, K, 3)), np.float32, order="C")      # (a copy of the caller's: writable, contiguous)
+
+
+def _visibility_launch(sg, scene, planes, n, h, w, points, bias, outputs):
+    """rth_scene_visibility on staged planes inside the staging `sg`: planes = the device pointers of instance, location and (for
+    facing) normal, [n, h, w](x3); points [n, K, 3] as _visibility_points gives them.  -> the staged int32 masks by name."""
+    if isinstance(points, np.ndarray):
+        if sg.sync:
+            d_points = sg.inputs([points])[0]
+        else:                                                           # (made under the staging's stream, which orders its reuse)
+            points = sg.torch.from_numpy(points).to(sg.dev)
+            d_points = points.data_ptr()
+    else:
+        points = points.contiguous()
+        d_points = points.data_ptr()
+    out = {k: sg.alloc((n, h, w), np.int32) for k in outputs}
+    masks = RtVisibility(*[sg.ptr(out[k]) if k in out else None for k in _VISIBILITY_OUTPUTS])
+    check(libs()[1].rth_scene_visibility(scene.h, planes["instance"], planes["location"], planes.get("normal"), w, h, n, d_points,
+                                         int(points.shape[1]), bias, C.byref(masks), sg.stream, sg.sync), "Scene::visibility")
+    return out
 
 
 def _xp(a):

@@ -30,6 +30,7 @@ struct RtTriangleHits;
 struct RtSweepHits;
 struct RtRegionCounts;
 struct RtRegionList;
+struct RtVisibility;
 
 class Scene {
 public:
@@ -147,6 +148,12 @@ public:
                        size_t workspace_bytes, void* stream = nullptr, bool synchronize = false);
     int list_in_regions(const float* d_regions, int32_t n, int32_t planes_per_region, const int64_t* d_offsets, int32_t max_hits,
                         const RtRegionList& out, void* stream = nullptr, bool synchronize = false);
+    // Visibility masks on the device scene: rt_visibility of include/rt_hip.h ("visibility masks"), where the rule is.  The planes
+    // ([count][height][width](x3), a G-buffer's instance, location and -- for `facing` -- normal), the points ([count][num_points][3]
+    // world) and the masks are DEVICE arrays.  Returns the status.
+    int visibility(const int32_t* d_instance, const float* d_location, const float* d_normal, int32_t width, int32_t height, int32_t count,
+                   const float* d_points, int32_t num_points, float bias, const RtVisibility& out, void* stream = nullptr,
+                   bool synchronize = false);
     RtScene* d_scene = nullptr;
     int num_mesh_instances = 0;
     int last_error = 0;                             // rt_hip.h status of the last device call (the reference ignores errors)

@@ -771,6 +771,15 @@ int Scene::sweep_spheres(const float* d_segments, const float* d_radius, int32_t
     return last_error;
 }
 
+int Scene::visibility(const int32_t* d_instance, const float* d_location, const float* d_normal, int32_t width, int32_t height, int32_t count,
+                      const float* d_points, int32_t num_points, float bias, const RtVisibility& out, void* stream, bool synchronize)
+{
+    last_error = d_scene ? rt_visibility(d_scene, d_instance, d_location, d_normal, width, height, count, d_points, num_points, bias, &out,
+                                         stream, synchronize ? 1 : 0)
+                         : RT_E_INVALID;
+    return last_error;
+}
+
 int Scene::count_in_regions(const float* d_regions, int32_t n, int32_t planes_per_region, const RtRegionCounts& out, void* stream,
                             bool synchronize)
 {

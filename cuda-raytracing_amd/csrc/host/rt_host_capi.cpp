@@ -193,6 +193,14 @@ int rth_scene_rebuild_mesh(RthScene* s, int32_t mesh_index, const float* tris18,
 }
 int32_t rth_scene_num_mesh_instances(const RthScene* s) { return s->scene.num_mesh_instances; }
 void* rth_scene_device_handle(RthScene* s) { return s->scene.d_scene; }
+int rth_scene_visibility(RthScene* s, const int32_t* d_instance, const float* d_location, const float* d_normal, int32_t width, int32_t height,
+                         int32_t count, const float* d_points, int32_t num_points, float bias, const void* visibility, void* stream,
+                         int synchronize)
+{
+    if (!s || !visibility) return RT_E_INVALID;
+    return s->scene.visibility(d_instance, d_location, d_normal, width, height, count, d_points, num_points, bias,
+                               *(const RtVisibility*)visibility, stream, synchronize != 0);
+}
 void rth_instance_build(const float* pose6, const float* scale3, float* out24)
 {
     MeshInstance in(0, 0, LRE(pose6), F3(scale3));

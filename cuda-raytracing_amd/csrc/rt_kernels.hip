@@ -2439,6 +2439,86 @@ __global__ __launch_bounds__(kQueryBlock, 8) void query_kernel(const RenderParam
     }
 }
 
+// Visibility masks (rt_visibility, include/rt_hip.h "visibility masks"): which of the caller's points see the
+// surface a pixel's primary ray hit.  The rays are made HERE from the staged G-buffer planes: origin = the point L, direction =
+// X - L (not normalised), bound = magnitude(X - L) * (1 - bias), cast as query_kernel<true> casts rt_occluded's rays -- the same
+// cast_ray_ex instantiation, the same any_hit_done, so bit k is exactly `rt_occluded answers 0`.  One wave per workgroup, one 8x8
+// tile of one frame per wave (workgroup (x, y, z) = tile (x, ty0 + y) of frame frame0 + z): a wave's rays share their origin, so they
+// almost always share a sign octant and stay in the hand-written loop.  The frame's point is an expression of blockIdx and the loop
+// counter, hence wave-uniform, and arrives by scalar loads (the address space says the words do not change while the kernel runs).
+// A lane that is outside the frame or whose pixel is a miss leaves before the loop (the miss stores its zeros first), so a wave
+// without a hit is gone at once and the loop's control stays uniform among the lanes that remain.  Across the cast a lane keeps its
+// mask and the address of its LDS column; the pixel and X are derived from the column again for every point (query_kernel's way:
+// registers the loop has no room for; the re-read is 12 bytes per lane from a line the cache holds).  `facing` needs no cast and has
+// a loop of its own after the casts, so that only one mask is carried.  One int32 store per plane and pixel, no atomics, no zero fill.
+struct VisParams {
+    const int32_t* instance;    // staged planes [count][height][width](x3)
+    const float* location;
+    const float* normal;        // null unless facing
+    const float* points;        // [count][num_points][3] world
+    int32_t width, height, num_points;
+    int32_t frame0, ty0;        // this launch's first frame and first tile row (a grid's y and z end at 65 535)
+    float bias;
+    int32_t *visible, *facing;  // [count][height][width], each optional
+};
+typedef const __attribute__((address_space(4))) float* VisPointPtr;
+
+// the pixel of the lane whose LDS column is `column`, and its element in a frame-major plane; false = outside the frame
+__device__ __forceinline__ bool visibility_pixel(const VisParams& v, const lds_int* column, const lds_int* base, size_t& px)
+{
+    const int lane = (int)(column - base);
+    const int x = (int)blockIdx.x * kPrimTile + (lane & 7), y = (v.ty0 + (int)blockIdx.y) * kPrimTile + (lane >> 3);
+    px = (((size_t)v.frame0 + blockIdx.z) * (size_t)v.height + (size_t)y) * (size_t)v.width + (size_t)x;
+    return x < v.width && y < v.height;
+}
+
+__global__ __launch_bounds__(kQueryBlock, 8) void visibility_kernel(const RenderParams p, const VisParams v)
+{
+    static_assert(kQueryBlock == kPrimTile * kPrimTile, "one wave = one 8x8 tile");
+    extern __shared__ int lds_stack[];                          // [lds_rows(stack_depth) + 1][kQueryBlock]
+    lds_int* column = (lds_int*)lds_stack + threadIdx.x;
+    size_t px;
+    if (!visibility_pixel(v, column, (lds_int*)lds_stack, px)) return;
+    if (v.instance[px] < 0) {                                   // rule 8
+        if (v.visible) v.visible[px] = 0;
+        if (v.facing) v.facing[px] = 0;
+        return;
+    }
+    const VisPointPtr pts = (VisPointPtr)(uintptr_t)(v.points + ((size_t)v.frame0 + blockIdx.z) * (size_t)v.num_points * 3);
+    if (v.visible) {
+        int spill[kMaxStack - kLdsStack];
+        QueryStack stack;
+        stack.lds = column; stack.spill = spill; stack.lds_depth = lds_rows(p.stack_depth);
+        const float s = 1.0f - v.bias;                          // rule 3
+        uint32_t mask = 0;
+        for (int k = 0; k < v.num_points; k++) {
+            asm volatile("" : "+v"(stack.lds));
+            visibility_pixel(v, stack.lds, (lds_int*)lds_stack, px);
+            const V3 L = v3(pts[k * 3], pts[k * 3 + 1], pts[k * 3 + 2]);
+            const V3 d = v3(v.location[px * 3] - L.x, v.location[px * 3 + 1] - L.y, v.location[px * 3 + 2] - L.z);      // rule 1
+            const float tmax = magnitude(d) * s;                // rules 2, 4
+            stack.sp = 0;
+            int pops = 0;
+            const Hit hit = cast_ray_ex<false, true, true, QueryStack, true, false, false, true>(p, L, d, stack, pops, tmax);
+            if (!any_hit_done(hit, tmax)) mask |= 1u << k;      // rule 5
+        }
+        asm volatile("" : "+v"(stack.lds));
+        column = stack.lds;
+        visibility_pixel(v, column, (lds_int*)lds_stack, px);
+        v.visible[px] = (int32_t)mask;
+    }
+    if (v.facing) {
+        const V3 X = v3(v.location[px * 3], v.location[px * 3 + 1], v.location[px * 3 + 2]);
+        const V3 n = v3(v.normal[px * 3], v.normal[px * 3 + 1], v.normal[px * 3 + 2]);
+        uint32_t mask = 0;
+        for (int k = 0; k < v.num_points; k++) {
+            const V3 w = v3(pts[k * 3] - X.x, pts[k * 3 + 1] - X.y, pts[k * 3 + 2] - X.z);      // rule 6
+            if (n.x * w.x + n.y * w.y + n.z * w.z > 0.0f) mask |= 1u << k;                      // rule 7
+        }
+        v.facing[px] = (int32_t)mask;
+    }
+}
+
 // Octant binning: a wave of arbitrary rays almost never shares a sign octant, and a wave that does not leaves the hand-written loop.
 // The two passes below sort the ray indices by the sign octant of their WORLD direction (a counting sort of 8 buckets; rays of
 // rotated instances may still differ in mesh space -- those waves fall back per instance, as they would unsorted).  Each workgroup
@@ -7025,6 +7105,38 @@ int rt_occluded(RtScene* s, const float* d_origins, const float* d_directions, c
     memset(&q, 0, sizeof q);
     q.org = d_origins; q.dir = d_directions; q.tmax = d_tmax; q.n = n; q.occluded = d_occluded;
     return launch_query(s, q, true, d_workspace, workspace_bytes, stream, synchronize);
+}
+
+// ---- visibility masks -------------------------------------------------------------------------------------------------------
+int rt_visibility(RtScene* s, const int32_t* d_instance, const float* d_location, const float* d_normal, int32_t width, int32_t height,
+                  int32_t count, const float* d_points, int32_t num_points, float bias, const RtVisibility* out, void* stream,
+                  int synchronize)
+{
+    if (!s || !d_instance || !d_location || !d_points || !out) return RT_E_INVALID;
+    if ((!out->visible && !out->facing) || (out->facing && !d_normal)) return RT_E_INVALID;
+    if (width < 1 || height < 1 || count < 1 || (int64_t)width * height > (int64_t)INT32_MAX / count) return RT_E_INVALID;
+    if (num_points < 1 || num_points > 32 || !(bias >= 0.0f && bias < 1.0f)) return RT_E_INVALID;      // (a NaN fails both)
+    return scene_launch(s, stream, synchronize, [&](hipStream_t st) -> int {
+        RenderParams p;
+        memset(&p, 0, sizeof p);
+        fill_scene(p, s);
+        p.num_frames = 1;
+        VisParams v;
+        memset(&v, 0, sizeof v);
+        v.instance = d_instance; v.location = d_location; v.normal = out->facing ? d_normal : nullptr; v.points = d_points;
+        v.width = width; v.height = height; v.num_points = num_points; v.bias = bias;
+        v.visible = out->visible; v.facing = out->facing;
+        const int tiles_x = (width + kPrimTile - 1) / kPrimTile, tiles_y = (height + kPrimTile - 1) / kPrimTile;
+        const size_t lds = query_shape(kQueryBlock, kQueryBlock, p.stack_depth, 1).lds;     // (+ the optimistic stack's spare row)
+        // a grid's y and z end at 65 535: as many launches as the tile rows and the frames need
+        for (int f0 = 0; f0 < count; f0 += 65535)
+            for (int y0 = 0; y0 < tiles_y; y0 += 65535) {
+                v.frame0 = f0; v.ty0 = y0;
+                const dim3 groups((unsigned)tiles_x, (unsigned)std::min(tiles_y - y0, 65535), (unsigned)std::min(count - f0, 65535));
+                hipLaunchKernelGGL(visibility_kernel, groups, dim3(kQueryBlock), lds, st, p, v);
+            }
+        return RT_OK;
+    });
 }
 
 // ---- point queries ----------------------------------------------------------------------------------------------------------

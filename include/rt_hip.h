@@ -525,6 +525,37 @@ int rt_point_cloud_offsets_rolling(RtScene *scene, const RtRayTable *table, cons
 int rt_point_cloud_fill_rolling(int32_t width, int32_t height, int32_t count, int32_t axis, int32_t slice_pixels, uint32_t fields,
                                 const void *d_workspace, size_t workspace_bytes, int64_t capacity, const RtPointCloud *out,
                                 void *stream, int synchronize);
+/* ---- visibility masks: is the surface a pixel sees also seen from over there?  For every pixel of staged
+ *      G-buffer planes and each of 1..32 caller points per frame -- a projector, the partner camera of a stereo pair, the next pose,
+ *      a point light, an antenna -- one bit: the point sees the pixel's surface hit.  The planes are tight, frame-major DEVICE planes
+ *      in RtGBuffer's layout (`instance`, `location`, `normal`): the output of rt_render_gbuffer, _table or _rolling, or of
+ *      rt_trace_rays reshaped.  Every offset is computed in size_t.
+ *      The rule, for pixel p of frame i with instance[p] >= 0, X = location[p], L = points[i][k]; fp32, each sum left to right,
+ *      nothing contracted:
+ *      1. v = X - L per component.
+ *      2. d = magnitude(v) of rt_math.h: sqrtf(v.x*v.x + v.y*v.y + v.z*v.z).
+ *      3. s = 1.0f - bias.
+ *      4. tmax = d * s.
+ *      5. Bit k of visible[p] is set exactly when rt_occluded answers 0 for origin L, direction v (not normalised) and bound tmax:
+ *         the library's own ray rule, quirks included -- back faces are never hit, a miss is not occluded.  The cast runs from L,
+ *         not from the hit: it is the ray a camera at L casts at that surface point, and the surface's own triangle, met at
+ *         about d, is excluded by the RELATIVE bias.
+ *      6. w = L - X per component.
+ *      7. Bit k of facing[p] is set exactly when normal.x*w.x + normal.y*w.y + normal.z*w.z > 0.  (The world is one-sided: a point
+ *         behind an open sheet sees through it as a camera there would.  Callers who want "lit" take visible & facing.)
+ *      8. A miss (instance < 0) gives 0 in both planes.
+ *      9. Bits >= num_points are 0.
+ *      A pixel whose X, or a point whose L, is non-finite, or a pair with v == 0, does not fault and does not change other pixels or
+ *      bits; its own bit is unspecified.
+ *      Asynchronous on `stream` unless synchronize != 0.  No scene scratch, no view records, no workspace: calls overlap each other
+ *      and renders on other streams, as the ray queries do.  The library splits a call into as many launches as its grid limits need.
+ *      RT_E_INVALID, judged before any device call: a NULL scene, d_instance, d_location, d_points or out; both outputs NULL; facing
+ *      wanted but d_normal NULL; width, height or count < 1; width * height * count > 2^31 - 1; num_points outside 1..32; bias not
+ *      finite or outside [0, 1). -------------------------------------------------------------------------------------------------- */
+typedef struct RtVisibility { int32_t *visible, *facing; } RtVisibility;   /* DEVICE [count][height][width], each optional, at least one */
+int rt_visibility(RtScene *scene, const int32_t *d_instance, const float *d_location, const float *d_normal /* NULL unless facing */,
+                  int32_t width, int32_t height, int32_t count, const float *d_points /* DEVICE [count][num_points][3], world */,
+                  int32_t num_points /* 1..32 */, float bias, const RtVisibility *out, void *stream, int synchronize);
 /* same frame plus the parity planes (instrumented copy of the kernel: counts every visit) */
 int rt_render_debug(RtScene *scene, const RtCameraParams *cam, uint8_t *d_img, size_t pitch,
                     const RtDebugPlanes *planes, void *stream, int synchronize);

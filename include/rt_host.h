@@ -73,6 +73,11 @@ int rth_scene_rebuild_mesh(RthScene *s, int32_t mesh_index, const float *tris18,
 int32_t rth_scene_num_mesh_instances(const RthScene *s);
 /* the RtScene* behind the Scene (for rt_render_debug etc.), NULL before upload */
 void *rth_scene_device_handle(RthScene *s);
+/* Scene::visibility: rt_visibility of rt_hip.h ("visibility masks") on the uploaded scene; visibility: const RtVisibility *.
+ * RT_E_INVALID for a NULL scene or visibility, a scene not uploaded, and rt_visibility's own cases. */
+int rth_scene_visibility(RthScene *s, const int32_t *d_instance, const float *d_location, const float *d_normal, int32_t width,
+                         int32_t height, int32_t count, const float *d_points, int32_t num_points, float bias, const void *visibility,
+                         void *stream, int synchronize);
 /* MeshInstance::build_inv (MeshInstance.hpp:39): out26 = pose6 inv_pose6 rotation3 inv_rotation3 scale3 inv_scale3 (minus ids) */
 void rth_instance_build(const float *pose6, const float *scale3, float *out24);
 
